@@ -4,6 +4,7 @@ bench.py -- MU-iterations/sec of the shift-invariant multiplicative-update loop 
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--path auto|generic|mfma|split|fft|hybrid]
                     [--algorithm full|cyclic --batch-size B] [--no-cpu-baseline] [--no-fft-variant] [--no-parity]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -90,6 +91,7 @@ CONFIGS = {
 PEAK_F32_TFLOPS = 157.3   # MI355X_MICROARCH.md: f32 vector = f32 MFMA
 PEAK_BF16_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense bf16 MFMA (AMD's 5 PF figure includes 2:1 sparsity)
 PEAK_HBM_GBS = 8000.0
+DUMP_BYTES = 60 << 20   # --dump-outputs: payload of all .npy files (the limit is 64 MB; headers and rounding fit beside it)
 
 
 def conv_flops(cfg, n):
@@ -124,6 +126,29 @@ def synth_V_on_device(cfg, n_local, seed, device):
     torch.cuda.empty_cache()
     torch.cuda.set_rng_state(gen_state, device)
     return out
+
+
+def dump_outputs(out_dir, W, H, seed=0):
+    """--dump-outputs: what the timed path hands its caller after the last timed step, as .npy files in `out_dir`.
+    W.npy in full; H.npy in full when it fits beside W in DUMP_BYTES, else H_sample.npy: the elements of H at a fixed
+    set of flat indices (np.unique of `seed`-ed uniform draws over H.numel(), ascending), so that every build of the
+    project dumps the same elements for the same arguments.  Returns {name: shape}."""
+    import torch
+    for t in (W, H):
+        assert t.dtype in (torch.float32, torch.float64), t.dtype
+    os.makedirs(out_dir, exist_ok=True)
+    W, H = W.detach(), H.detach()
+    out = {'W': W.cpu().numpy()}
+    room = (DUMP_BYTES - W.numel() * W.element_size()) // H.element_size()
+    if H.numel() <= room:
+        out['H'] = H.cpu().numpy()
+    else:
+        flat = np.unique(np.random.default_rng(seed).integers(0, H.numel(), size=room))
+        idx = tuple(torch.from_numpy(i).to(H.device) for i in np.unravel_index(flat, H.shape))
+        out['H_sample'] = H[idx].cpu().numpy()     # (H may be a strided view of padded rows: index, do not reshape)
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(arr))
+    return {name: arr.shape for name, arr in out.items()}
 
 
 # kernel group of the timeline -> kernel family -> (name of its main kernel as rocprof prints it, further kernels)
@@ -322,6 +347,9 @@ def main():
                     help='--gpus N > 1: further timed legs beside the weak-scaling headline, comma separated: strong '
                          '(config 3, 256 GLOBAL samples, 256 / N per GPU), config4 / config5 (Cyclic-MU epochs on the '
                          'per-GPU shards of BASELINE configs[3] / configs[4], one collective per epoch); "none" skips them')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write W and H of the headline model (rank 0; H sampled when large) as '
+                         'DIR/<name>.npy, for output-by-output comparisons of two builds')
     ap.add_argument('--leg-steps', type=int, default=None, help='timed steps of the further legs (default: min(steps, 20); '
                     'config5: min(steps, 8))')
     args = ap.parse_args()
@@ -517,6 +545,8 @@ def main():
         return model, float(t.item()), spans, paths
 
     nmf, elapsed, spans, paths = run_leg(args.path, group)
+    if args.dump_outputs and rank == 0:   # outside the timed region, before anything else touches the model
+        dump_outputs(args.dump_outputs, nmf._W, nmf._H)
     be = nmf._backend
     energy = nmf._energy_function()     # collective when sharded; outside the timed region
     last_family = be.last_path

@@ -1,10 +1,13 @@
 """bench.py's host-side helpers (no GPU): the stamp that says whether the committed profiles belong to the kernel sources
-in the tree, the self-launch command of `--gpus N`, and the traffic tool's difference-of-two-runs arithmetic."""
+in the tree, the self-launch command of `--gpus N`, the traffic tool's difference-of-two-runs arithmetic and the files of
+`--dump-outputs`."""
 import csv
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -87,3 +90,30 @@ def test_traffic_per_iteration_is_the_difference_of_two_runs(tmp_path):
     assert abs(d['iteration_bytes'] - per_it) < 1e-6 * per_it               # k_b cancels entirely, k_a's set-up launch too
     assert d['per_kernel'][A]['bytes_per_launch'] == (2 * 1000.0 + 500.0) * 1024 and d['per_kernel'][A]['launches_per_iteration'] == 1.0
     assert d['per_kernel'][B]['bytes_per_iteration'] == 0.0
+
+
+def test_dump_outputs_writes_W_and_H_or_a_fixed_sample_of_H(tmp_path, monkeypatch):
+    """--dump-outputs: W in full; H in full when it fits the budget, else the same seeded sample of its elements in every
+    run (H here a strided view of padded rows, as the backend may hold it); float32 / float64 only, within 64 MB."""
+    import numpy as np
+    import torch
+    assert bench.DUMP_BYTES <= 64 << 20
+    W = torch.rand(4, 1, 3, 3)
+    H = torch.rand(5, 4, 10, 12)
+    assert bench.dump_outputs(str(tmp_path / 'full'), W, H) == {'W': (4, 1, 3, 3), 'H': (5, 4, 10, 12)}
+    assert np.array_equal(np.load(tmp_path / 'full' / 'W.npy'), W.numpy())
+    assert np.array_equal(np.load(tmp_path / 'full' / 'H.npy'), H.numpy())
+
+    Wd = W.double()
+    Hp = torch.rand(5, 4, 10, 16, dtype=torch.float64)[..., :12]
+    monkeypatch.setattr(bench, 'DUMP_BYTES', Wd.numel() * 8 + 100 * 8)
+    for d in ('a', 'b'):
+        assert set(bench.dump_outputs(str(tmp_path / d), Wd, Hp)) == {'W', 'H_sample'}
+    assert not (tmp_path / 'a' / 'H.npy').exists()
+    s = np.load(tmp_path / 'a' / 'H_sample.npy')
+    assert s.dtype == np.float64 and 0 < s.size <= 100
+    assert np.array_equal(s, np.load(tmp_path / 'b' / 'H_sample.npy'))
+    flat = np.unique(np.random.default_rng(0).integers(0, Hp.numel(), size=100))
+    assert np.array_equal(s, Hp.numpy().reshape(-1)[flat])
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / 'c'), W.half(), H)

@@ -596,6 +596,38 @@ def test_bench_line_contract():
     assert p['W_rel_diff_vs_oracle'] < 1e-5 and p['H_rel_diff_vs_oracle'] < 1e-5 and p['energy_gap_vs_oracle'] < 1e-5
 
 
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR` on BASELINE config 2: W and a fixed sample of H (H alone is 76 MB) after the last
+    timed step, float32, within 64 MB.  The inputs are the same in every run and --steps is the number of timed steps:
+    warmup 1 + 3 steps and warmup 2 + 2 steps are the same four iterations from the same start -- the same outputs --
+    and warmup 1 + 2 steps are not."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
+    dumps = {}
+    for warmup, steps in ((1, 3), (2, 2), (1, 2)):
+        d = tmp_path / f'w{warmup}s{steps}'
+        out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--config', '2', '--steps', str(steps),
+                              '--warmup', str(warmup), '--no-cpu-baseline', '--no-fft-variant', '--no-parity',
+                              '--dump-outputs', str(d)], env=env, capture_output=True, text=True, timeout=300, cwd=root)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith('{')]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line['steps'] == steps and line['warmup'] == warmup and line['ms_per_step'] > 0
+        assert sorted(os.listdir(d)) == ['H_sample.npy', 'W.npy']
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+        dumps[warmup, steps] = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    a, b, c = dumps[1, 3], dumps[2, 2], dumps[1, 2]
+    assert a['W'].shape == (16, 1, 9, 9) and a['W'].dtype == np.float32 and a['H_sample'].dtype == np.float32
+    assert a['H_sample'].size > 1 << 20 and np.isfinite(a['H_sample']).all() and (a['W'] >= 0).all()
+    for name in ('W', 'H_sample'):
+        assert relmax(b[name], a[name]) < 1e-6, name
+    assert relmax(c['W'], a['W']) > 1e-6
+
+
 def test_bench_launches_its_own_ranks(tmp_path):
     """The form the driver's SCALE run takes: plain `python bench.py --gpus 2 ...` with no WORLD_SIZE in the environment.
     bench.py starts the two ranks itself as CHILD processes (torch.distributed.run) before it touches the GPU and relays
