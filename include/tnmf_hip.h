@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define TNMF_HIP_ABI_VERSION 7
+#define TNMF_HIP_ABI_VERSION 8
 
 enum {
     TNMF_OK = 0,
@@ -252,6 +252,7 @@ typedef struct {
     int n0, n1;  /* sample range [n0, n1) of the resident problem (may be empty) */
     double a, b; /* TNMF_OP_GRAD_W */
 } tnmf_hip_op;
+/* (Frobenius objective only: the beta-divergence steps below are driven step by step.) */
 int tnmf_hip_run_schedule(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, void *W_inout, void *H_inout,
                           void *R_scratch, void *acc, const tnmf_hip_op *ops, int n_ops, double eps, double sparsity,
                           void *stream);
@@ -274,6 +275,44 @@ int tnmf_hip_sum_parts(tnmf_hip_ctx *ctx, int dtype, const void *parts, int n_pa
  * `pos` is left incremented by eps, like the reference's in-place `pos += eps`. */
 int tnmf_hip_apply_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, void *W_inout, void *negpos, double eps,
                      void *stream);
+
+/* ---- beta-divergence objectives (ABI 8) ----------------------------------------------------------------------------
+ * D_beta(V | R): beta = 2 is the Frobenius objective of every entry above, 1 Kullback-Leibler, 0 Itakura-Saito, any other
+ * finite beta the general form.  The multiplicative updates (Serizel et al. 2016, the mini-batch algorithms the reference
+ * names, tnmf/TransformInvariantNMF.py:135-139) are those of the Frobenius objective with (V, R) replaced by the fields
+ *   R~ = max(R, 0) + eps,   Q = V * R~^(beta-2),   P = R~^(beta-1)
+ *   H <- H * corr_W(W, Q) / (corr_W(W, P) + eps + sparsity [+ lateral terms]),   W <- W * corr_H(H, Q) / (corr_H(H, P) + eps)
+ * so every kernel family, reconstruction mode, row stride and lateral epilogue of the Frobenius steps runs unchanged on
+ * (Q, P).  With beta == 2 every entry below IS its Frobenius counterpart (same call, same bits).  With beta != 2:
+ *   - volumes (ndim == 3) answer TNMF_E_UNSUPPORTED and non-finite beta likewise, before anything is written;
+ *   - Q lives in a work buffer of the context allocated by the first such call (tnmf_hip_ctx_reserve does not size it):
+ *     a caller that captures the calls into a graph makes one warm-up call first;
+ *   - P overwrites the reconstruction in R_scratch (or the context's scratch);
+ *   - the FFT family never takes Q for the samples whose spectra it caches (Q has a fixed address and new contents every
+ *     call): the spectra of V are neither reused nor recorded for it, those of H are kept as for the Frobenius steps.
+ * tnmf_hip_run_schedule stays Frobenius-only. */
+
+/* Q = V * R~^(beta-2), P = R~^(beta-1) elementwise over n_elems elements of type dtype.  beta 0, 1, 2: divisions and
+ * products only (beta 1 writes P = 1); any other beta: pow in the element type.  P may alias R; nothing else may alias. */
+int tnmf_hip_beta_fields(tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *R, void *Q,
+                         void *P, size_t n_elems, void *stream);
+
+/* tnmf_hip_update_H_ex for D_beta: reconstruct, fields, then the same correlations and update with (Q, P). */
+int tnmf_hip_update_H_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *V, const void *W,
+                           void *H_inout, void *R_scratch, double eps, double sparsity, double inhibition,
+                           double cross_inhibition, const double *kernel0, int len0, const double *kernel1, int len1,
+                           const double *kernel2, int len2, double beta, void *stream);
+
+/* tnmf_hip_grad_W_fused for D_beta: negpos = [corr_H(H, Q) | corr_H(H, P)] as one [2,M,C,*A] buffer -- the same buffer
+ * the collective carries and tnmf_hip_apply_W consumes.  r_is_valid != 0: R_scratch holds reconstruct(W, H) (it is
+ * overwritten with P). */
+int tnmf_hip_grad_W_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *W, const void *H,
+                         void *R_scratch, int r_is_valid, void *negpos, double beta, double eps, void *stream);
+
+/* *out_host = sum D_beta(V | max(R, 0) + eps) in double (beta 1: V log(V/R~) - V + R~ with 0 log 0 = 0; beta 0:
+ * V/R~ - log(V/R~) - 1), deterministic two-stage reduction.  beta == 2: tnmf_hip_energy.  Synchronises. */
+int tnmf_hip_energy_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, double beta, double eps, const void *V,
+                         const void *W, const void *H, double *out_host, void *stream);
 
 #ifdef __cplusplus
 }

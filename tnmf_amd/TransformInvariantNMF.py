@@ -67,6 +67,27 @@ def _joined(batches: list) -> list:
     return [slice(lo, hi) for lo, hi in out]
 
 
+_BETA_NAMES = {'frobenius': 2., 'kullback-leibler': 1., 'itakura-saito': 0.}
+
+# the hooks a backend needs for a beta-divergence objective other than the Frobenius norm
+_BETA_HOOKS = ('fused_update_H_beta', 'fused_update_W_beta', 'local_gradient_W_beta', 'reconstruction_energy_beta')
+
+
+def beta_loss_value(beta_loss) -> float:
+    """beta of ``beta_loss``: scikit-learn's names ('frobenius' 2, 'kullback-leibler' 1, 'itakura-saito' 0) or a finite
+    number; anything else raises ValueError."""
+    if isinstance(beta_loss, str):
+        if beta_loss not in _BETA_NAMES:
+            raise ValueError(f'beta_loss must be one of {sorted(_BETA_NAMES)} or a finite float, not {beta_loss!r}')
+        return _BETA_NAMES[beta_loss]
+    if isinstance(beta_loss, (bool, np.bool_)) or not isinstance(beta_loss, (int, float, np.integer, np.floating)):
+        raise ValueError(f'beta_loss must be one of {sorted(_BETA_NAMES)} or a finite float, not {beta_loss!r}')
+    beta = float(beta_loss)
+    if not np.isfinite(beta):
+        raise ValueError(f'beta_loss must be finite, not {beta_loss!r}')
+    return beta
+
+
 def _backend_registry():
     from .backends.HIP import HIP_Backend
     return {'hip': HIP_Backend}
@@ -86,13 +107,18 @@ class TransformInvariantNMF:
     backend : ``'hip'`` or a :class:`~tnmf_amd.backends._Backend.Backend` instance
     logger, verbose : as in the reference (0 errors .. 3 debug)
     use_fused_updates : use the backend's fused half-step kernels when no inhibition term is requested
+    beta_loss : the objective, D_beta(V | R): ``'frobenius'`` / 2 (default, 1/2 ||V - R||^2), ``'kullback-leibler'`` / 1,
+                ``'itakura-saito'`` / 0 or any finite float (scikit-learn's names).  beta != 2 runs the multiplicative
+                updates of Serizel et al. 2016 on the backend's beta hooks, step by step (no one-call schedules), and the
+                energy reports D_beta of R + eps; it needs V > 0 for beta <= 0.
     **kwargs : forwarded to the backend constructor (``reconstruction_mode``, ``device``, ``path``, ``init``,
                ``process_group``)
     """
 
     def __init__(self, n_atoms: int, atom_shape: Tuple[int, ...], inhibition_range: Union[int, Tuple[int, ...]] = None,
                  backend: Union[str, Backend] = 'hip', logger: logging.Logger = None, verbose: int = 0,
-                 use_fused_updates: bool = True, **kwargs):
+                 use_fused_updates: bool = True, beta_loss: Union[str, float] = 2., **kwargs):
+        self._beta = beta_loss_value(beta_loss)
         self.atom_shape = tuple(atom_shape)
         self.n_atoms = n_atoms
         k = len(self.atom_shape)
@@ -115,6 +141,12 @@ class TransformInvariantNMF:
             self._backend = registry[backend.lower()](**kwargs)
         else:
             self._backend = backend
+
+        if self._beta != 2.:
+            missing = [h for h in _BETA_HOOKS if getattr(self._backend, h, None) is None]
+            if missing:
+                raise NotImplementedError(f'beta_loss={beta_loss!r}: the backend {type(self._backend).__name__} has no '
+                                          f'beta-divergence hooks ({", ".join(missing)})')
 
         self._logger = logger if logger is not None else logging.getLogger(self.__class__.__name__)
         self._logger.setLevel([logging.ERROR, logging.WARNING, logging.INFO, logging.DEBUG][verbose])
@@ -148,7 +180,14 @@ class TransformInvariantNMF:
     def R_partial(self, i_atom: int) -> np.ndarray:
         return self._backend.to_ndarray(self._backend.partial_reconstruct(self._W, self._H, i_atom))
 
+    @property
+    def beta_loss(self) -> float:
+        """beta of the objective D_beta (2: Frobenius)."""
+        return self._beta
+
     def _energy_function(self) -> float:
+        if self._beta != 2.:
+            return self._backend.reconstruction_energy_beta(self._V, self._W, self._H, beta=self._beta, eps=self.eps)
         return self._backend.reconstruction_energy(self._V, self._W, self._H)
 
     # -- elementwise multiplicative update (reference :217-238) ----------------------------------------------
@@ -170,6 +209,9 @@ class TransformInvariantNMF:
         return getattr(self._backend, name, None) if self._use_fused else None
 
     def _update_W(self, s: slice = sliceNone):
+        if self._beta != 2.:
+            self._backend.fused_update_W_beta(self._V, self._W, self._H, s, beta=self._beta, eps=self.eps)
+            return
         fused = self._fused('fused_update_W')
         if fused is not None:
             fused(self._V, self._W, self._H, s, eps=self.eps)
@@ -180,6 +222,13 @@ class TransformInvariantNMF:
 
     def _update_H(self, s: slice = sliceNone, sparsity: float = 0., inhibition: float = 0., cross_inhibition: float = 0.):
         lateral = inhibition > 0 or cross_inhibition > 0
+        if self._beta != 2.:
+            # (no fall-back to the Frobenius lines below: a step the backend cannot take raises)
+            kw = dict(inhibition=inhibition, cross_inhibition=cross_inhibition,
+                      inhibition_kernels=self._inhibition_kernels_1D) if lateral else {}
+            self._backend.fused_update_H_beta(self._V, self._W, self._H, s, beta=self._beta, sparsity=sparsity,
+                                              eps=self.eps, **kw)
+            return
         fused = self._fused('fused_update_H')
         if fused is not None:
             try:
@@ -239,6 +288,11 @@ class TransformInvariantNMF:
             self._logger.info(f'{what}: {step}\tEnergy function: {self._energy_function()}')
         return True
 
+    def _check_beta_samples(self, V: np.ndarray):
+        # (R^(beta-1) and V / R of a zero sample: the divergence is not defined there -- scikit-learn refuses the same)
+        if self._beta <= 0 and np.any(V == 0):
+            raise ValueError(f'beta_loss={self._beta} <= 0 needs V without zeros')
+
     # -- full batch (reference :282-348) ------------------------------------------------------------------------
     def fit_batch(self, V: np.ndarray, n_iterations: int = 1000, update_H: bool = True, update_W: bool = True,
                   keep_W: bool = False, sparsity_H: float = 0., inhibition_strength: float = 0.,
@@ -246,6 +300,7 @@ class TransformInvariantNMF:
         assert np.all(V >= 0)
         assert update_H or update_W
         assert sparsity_H >= 0 and inhibition_strength >= 0 and cross_atom_inhibition_strength >= 0
+        self._check_beta_samples(V)
         self._initialize_matrices(V, keep_W)
         h_args = dict(sparsity=sparsity_H, inhibition=inhibition_strength,
                       cross_inhibition=cross_atom_inhibition_strength)
@@ -263,6 +318,7 @@ class TransformInvariantNMF:
         assert np.all(V >= 0)
         assert sparsity_H >= 0 and inhibition_strength >= 0 and cross_atom_inhibition_strength >= 0
         assert isinstance(algorithm, MiniBatchAlgorithm)
+        self._check_beta_samples(V)
         # The reference decides whether to shuffle V with `algorithm in (5, 6, 7, 8)` (:410), an Enum-vs-int test
         # that is never true, so V is never shuffled; this front end keeps that behaviour.
         self._initialize_matrices(V, keep_W)
@@ -284,9 +340,19 @@ class TransformInvariantNMF:
                 break
         self._logger.info('MiniBatch TNMF finished.')
 
+    def _local_gradient_W(self):
+        """The backend's hook for this rank's [neg | pos] of the W gradient (not yet summed over ranks), or None."""
+        if self._beta != 2.:
+            return lambda V, W, H, s: self._backend.local_gradient_W_beta(V, W, H, s, beta=self._beta, eps=self.eps)
+        return self._fused('local_gradient_W')
+
     def _blend_gradient_W(self, acc, lam: float, s: slice):
         """acc <- (1 - lam) * acc + lam * grad_W(batch s); lam == 1 is a plain sum (reference :444-455)."""
-        neg, pos = self._backend.reconstruction_gradient_W(self._V, self._W, self._H, s)
+        if self._beta != 2.:
+            negpos = self._backend.all_reduce_gradient_W(self._local_gradient_W()(self._V, self._W, self._H, s))
+            neg, pos = negpos[0], negpos[1]
+        else:
+            neg, pos = self._backend.reconstruction_gradient_W(self._V, self._W, self._H, s)
         if acc is None:
             # the reference starts from the integers (0, 0): `0 + g` / `0 * (1 - lam) + lam * g`
             if lam == 1:
@@ -311,7 +377,7 @@ class TransformInvariantNMF:
     # acc = a * acc + b * gradient_W(batch), ('W',) for the W update from acc -- where the backend offers that and no
     # lateral term is on (those go through tnmf_hip_update_H_ex batch by batch).
     def _scheduler(self, h_args):
-        run = self._fused('run_schedule') if self._use_schedules else None
+        run = self._fused('run_schedule') if self._use_schedules and self._beta == 2. else None
         if run is None or not getattr(self._backend, 'supports_schedules', False):
             return None
         if h_args['inhibition'] > 0 or h_args['cross_inhibition'] > 0:
@@ -335,7 +401,7 @@ class TransformInvariantNMF:
             run(self._V, self._W, self._H, ops + [('W',)], self._backend.new_gradient_accumulator(self._W),
                 sparsity=h_args['sparsity'], eps=self.eps)
             return None
-        local = self._fused('local_gradient_W')
+        local = self._local_gradient_W()
         lateral = h_args['inhibition'] > 0 or h_args['cross_inhibition'] > 0
         if local is not None and not lateral:
             # sum this rank's [neg | pos] over its batches, ONE all-reduce per epoch, then the fused MU

@@ -11,7 +11,7 @@ from typing import Optional, Sequence
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libtnmf_hip.so')
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 # every symbol include/tnmf_hip.h declares
 EXPORTS = (
@@ -24,6 +24,7 @@ EXPORTS = (
     'tnmf_hip_ctx_last_schedule_persistent',
     'tnmf_hip_ctx_cache_counters', 'tnmf_hip_sum_parts',
     'tnmf_hip_update_H_ex', 'tnmf_hip_run_schedule', 'tnmf_hip_axpby', 'tnmf_hip_convolve_axis',
+    'tnmf_hip_beta_fields', 'tnmf_hip_update_H_beta', 'tnmf_hip_grad_W_beta', 'tnmf_hip_energy_beta',
 )
 
 MODES = {'valid': 0, 'full': 1, 'circular': 2, 'reflect': 3}
@@ -109,6 +110,11 @@ def load() -> ctypes.CDLL:
     lib.tnmf_hip_apply_W.argtypes = [vp, gp, vp, vp, cd, vp]
     lib.tnmf_hip_sum_parts.argtypes = [vp, ci, vp, ci, sz, vp, vp]
     lib.tnmf_hip_axpby.argtypes = [vp, ci, vp, vp, cd, cd, sz, vp]
+    lib.tnmf_hip_beta_fields.argtypes = [vp, ci, cd, cd, vp, vp, vp, vp, sz, vp]
+    lib.tnmf_hip_update_H_beta.argtypes = [vp, gp, ci, vp, vp, vp, vp, cd, cd, cd, cd, ctypes.POINTER(cd), ci,
+                                           ctypes.POINTER(cd), ci, ctypes.POINTER(cd), ci, cd, vp]
+    lib.tnmf_hip_grad_W_beta.argtypes = [vp, gp, vp, vp, vp, vp, ci, vp, cd, cd, vp]
+    lib.tnmf_hip_energy_beta.argtypes = [vp, gp, cd, cd, vp, vp, vp, ctypes.POINTER(cd), vp]
     lib.tnmf_hip_pad_H.argtypes = [vp, gp, ci, vp, vp, vp]
     lib.tnmf_hip_fold_H.argtypes = [vp, gp, ci, vp, vp, vp]
     for name in EXPORTS:

@@ -657,6 +657,118 @@ class HIP_Backend(Backend):
         else:
             self._note_H_cache(Hs, W)
 
+    # -- beta-divergence objectives (tnmf_hip_update_H_beta / _grad_W_beta / _energy_beta) ---------------------------
+    # The multiplicative updates of D_beta are those of the Frobenius objective with (V, R) replaced by the fields
+    # Q = V * R~^(beta-2), P = R~^(beta-1) of R~ = R + eps (include/tnmf_hip.h, "beta-divergence objectives"); beta == 2
+    # is the Frobenius call itself.  Volumes are not covered.
+    def _check_beta_geometry(self):
+        if len(self.atom_shape) == 3:
+            raise NotImplementedError('beta-divergence objectives other than the Frobenius norm: 1 or 2 shift axes only')
+
+    def fused_update_H_beta(self, V, W: torch.Tensor, H: torch.Tensor, s: slice = sliceNone, beta: float = 2.,
+                            sparsity: float = 0., eps: float = 1e-9, inhibition: float = 0., cross_inhibition: float = 0.,
+                            inhibition_kernels: Optional[Sequence[np.ndarray]] = None) -> None:
+        """One H half step of the D_beta objective, in place, for every reconstruction mode and lateral term."""
+        self._check_beta_geometry()
+        ls = self._local(s)
+        Hs, Vs = H[ls], self._V_dev[ls]
+        if Hs.shape[0] == 0:
+            return
+        self._check_W(W)
+        self._check_H(Hs, W.shape[0])
+        lateral = inhibition > 0 or cross_inhibition > 0
+        k = len(self.atom_shape)
+        ks = [np.ascontiguousarray(kk, dtype=np.float64) for kk in (inhibition_kernels or ())] if lateral else []
+        if lateral and len(ks) != k:
+            raise ValueError('one inhibition kernel per shift axis')
+        kp = [kk.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) for kk in ks] + [None, None, None]
+        kl = [len(kk) for kk in ks] + [0, 0, 0]
+        Rs = self._R_scratch[ls]
+        if self._mode == 0:
+            self._validate_H_cache(Hs, W)   # (the library drops the spectra of the samples it updates itself)
+        else:
+            self._foreign_H()
+
+        def run(Hc, ld):
+            with self._timed('update_H'):
+                rc = self._lib.tnmf_hip_update_H_beta(
+                    self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)), self._mode, _ptr(Vs), _ptr(W),
+                    _ptr(Hc), _ptr(Rs), float(eps), float(sparsity), float(inhibition), float(cross_inhibition),
+                    kp[0], kl[0], kp[1], kl[1], kp[2], kl[2], float(beta), self._stream())
+            return rc, 'tnmf_hip_update_H_beta'
+
+        try:
+            if self._mode != 0:
+                assert Hs.is_contiguous()
+                rc, where = run(Hs, 0)
+                _lib.check(rc, where)
+                self._foreign_H()
+            elif self._call_H(Hs, True, run):
+                self._foreign_H()   # the library updated (and kept spectra of) a temporary copy
+            else:
+                self._note_H_cache(Hs, W)
+        except _lib.TnmfHipError as exc:
+            self._foreign_H()
+            if exc.code == _lib.E_UNSUPPORTED and lateral:
+                raise NotImplementedError('lateral terms outside the fused kernel') from exc
+            raise
+
+    def local_gradient_W_beta(self, V, W: torch.Tensor, H: torch.Tensor, s: slice = sliceNone, beta: float = 2.,
+                              eps: float = 1e-9) -> torch.Tensor:
+        """This rank's [neg | pos] = [corr_H(H, Q) | corr_H(H, P)] as one [2, M, C, *A] buffer, NOT yet summed over ranks."""
+        self._check_beta_geometry()
+        ls = self._local(s)
+        Hs, Vs = H[ls], self._V_dev[ls]
+        self._check_W(W)
+        self._check_H(Hs, W.shape[0])
+        if self._mode == 0:
+            self._validate_H_cache(Hs, W)
+        else:
+            self._foreign_H()
+        Hs = self._pad(Hs)
+        negpos = torch.empty_like(self._negpos)
+        Rs = self._R_scratch[ls] if Hs.shape[0] else None
+
+        def run(Hc, ld):
+            with self._timed('grad_W'):
+                rc = self._lib.tnmf_hip_grad_W_beta(self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)),
+                                                    _ptr(Vs), _ptr(W), _ptr(Hc), _ptr(Rs), 0, _ptr(negpos), float(beta),
+                                                    float(eps), self._stream())
+            return rc, 'tnmf_hip_grad_W_beta'
+
+        copied = self._call_H(Hs, False, run)
+        if copied or self._mode != 0:
+            self._foreign_H()   # the spectra the library may have kept belong to a temporary
+        elif Hs.shape[0]:
+            self._note_H_cache(Hs, W)
+        return negpos
+
+    def fused_update_W_beta(self, V, W: torch.Tensor, H: torch.Tensor, s: slice = sliceNone, beta: float = 2.,
+                            eps: float = 1e-9) -> None:
+        """One W half step of the D_beta objective, in place: local gradient, the same collective as fused_update_W
+        (only the [neg | pos] buffer crosses ranks), MU + normalise."""
+        negpos = self.local_gradient_W_beta(V, W, H, s, beta=beta, eps=eps)
+        self._all_reduce(negpos)
+        self.apply_W(W, negpos, eps)
+
+    def reconstruction_energy_beta(self, V, W: torch.Tensor, H: torch.Tensor, beta: float = 2.,
+                                   eps: float = 1e-9) -> float:
+        """sum D_beta(V | R + eps) (beta == 2: 1/2 sum (V - R)^2) -> tnmf_hip_energy_beta (+ all-reduce)."""
+        self._check_beta_geometry()
+        self._check_W(W)
+        self._foreign_H()
+        self._check_H(H, W.shape[0])
+        H = self._pad(H)
+        out = ctypes.c_double(0.0)
+        self._call_H(H, False, lambda Hc, ld: (self._lib.tnmf_hip_energy_beta(
+            self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)), float(beta), float(eps),
+            _ptr(self._V_dev), _ptr(W), _ptr(Hc), ctypes.byref(out), self._stream()), 'tnmf_hip_energy_beta'))
+        if self._world > 1:
+            t = torch.tensor([out.value], dtype=torch.float64, device=self._device)
+            self._all_reduce(t)
+            return float(t.item())
+        return float(out.value)
+
     # -- a whole mini-batch epoch in one call -------------------------------------------------------------------
     @property
     def supports_schedules(self) -> bool:

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "beta.h"
 #include "fft.h"
 #include "generic.h"
 #include "mfma.h"
@@ -304,6 +305,22 @@ int do_corr_H(tnmf_hip_ctx *ctx, const Geo &g, int dtype, const Scratch &sc, con
 }
 
 
+// beta-divergence steps (beta != 2): the fields of R (ctx->qb receives Q, R is overwritten with P); *Q_out = Q.  Q sits at
+// a fixed address with new contents every call: the FFT family is told never to take it for the samples it caches.
+int beta_fields_of(tnmf_hip_ctx *ctx, const Geo &g, int dtype, double beta, double eps, const void *V, void *R,
+                   const void **Q_out, hipStream_t s) {
+    const size_t n = (size_t)g.N * g.C * g.Dy * g.Dx;
+    CHECK(ensure_buffer(&ctx->qb, &ctx->qb_bytes, align_up(n * esize(dtype), 256), false));
+    ctx->fft.V_volatile = ctx->qb;
+    CHECK(launch_beta_fields(ctx, dtype, beta, eps, V, R, ctx->qb, R, n, s));
+    *Q_out = ctx->qb;
+    return TNMF_OK;
+}
+
+static_assert(kBetaPartials <= kEnergyPartials, "the energy words of the scratch hold the beta partials");
+
+inline bool beta_ok(double beta) { return beta == beta && beta - beta == 0.0; }   // finite
+
 // ---- three shift axes: the entry points below hand over to these (same argument meaning, C-contiguous H)
 int vol_api_reconstruct(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *W, const void *H, void *R, void *stream) {
     VOL_ENTER(ctx, geom);
@@ -577,13 +594,14 @@ int tnmf_hip_ctx_create(int device_id, tnmf_hip_ctx **out) {
 int tnmf_hip_ctx_destroy(tnmf_hip_ctx *ctx) {
     if (!ctx) return TNMF_OK;
     int rc = TNMF_OK;
-    if (ctx->ws || ctx->fft.ws || ctx->wimg || ctx->hw) {
+    if (ctx->ws || ctx->fft.ws || ctx->wimg || ctx->hw || ctx->qb) {
         (void)hipSetDevice(ctx->device);
         (void)hipDeviceSynchronize();
     }
     fft_release(ctx);
     split_release(ctx);
     if (ctx->hw) (void)hipFree(ctx->hw);
+    if (ctx->qb) (void)hipFree(ctx->qb);
     for (int i = 0; i < tnmf_hip_ctx::kOpSlots; ++i) {
         if (ctx->ops_done[i]) (void)hipEventDestroy(ctx->ops_done[i]);
         if (ctx->ops_pinned[i]) (void)hipHostFree(ctx->ops_pinned[i]);
@@ -771,6 +789,40 @@ int tnmf_hip_energy(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V,
     return TNMF_OK;
 }
 
+int tnmf_hip_energy_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, double beta, double eps, const void *V,
+                         const void *W, const void *H, double *out_host, void *stream) {
+    if (beta == 2.0) return tnmf_hip_energy(ctx, geom, V, W, H, out_host, stream);
+    if (!ctx || !geom) return TNMF_E_NULL;
+    if (is_vol(geom) || !beta_ok(beta)) return TNMF_E_UNSUPPORTED;
+    ENTER(ctx, geom);
+    if (!out_host) return TNMF_E_NULL;
+    if (g.N == 0) {
+        *out_host = 0.0;
+        return TNMF_OK;
+    }
+    if (!V || !W || !H) return TNMF_E_NULL;
+    const Scratch sc = plan_scratch(ctx, g, dtype);
+    CHECK(ensure_scratch(ctx, sc.total));
+    void *Rs = ws_at(ctx, sc.r_off);
+    CHECK(do_reconstruct(ctx, g, dtype, W, H, Rs, s));
+    double *red = reinterpret_cast<double *>(ws_at(ctx, sc.red_off));   // (kEnergyPartials == kBetaPartials words + result)
+    CHECK(launch_beta_energy(ctx, dtype, beta, eps, V, Rs, (size_t)g.N * g.C * g.Dy * g.Dx, red, red + kEnergyPartials, s));
+    TNMF_HIP_TRY(hipMemcpyAsync(out_host, red + kEnergyPartials, sizeof(double), hipMemcpyDeviceToHost, s));
+    TNMF_HIP_TRY(hipStreamSynchronize(s));
+    return TNMF_OK;
+}
+
+int tnmf_hip_beta_fields(tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *R, void *Q,
+                         void *P, size_t n_elems, void *stream) {
+    if (!ctx) return TNMF_E_NULL;
+    if (dtype != 0 && dtype != 1) return TNMF_E_DTYPE;
+    if (!beta_ok(beta)) return TNMF_E_UNSUPPORTED;
+    if (n_elems > 0 && (!V || !R || !Q || !P)) return TNMF_E_NULL;
+    if (n_elems > 0 && (Q == V || Q == R || P == V)) return TNMF_E_NULL;   // (only P may alias R)
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return launch_beta_fields(ctx, dtype, beta, eps, V, R, Q, P, n_elems, static_cast<hipStream_t>(stream));
+}
+
 int tnmf_hip_convolve_multi_1d(tnmf_hip_ctx *ctx, int dtype, int ndim, size_t rows, const int *shape,
                                const void *in, void *out, void *tmp, const double *kernel0, int len0,
                                const double *kernel1, int len1, void *stream) {
@@ -835,18 +887,12 @@ int tnmf_hip_update_H(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *
     return do_corr_W(ctx, g, dtype, V, Rs, W, H_inout, nullptr, nullptr, true, reg, s);
 }
 
-int tnmf_hip_update_H_ex(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *V, const void *W,
-                         void *H_inout, void *R_scratch, double eps, double sparsity, double inhibition,
-                         double cross_inhibition, const double *kernel0, int len0, const double *kernel1, int len1,
-                         const double *kernel2, int len2, void *stream) {
-    if (is_vol(geom)) {
-        const double *const kern[3] = {kernel0, kernel1, kernel2};
-        const int klen[3] = {len0, len1, len2};
-        return vol_api_update_H_ex(ctx, geom, mode, V, W, H_inout, R_scratch, eps, sparsity, inhibition, cross_inhibition,
-                                   kern, klen, stream);
-    }
-    (void)kernel2;
-    (void)len2;
+// the H half step of tnmf_hip_update_H_ex on one or two shift axes; beta != NULL: of the beta-divergence (*beta != 2),
+// the fields (Q, P) of the reconstruction standing in for (V, R) in every correlation
+static int update_H_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *V, const void *W,
+                       void *H_inout, void *R_scratch, double eps, double sparsity, double inhibition,
+                       double cross_inhibition, const double *kernel0, int len0, const double *kernel1, int len1,
+                       const double *beta, void *stream) {
     ENTER(ctx, geom);
     if (mode < TNMF_MODE_VALID || mode > TNMF_MODE_REFLECT) return TNMF_E_UNSUPPORTED;
     if (g.N == 0) return TNMF_OK;
@@ -879,6 +925,7 @@ int tnmf_hip_update_H_ex(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode,
             CHECK(launch_inhibition(ctx, dtype, g.N, g.M, g.Hy, g.Hs, H_inout, E, ky, ly, kx, lx, inhibition, xc, s));
         }
         CHECK(do_reconstruct(ctx, g, dtype, W, H_inout, Rs, s));
+        if (beta) CHECK(beta_fields_of(ctx, g, dtype, *beta, eps, V, Rs, &V, s));
         int rc = do_corr_W(ctx, g, dtype, V, Rs, W, H_inout, nullptr, nullptr, true, reg, s, E);
         if (!E || (rc != TNMF_E_UNSUPPORTED && rc != TNMF_E_STRIDE)) return rc;
         // this kernel family has no epilogue for the extra term (nothing has been written): unfused gradient into the
@@ -909,10 +956,38 @@ int tnmf_hip_update_H_ex(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode,
     fft_invalidate(ctx);   // the padded copy lives at the same address every call, with new contents
     CHECK(launch_pad_fold(ctx, g, dtype, mode, false, H_inout, Hp, s));
     CHECK(do_reconstruct(ctx, g, dtype, W, Hp, Rs, s));
+    if (beta) CHECK(beta_fields_of(ctx, g, dtype, *beta, eps, V, Rs, &V, s));
     CHECK(do_corr_W(ctx, g, dtype, V, Rs, W, nullptr, negp, posp, false, 0.0, s));
     if (lateral) CHECK(launch_inhibition(ctx, dtype, g.N, g.M, Sy, Sx, H_inout, E, ky, ly, kx, lx, inhibition, xc, s));
     fft_invalidate(ctx);
     return launch_fold_update(ctx, g, dtype, mode, Sy, Sx, H_inout, negp, posp, E, reg, s);
+}
+
+int tnmf_hip_update_H_ex(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *V, const void *W,
+                         void *H_inout, void *R_scratch, double eps, double sparsity, double inhibition,
+                         double cross_inhibition, const double *kernel0, int len0, const double *kernel1, int len1,
+                         const double *kernel2, int len2, void *stream) {
+    if (is_vol(geom)) {
+        const double *const kern[3] = {kernel0, kernel1, kernel2};
+        const int klen[3] = {len0, len1, len2};
+        return vol_api_update_H_ex(ctx, geom, mode, V, W, H_inout, R_scratch, eps, sparsity, inhibition, cross_inhibition,
+                                   kern, klen, stream);
+    }
+    return update_H_2d(ctx, geom, mode, V, W, H_inout, R_scratch, eps, sparsity, inhibition, cross_inhibition, kernel0,
+                       len0, kernel1, len1, nullptr, stream);
+}
+
+int tnmf_hip_update_H_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *V, const void *W,
+                           void *H_inout, void *R_scratch, double eps, double sparsity, double inhibition,
+                           double cross_inhibition, const double *kernel0, int len0, const double *kernel1, int len1,
+                           const double *kernel2, int len2, double beta, void *stream) {
+    if (beta == 2.0)
+        return tnmf_hip_update_H_ex(ctx, geom, mode, V, W, H_inout, R_scratch, eps, sparsity, inhibition,
+                                    cross_inhibition, kernel0, len0, kernel1, len1, kernel2, len2, stream);
+    if (!ctx || !geom) return TNMF_E_NULL;
+    if (is_vol(geom) || !beta_ok(beta)) return TNMF_E_UNSUPPORTED;
+    return update_H_2d(ctx, geom, mode, V, W, H_inout, R_scratch, eps, sparsity, inhibition, cross_inhibition, kernel0,
+                       len0, kernel1, len1, &beta, stream);
 }
 
 int tnmf_hip_grad_W_fused(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *W, const void *H,
@@ -935,6 +1010,27 @@ int tnmf_hip_grad_W_fused(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const vo
     char *np = static_cast<char *>(negpos);
     const size_t wbytes = (size_t)g.M * g.C * g.Ay * g.Ax * esize(dtype);
     return do_corr_H(ctx, g, dtype, sc, V, Rs, H, np, np + wbytes, s);
+}
+
+int tnmf_hip_grad_W_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *W, const void *H,
+                         void *R_scratch, int r_is_valid, void *negpos, double beta, double eps, void *stream) {
+    if (beta == 2.0) return tnmf_hip_grad_W_fused(ctx, geom, V, W, H, R_scratch, r_is_valid, negpos, stream);
+    if (!ctx || !geom) return TNMF_E_NULL;
+    if (is_vol(geom) || !beta_ok(beta)) return TNMF_E_UNSUPPORTED;
+    ENTER(ctx, geom);
+    if (!negpos || !W || (g.N > 0 && (!V || !H))) return TNMF_E_NULL;
+    const Scratch sc = plan_scratch(ctx, g, dtype);
+    CHECK(ensure_scratch(ctx, sc.total));
+    if (r_is_valid && !R_scratch) return TNMF_E_NULL;
+    void *Rs = R_scratch ? R_scratch : ws_at(ctx, sc.r_off);
+    const void *Q = V;
+    if (g.N > 0) {
+        if (!r_is_valid) CHECK(do_reconstruct(ctx, g, dtype, W, H, Rs, s));
+        CHECK(beta_fields_of(ctx, g, dtype, beta, eps, V, Rs, &Q, s));
+    }
+    char *np = static_cast<char *>(negpos);
+    const size_t wbytes = (size_t)g.M * g.C * g.Ay * g.Ax * esize(dtype);
+    return do_corr_H(ctx, g, dtype, sc, Q, Rs, H, np, np + wbytes, s);
 }
 
 int tnmf_hip_run_schedule(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, void *W_inout, void *H_inout,

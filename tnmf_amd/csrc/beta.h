@@ -1,0 +1,19 @@
+// Host-side entry points of beta.hip: the elementwise fields and the energy of the beta-divergence objective.
+//
+// The multiplicative updates of D_beta (Serizel et al. 2016) have the form of the Frobenius ones with the samples and the
+// reconstruction replaced by two fields of R~ = max(R, 0) + eps:
+//   Q = V * R~^(beta - 2),   P = R~^(beta - 1)
+// (beta = 2: Q = V, P = R~).  Every correlation kernel of the library takes the sample operand and the reconstruction
+// operand separately, so the beta step is reconstruct -> fields -> the existing correlations on (Q, P).
+#pragma once
+#include "common.h"
+
+// beta in {0, 1, 2} runs exact arithmetic (divisions and products, no pow); beta = 1 writes P = 1 without reading R
+// for it.  P may alias R.  n elements of type dtype.
+int launch_beta_fields(const tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *R,
+                       void *Q, void *P, size_t n, hipStream_t s);
+// *out_dev = D_beta(V | max(R, 0) + eps) summed in double (beta != 2), deterministic: per-block partials, then one block
+// sums them in a fixed order.  partials: at least kBetaPartials doubles.
+constexpr int kBetaPartials = 2048;
+int launch_beta_energy(const tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *R,
+                       size_t n, double *partials, double *out_dev, hipStream_t s);

@@ -1,0 +1,182 @@
+// beta.hip -- the elementwise kernels of the beta-divergence objective (beta.h): the fields Q, P that stand in for V, R
+// in the correlations of a multiplicative update, and the D_beta energy.  Streaming kernels: 16-byte loads and stores
+// for aligned operands, a scalar tail for lengths that are not a whole number of vectors.
+#include <cmath>
+#include <cstdint>
+
+#include "beta.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+
+// K: 0 = Itakura-Saito (beta 0), 1 = Kullback-Leibler (beta 1), 2 = Frobenius (beta 2), 3 = any other beta (pow)
+template <int K, typename T>
+__device__ __forceinline__ void field(T v, T r, T eps, T bm2, T bm1, T &q, T &p) {
+    const T rt = (r > T(0) ? r : T(0)) + eps;
+    if constexpr (K == 0) {
+        p = T(1) / rt;
+        q = v / (rt * rt);
+    } else if constexpr (K == 1) {
+        p = T(1);
+        q = v / rt;
+    } else if constexpr (K == 2) {
+        p = rt;
+        q = v;
+    } else {
+        p = pow(rt, bm1);
+        q = v * pow(rt, bm2);
+    }
+}
+
+template <typename T> struct Vec;
+template <> struct Vec<float> { using type = float4; static constexpr int n = 4; };
+template <> struct Vec<double> { using type = double2; static constexpr int n = 2; };
+
+template <typename VT, typename T>
+__device__ __forceinline__ T &lane(VT &v, int i) { return reinterpret_cast<T *>(&v)[i]; }
+
+// vec: all four operands 16-byte aligned -> n / L vector iterations, then the scalar tail; else everything scalar
+template <int K, typename T, bool kVec>
+__global__ __launch_bounds__(kBlock) void k_beta_fields(const T *__restrict__ V, const T *R, T *__restrict__ Q, T *P,
+                                                        size_t n, T eps, T bm2, T bm1) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    size_t done = 0;
+    if constexpr (kVec) {
+        using VT = typename Vec<T>::type;
+        constexpr int L = Vec<T>::n;
+        const size_t nv = n / L;
+        for (size_t i = tid; i < nv; i += stride) {
+            VT v = reinterpret_cast<const VT *>(V)[i];
+            VT r = reinterpret_cast<const VT *>(R)[i];   // (read once: P may alias R)
+            VT q, p;
+#pragma unroll
+            for (int j = 0; j < L; ++j)
+                field<K, T>(lane<VT, T>(v, j), lane<VT, T>(r, j), eps, bm2, bm1, lane<VT, T>(q, j), lane<VT, T>(p, j));
+            reinterpret_cast<VT *>(Q)[i] = q;
+            reinterpret_cast<VT *>(P)[i] = p;
+        }
+        done = nv * L;
+    }
+    for (size_t i = done + tid; i < n; i += stride) {
+        T q, p;
+        field<K, T>(V[i], R[i], eps, bm2, bm1, q, p);
+        Q[i] = q;
+        P[i] = p;
+    }
+}
+
+__device__ __forceinline__ double block_sum(double x, double *sh) {
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+    const int w = threadIdx.x / 64, l = threadIdx.x % 64;
+    if (l == 0) sh[w] = x;
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x == 0)
+        for (int i = 0; i < kBlock / 64; ++i) t += sh[i];
+    return t;
+}
+
+// D_beta(v | r~) of one element in double (r~ = max(r, 0) + eps)
+template <int K>
+__device__ __forceinline__ double divergence(double v, double r, double eps, double beta) {
+    const double rt = (r > 0.0 ? r : 0.0) + eps;
+    if constexpr (K == 0) {
+        const double x = v / rt;
+        return x - log(x) - 1.0;
+    } else if constexpr (K == 1) {
+        return (v > 0.0 ? v * log(v / rt) : 0.0) - v + rt;   // (0 log 0 = 0)
+    } else {
+        return (pow(v, beta) + (beta - 1.0) * pow(rt, beta) - beta * v * pow(rt, beta - 1.0)) / (beta * (beta - 1.0));
+    }
+}
+
+template <int K, typename T>
+__global__ __launch_bounds__(kBlock) void k_beta_energy(const T *__restrict__ V, const T *__restrict__ R, size_t n,
+                                                        double eps, double beta, double *__restrict__ partial) {
+    __shared__ double sh[kBlock / 64];
+    double acc = 0.0;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        acc += divergence<K>((double)V[i], (double)R[i], eps, beta);
+    const double tot = block_sum(acc, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(kBlock) void k_beta_sum(const double *__restrict__ partial, int n, double *__restrict__ out) {
+    __shared__ double sh[kBlock / 64];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += kBlock) acc += partial[i];
+    const double tot = block_sum(acc, sh);
+    if (threadIdx.x == 0) *out = tot;
+}
+
+inline int grid_of(size_t work, const tnmf_hip_ctx *ctx) {
+    const size_t want = (work + kBlock - 1) / kBlock;
+    const size_t cap = (size_t)ctx->num_cu * 8;
+    return (int)(want < cap ? (want ? want : 1) : cap);
+}
+
+template <int K, typename T>
+int fields_as(const tnmf_hip_ctx *ctx, double beta, double eps, const void *V, const void *R, void *Q, void *P, size_t n,
+              hipStream_t s) {
+    const bool vec = ((reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(Q) |
+                       reinterpret_cast<uintptr_t>(P)) & 15) == 0;
+    const int grid = grid_of(vec ? n / Vec<T>::n + 1 : n, ctx);
+    const T e = (T)eps, bm2 = (T)(beta - 2.0), bm1 = (T)(beta - 1.0);
+    if (vec)
+        hipLaunchKernelGGL((k_beta_fields<K, T, true>), dim3(grid), dim3(kBlock), 0, s, (const T *)V, (const T *)R,
+                           (T *)Q, (T *)P, n, e, bm2, bm1);
+    else
+        hipLaunchKernelGGL((k_beta_fields<K, T, false>), dim3(grid), dim3(kBlock), 0, s, (const T *)V, (const T *)R,
+                           (T *)Q, (T *)P, n, e, bm2, bm1);
+    TNMF_LAUNCH_CHECK();
+    return TNMF_OK;
+}
+
+template <typename T>
+int fields_typed(const tnmf_hip_ctx *ctx, double beta, double eps, const void *V, const void *R, void *Q, void *P,
+                 size_t n, hipStream_t s) {
+    if (beta == 0.0) return fields_as<0, T>(ctx, beta, eps, V, R, Q, P, n, s);
+    if (beta == 1.0) return fields_as<1, T>(ctx, beta, eps, V, R, Q, P, n, s);
+    if (beta == 2.0) return fields_as<2, T>(ctx, beta, eps, V, R, Q, P, n, s);
+    return fields_as<3, T>(ctx, beta, eps, V, R, Q, P, n, s);
+}
+
+template <typename T>
+int energy_typed(const tnmf_hip_ctx *ctx, double beta, double eps, const void *V, const void *R, size_t n, double *partials,
+                 int grid, hipStream_t s) {
+    if (beta == 0.0)
+        hipLaunchKernelGGL((k_beta_energy<0, T>), dim3(grid), dim3(kBlock), 0, s, (const T *)V, (const T *)R, n, eps, beta,
+                           partials);
+    else if (beta == 1.0)
+        hipLaunchKernelGGL((k_beta_energy<1, T>), dim3(grid), dim3(kBlock), 0, s, (const T *)V, (const T *)R, n, eps, beta,
+                           partials);
+    else
+        hipLaunchKernelGGL((k_beta_energy<3, T>), dim3(grid), dim3(kBlock), 0, s, (const T *)V, (const T *)R, n, eps, beta,
+                           partials);
+    TNMF_LAUNCH_CHECK();
+    return TNMF_OK;
+}
+
+}  // namespace
+
+int launch_beta_fields(const tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *R,
+                       void *Q, void *P, size_t n, hipStream_t s) {
+    if (n == 0) return TNMF_OK;
+    return dtype == 0 ? fields_typed<float>(ctx, beta, eps, V, R, Q, P, n, s)
+                      : fields_typed<double>(ctx, beta, eps, V, R, Q, P, n, s);
+}
+
+int launch_beta_energy(const tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *R,
+                       size_t n, double *partials, double *out_dev, hipStream_t s) {
+    int grid = grid_of(n, ctx);
+    if (grid > kBetaPartials) grid = kBetaPartials;
+    const int rc = dtype == 0 ? energy_typed<float>(ctx, beta, eps, V, R, n, partials, grid, s)
+                              : energy_typed<double>(ctx, beta, eps, V, R, n, partials, grid, s);
+    if (rc != TNMF_OK) return rc;
+    hipLaunchKernelGGL(k_beta_sum, dim3(1), dim3(kBlock), 0, s, partials, grid, out_dev);
+    TNMF_LAUNCH_CHECK();
+    return TNMF_OK;
+}

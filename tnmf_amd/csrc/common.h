@@ -34,6 +34,9 @@ struct FftState {
     bool explicit_bind = false;   // ... as told by tnmf_hip_ctx_bind (kept across foreign calls), not taken from a call
     const void *H_base = nullptr;
     const void *V_base = nullptr;
+    // a scratch operand passed in the place of the samples (the field Q of the beta-divergence steps: fixed address,
+    // new contents every call): never adopted as V, never cached
+    const void *V_volatile = nullptr;
     Geo geo = {};                 // geo.N = samples of the binding
     int dtype = 0;
     // per sample of the binding: the workspace holds ...
@@ -66,6 +69,8 @@ struct tnmf_hip_ctx {
     size_t wimg_bytes;
     void *hw = nullptr;     // activation-sized work arrays of tnmf_hip_update_H_ex (lateral terms, padded H, its gradients)
     size_t hw_bytes = 0;
+    void *qb = nullptr;     // the field Q [N,C,*D] of the beta-divergence entry points (allocated by the first beta != 2 call)
+    size_t qb_bytes = 0;
     // persistent schedule kernel: the operation list travels host -> device through a ring of PINNED staging slots (an
     // asynchronous copy from the caller's pageable array could still be reading it after the call has returned); a slot is
     // reused only after the copy that read it has completed (one event per slot)

@@ -411,6 +411,7 @@ struct Call {
 int prepare(tnmf_hip_ctx *ctx, const Geo &g, int dtype, const void *H, const void *V, Call *c, bool window = false) {
     if (!fft_has(g, dtype)) return TNMF_E_UNSUPPORTED;
     FftState &f = ctx->fft;
+    if (V && V == f.V_volatile) V = nullptr;   // (scratch in the place of the samples: neither located, bound nor cached)
     c->sl = locate(f, g, dtype, H, V);
     if (!c->sl.cached) {
         if (f.cache_enabled && !f.explicit_bind && (H || V)) {
@@ -470,6 +471,12 @@ int spectra_V(tnmf_hip_ctx *ctx, const Geo &g, const Call &c, int dtype, const v
     const bool track = c.sl.v_cached && f.cache_enabled;
     const bool hit = track && all_ok(f.V_ok, c.sl.n0, g.N);
     ++(hit ? f.v_hits : f.v_runs);
+    if (!track && c.sl.cached) {
+        // other samples than the bound ones (e.g. the beta-divergence field Q) go through the slots of the binding:
+        // what the cache held for those samples is overwritten
+        set_ok(f.V_ok, c.sl.n0, g.N, 0);
+        set_ok(f.SV_ok, c.sl.n0, g.N, 0);
+    }
     if (!hit) {
         if (track) {
             set_ok(f.V_ok, c.sl.n0, g.N, 0);
