@@ -36,15 +36,12 @@ def test_backend_without_beta_hooks_is_refused(value):
 class _BetaHooks(OracleBackend):
     """An oracle backend that claims the beta hooks (never called here: fit refuses the samples first)."""
 
-    def fused_update_H_beta(self, *a, **k):
-        raise AssertionError('not reached')
-
-    fused_update_W_beta = local_gradient_W_beta = reconstruction_energy_beta = fused_update_H_beta
+    supports_beta_loss = True
 
 
 @pytest.mark.parametrize('beta', ['itakura-saito', -1.])
 @pytest.mark.parametrize('how', ['fit_batch', 'fit_minibatches'])
-def test_zeros_in_V_are_refused_for_beta_at_most_zero(beta, how):
+def test_zeros_in_V_are_refused_for_beta_at_most_zero_by_a_beta_backend(beta, how):
     V = np.random.default_rng(0).random((3, 1, 8)) + 0.1
     V[1, 0, 4] = 0.
     nmf = TransformInvariantNMF(n_atoms=2, atom_shape=(3,), backend=_BetaHooks(), beta_loss=beta)

@@ -141,24 +141,57 @@ def test_row_padded_activations_on_the_split_path(beta, lateral):
 
 
 # -- 3. beta == 2 through the new entries is the Frobenius step ------------------------------------------------------
+def _entries(nmf):
+    """(library, ctx, geometry, V, W, H, R scratch, stream) of a model's resident problem, for calling the C ABI."""
+    be = nmf._backend
+    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    g = be._geom(nmf._H.shape[0], nmf._W.shape[0], be._row_stride(nmf._H))
+    return be._lib, be._ctx, ctypes.byref(g), p(be._V_dev), p(nmf._W), p(nmf._H), p(be._R_scratch), be._stream()
+
+
 @pytest.mark.parametrize('dtype,path', [(np.float64, 'auto'), (np.float32, 'auto'), (np.float32, 'fft')],
                          ids=['f64_auto', 'f32_auto', 'f32_fft'])
-def test_beta_2_entries_are_bit_identical(dtype, path):
+def test_beta_2_entry_points_are_the_frobenius_calls(dtype, path):
+    """include/tnmf_hip.h: at beta == 2 each beta entry point is its Frobenius counterpart, and tnmf_hip_update_H is the
+    'valid' step of tnmf_hip_update_H_ex without lateral terms -- same bits.  So are the backend hooks with beta=2."""
     V = positive_V((12, 1, 96, 96), seed=4, dtype=dtype)
     a, b = model(V, 32, (12, 12), 2., path=path), model(V, 32, (12, 12), 2., path=path)
+    sp, eps = 0.05, a.eps
+    none = (None, 0, None, 0, None, 0)
     for _ in range(2):
-        a._update_H(sparsity=0.05)
-        b._backend.fused_update_H_beta(b._V, b._W, b._H, beta=2., sparsity=0.05, eps=b.eps)
+        lib, ca, ga, Va, Wa, Ha, Ra, sa = _entries(a)
+        _, cb, gb, Vb, Wb, Hb, Rb, sb = _entries(b)
+        _lib.check(lib.tnmf_hip_update_H(ca, ga, Va, Wa, Ha, Ra, 0, eps, sp, sa), 'update_H')
+        _lib.check(lib.tnmf_hip_update_H_ex(cb, gb, 0, Vb, Wb, Hb, Rb, eps, sp, 0., 0., *none, sb), 'update_H_ex')
+        assert np.array_equal(a.H, b.H)
+        _lib.check(lib.tnmf_hip_update_H_ex(ca, ga, 0, Va, Wa, Ha, Ra, eps, sp, 0., 0., *none, sa), 'update_H_ex')
+        _lib.check(lib.tnmf_hip_update_H_beta(cb, gb, 0, Vb, Wb, Hb, Rb, eps, sp, 0., 0., *none, 2., sb), 'update_H_beta')
+        assert np.array_equal(a.H, b.H)
+        npa, npb = torch.empty_like(a._backend._negpos), torch.empty_like(b._backend._negpos)
+        _lib.check(lib.tnmf_hip_grad_W_fused(ca, ga, Va, Wa, Ha, Ra, 0, ctypes.c_void_p(npa.data_ptr()), sa), 'grad_W')
+        _lib.check(lib.tnmf_hip_grad_W_beta(cb, gb, Vb, Wb, Hb, Rb, 0, ctypes.c_void_p(npb.data_ptr()), 2., eps, sb),
+                   'grad_W_beta')
+        assert np.array_equal(npa.cpu().numpy(), npb.cpu().numpy())
+        a._backend.apply_W(a._W, npa, eps)
+        b._backend.apply_W(b._W, npb, eps)
+        assert np.array_equal(a.W, b.W)
+        ea, eb = ctypes.c_double(0.), ctypes.c_double(1.)
+        _lib.check(lib.tnmf_hip_energy(ca, ga, Va, Wa, Ha, ctypes.byref(ea), sa), 'energy')
+        _lib.check(lib.tnmf_hip_energy_beta(cb, gb, 2., eps, Vb, Wb, Hb, ctypes.byref(eb), sb), 'energy_beta')
+        assert ea.value == eb.value
+    # the hooks: beta=2. is the default objective
+    for _ in range(2):
+        a._backend.fused_update_H(a._V, a._W, a._H, sparsity=sp, eps=eps)
+        b._backend.fused_update_H(b._V, b._W, b._H, sparsity=sp, eps=eps, beta=2.)
         assert np.array_equal(a.H, b.H)
         ga = a._backend.local_gradient_W(a._V, a._W, a._H).cpu().numpy()
-        gb = b._backend.local_gradient_W_beta(b._V, b._W, b._H, beta=2., eps=b.eps).cpu().numpy()
+        gb = b._backend.local_gradient_W(b._V, b._W, b._H, beta=2., eps=eps).cpu().numpy()
         assert np.array_equal(ga, gb)
-        a._update_W()
-        b._backend.fused_update_W_beta(b._V, b._W, b._H, beta=2., eps=b.eps)
+        a._backend.fused_update_W(a._V, a._W, a._H, eps=eps)
+        b._backend.fused_update_W(b._V, b._W, b._H, eps=eps, beta=2.)
         assert np.array_equal(a.W, b.W)
-    ea = a._backend.reconstruction_energy(a._V, a._W, a._H)
-    eb = b._backend.reconstruction_energy_beta(b._V, b._W, b._H, beta=2., eps=b.eps)
-    assert ea == eb
+    assert a._backend.reconstruction_energy(a._V, a._W, a._H) == \
+        b._backend.reconstruction_energy(b._V, b._W, b._H, beta=2., eps=eps)
 
 
 def test_frobenius_by_name_is_the_default_fit():

@@ -69,9 +69,6 @@ def _joined(batches: list) -> list:
 
 _BETA_NAMES = {'frobenius': 2., 'kullback-leibler': 1., 'itakura-saito': 0.}
 
-# the hooks a backend needs for a beta-divergence objective other than the Frobenius norm
-_BETA_HOOKS = ('fused_update_H_beta', 'fused_update_W_beta', 'local_gradient_W_beta', 'reconstruction_energy_beta')
-
 
 def beta_loss_value(beta_loss) -> float:
     """beta of ``beta_loss``: scikit-learn's names ('frobenius' 2, 'kullback-leibler' 1, 'itakura-saito' 0) or a finite
@@ -142,11 +139,9 @@ class TransformInvariantNMF:
         else:
             self._backend = backend
 
-        if self._beta != 2.:
-            missing = [h for h in _BETA_HOOKS if getattr(self._backend, h, None) is None]
-            if missing:
-                raise NotImplementedError(f'beta_loss={beta_loss!r}: the backend {type(self._backend).__name__} has no '
-                                          f'beta-divergence hooks ({", ".join(missing)})')
+        if self._beta != 2. and not getattr(self._backend, 'supports_beta_loss', False):
+            raise NotImplementedError(f'beta_loss={beta_loss!r}: the backend {type(self._backend).__name__} does not '
+                                      f'support beta-divergence objectives')
 
         self._logger = logger if logger is not None else logging.getLogger(self.__class__.__name__)
         self._logger.setLevel([logging.ERROR, logging.WARNING, logging.INFO, logging.DEBUG][verbose])
@@ -185,10 +180,15 @@ class TransformInvariantNMF:
         """beta of the objective D_beta (2: Frobenius)."""
         return self._beta
 
-    def _energy_function(self) -> float:
+    def _objective(self, **kwargs) -> dict:
+        """Keyword arguments of a backend hook, plus ``beta`` and ``eps`` for an objective other than the Frobenius norm
+        (at beta == 2 the hooks are called exactly as on a Frobenius-only backend)."""
         if self._beta != 2.:
-            return self._backend.reconstruction_energy_beta(self._V, self._W, self._H, beta=self._beta, eps=self.eps)
-        return self._backend.reconstruction_energy(self._V, self._W, self._H)
+            kwargs.update(beta=self._beta, eps=self.eps)
+        return kwargs
+
+    def _energy_function(self) -> float:
+        return self._backend.reconstruction_energy(self._V, self._W, self._H, **self._objective())
 
     # -- elementwise multiplicative update (reference :217-238) ----------------------------------------------
     def _multiplicative_update(self, arr, neg, pos, sparsity: float = 0., normalization_axes=None):
@@ -208,13 +208,14 @@ class TransformInvariantNMF:
     def _fused(self, name: str):
         return getattr(self._backend, name, None) if self._use_fused else None
 
+    def _step_hook(self, name: str):
+        """_fused(name); beta != 2 always takes the backend's hook (the reference's Frobenius lines do not apply to it)."""
+        return getattr(self._backend, name) if self._beta != 2. else self._fused(name)
+
     def _update_W(self, s: slice = sliceNone):
-        if self._beta != 2.:
-            self._backend.fused_update_W_beta(self._V, self._W, self._H, s, beta=self._beta, eps=self.eps)
-            return
-        fused = self._fused('fused_update_W')
+        fused = self._step_hook('fused_update_W')
         if fused is not None:
-            fused(self._V, self._W, self._H, s, eps=self.eps)
+            fused(self._V, self._W, self._H, s, **self._objective(eps=self.eps))
             return
         neg, pos = self._backend.reconstruction_gradient_W(self._V, self._W, self._H, s)
         assert neg.shape == self._W.shape and pos.shape == self._W.shape
@@ -222,26 +223,19 @@ class TransformInvariantNMF:
 
     def _update_H(self, s: slice = sliceNone, sparsity: float = 0., inhibition: float = 0., cross_inhibition: float = 0.):
         lateral = inhibition > 0 or cross_inhibition > 0
-        if self._beta != 2.:
-            # (no fall-back to the Frobenius lines below: a step the backend cannot take raises)
+        fused = self._step_hook('fused_update_H')
+        if fused is not None:
             kw = dict(inhibition=inhibition, cross_inhibition=cross_inhibition,
                       inhibition_kernels=self._inhibition_kernels_1D) if lateral else {}
-            self._backend.fused_update_H_beta(self._V, self._W, self._H, s, beta=self._beta, sparsity=sparsity,
-                                              eps=self.eps, **kw)
-            return
-        fused = self._fused('fused_update_H')
-        if fused is not None:
             try:
-                if lateral:
-                    fused(self._V, self._W, self._H, s, sparsity=sparsity, eps=self.eps, inhibition=inhibition,
-                          cross_inhibition=cross_inhibition, inhibition_kernels=self._inhibition_kernels_1D)
-                else:
-                    fused(self._V, self._W, self._H, s, sparsity=sparsity, eps=self.eps)
+                fused(self._V, self._W, self._H, s, sparsity=sparsity, **self._objective(eps=self.eps, **kw))
                 return
             except NotImplementedError:
                 # (inhibition kernels longer than the backend's fused kernel takes; lateral terms or reconstruction modes
-                # of volumes: nothing has been written, the reference's own lines below do the step)
-                pass
+                # of volumes: nothing has been written, the reference's own lines below do the step -- for the Frobenius
+                # objective only: beta != 2 has no fall-back, a step the backend cannot take raises)
+                if self._beta != 2.:
+                    raise
         neg, pos = self._backend.reconstruction_gradient_H(self._V, self._W, self._H, s)
         Hs = self._H[s]
         assert neg.shape == Hs.shape and pos.shape == Hs.shape
@@ -343,7 +337,7 @@ class TransformInvariantNMF:
     def _local_gradient_W(self):
         """The backend's hook for this rank's [neg | pos] of the W gradient (not yet summed over ranks), or None."""
         if self._beta != 2.:
-            return lambda V, W, H, s: self._backend.local_gradient_W_beta(V, W, H, s, beta=self._beta, eps=self.eps)
+            return lambda V, W, H, s: self._backend.local_gradient_W(V, W, H, s, **self._objective())
         return self._fused('local_gradient_W')
 
     def _blend_gradient_W(self, acc, lam: float, s: slice):

@@ -289,6 +289,37 @@ class HIP_Backend(Backend):
             Hs.copy_(Hc)
         return True
 
+    def _call_resident_H(self, Hs: torch.Tensor, W: torch.Tensor, inplace: bool, call, lateral: bool = False) -> None:
+        """_call_H on a slice of the resident activations, with the spectrum-cache bookkeeping around it: before the call
+        the cache is validated ('valid' mode) or dropped; after it the library's spectra are noted as those of (Hs, W),
+        or dropped when they belong to a temporary copy or to another reconstruction mode.  A library error drops them
+        too; TNMF_E_UNSUPPORTED with lateral terms becomes NotImplementedError (the library answers it before it writes H:
+        inhibition kernels too long for the lateral-term kernel's LDS tile, or planes beyond its 32-bit offsets)."""
+        if self._mode == 0:
+            self._validate_H_cache(Hs, W)   # (the library drops the spectra of the samples it updates itself)
+        else:
+            self._foreign_H()
+        try:
+            copied = self._call_H(Hs, inplace, call)
+        except _lib.TnmfHipError as exc:
+            self._foreign_H()
+            if exc.code == _lib.E_UNSUPPORTED and lateral:
+                raise NotImplementedError('lateral terms outside the fused kernel') from exc
+            raise
+        if copied or self._mode != 0:
+            self._foreign_H()   # (the spectra the library may have kept belong to a temporary, or are not cached)
+        elif Hs.shape[0]:
+            self._note_H_cache(Hs, W)
+
+    # beta-divergence objectives (the hooks' `beta`): the multiplicative updates of D_beta are those of the Frobenius
+    # objective with (V, R) replaced by the fields Q = V * R~^(beta-2), P = R~^(beta-1) of R~ = R + eps
+    # (include/tnmf_hip.h, "beta-divergence objectives"); beta == 2 is the Frobenius call itself.  Volumes are not covered.
+    supports_beta_loss = True
+
+    def _check_beta(self, beta: float) -> None:
+        if beta != 2. and len(self.atom_shape) == 3:
+            raise NotImplementedError('beta-divergence objectives other than the Frobenius norm: 1 or 2 shift axes only')
+
     def _local(self, s: slice) -> slice:
         """Slices address this rank's resident samples (all samples when there is no process group)."""
         lo, hi, step = s.indices(self._shard[1] - self._shard[0])
@@ -460,57 +491,26 @@ class HIP_Backend(Backend):
             _ptr(neg), _ptr(pos), self._stream()), 'tnmf_hip_grad_H'))
         return self._fold(neg), self._fold(pos)
 
-    def _local_grad_W(self, W, H, s) -> torch.Tensor:
-        ls = self._local(s)
-        Hs, Vs = H[ls], self._V_dev[ls]
-        self._check_W(W)
-        self._check_H(Hs, W.shape[0])
-        if self._mode == 0:
-            self._validate_H_cache(Hs, W)
-        Hs = self._pad(Hs)
-        negpos = torch.empty_like(self._negpos)
-        Rs = self._R_scratch[ls] if Hs.shape[0] else None
-
-        def run(Hc, ld):
-            g = self._geom(Hc.shape[0], W.shape[0], ld)
-            r_valid = 0
-            if self._timeline is not None and Hc.shape[0]:
-                with self._timed('reconstruct'):
-                    rc = self._lib.tnmf_hip_reconstruct(self._ctx, ctypes.byref(g), _ptr(W), _ptr(Hc), _ptr(Rs),
-                                                        self._stream())
-                if rc != 0:
-                    return rc, 'tnmf_hip_reconstruct'
-                r_valid = 1
-            with self._timed('grad_W'):
-                rc = self._lib.tnmf_hip_grad_W_fused(self._ctx, ctypes.byref(g), _ptr(Vs), _ptr(W), _ptr(Hc), _ptr(Rs),
-                                                     r_valid, _ptr(negpos), self._stream())
-            return rc, 'tnmf_hip_grad_W_fused'
-
-        copied = self._call_H(Hs, False, run)
-        if copied:
-            self._foreign_H()   # the spectra the library may have kept belong to a temporary
-        elif self._mode == 0 and Hs.shape[0]:
-            self._note_H_cache(Hs, W)
-        return negpos
-
     def reconstruction_gradient_W(self, V, W: torch.Tensor, H: torch.Tensor, s: slice = sliceNone):
         """(neg, pos) of W's shape (reference: NumPy.py:69-91) -> tnmf_hip_grad_W_fused; summed over the ranks of
         the process group (one all-reduce of the contiguous [neg | pos] buffer)."""
         self._foreign_H()
-        negpos = self._local_grad_W(W, H, s)
+        negpos = self.local_gradient_W(V, W, H, s)
         self._all_reduce(negpos)
         return negpos[0], negpos[1]
 
-    def reconstruction_energy(self, V, W: torch.Tensor, H: torch.Tensor) -> float:
-        """1/2 sum (V - R)^2 (reference: _Backend.py:127-130) -> tnmf_hip_energy (+ all-reduce)."""
+    def reconstruction_energy(self, V, W: torch.Tensor, H: torch.Tensor, beta: float = 2., eps: float = 1e-9) -> float:
+        """1/2 sum (V - R)^2 (reference: _Backend.py:127-130), or for beta != 2 sum D_beta(V | R + eps)
+        -> tnmf_hip_energy_beta (+ all-reduce)."""
+        self._check_beta(beta)
         self._check_W(W)
         self._foreign_H()
         self._check_H(H, W.shape[0])
         H = self._pad(H)
         out = ctypes.c_double(0.0)
-        self._call_H(H, False, lambda Hc, ld: (self._lib.tnmf_hip_energy(
-            self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)), _ptr(self._V_dev), _ptr(W), _ptr(Hc),
-            ctypes.byref(out), self._stream()), 'tnmf_hip_energy'))
+        self._call_H(H, False, lambda Hc, ld: (self._lib.tnmf_hip_energy_beta(
+            self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)), float(beta), float(eps),
+            _ptr(self._V_dev), _ptr(W), _ptr(Hc), ctypes.byref(out), self._stream()), 'tnmf_hip_energy_beta'))
         if self._world > 1:
             t = torch.tensor([out.value], dtype=torch.float64, device=self._device)
             self._all_reduce(t)
@@ -583,191 +583,53 @@ class HIP_Backend(Backend):
 
     def fused_update_H(self, V, W: torch.Tensor, H: torch.Tensor, s: slice = sliceNone, sparsity: float = 0.,
                        eps: float = 1e-9, inhibition: float = 0., cross_inhibition: float = 0.,
-                       inhibition_kernels: Optional[Sequence[np.ndarray]] = None) -> None:
+                       inhibition_kernels: Optional[Sequence[np.ndarray]] = None, beta: float = 2.) -> None:
         """One H half step, in place (reference: TransformInvariantNMF.py:246-271): 'valid' mode without lateral terms on
         the fused kernels (tnmf_hip_update_H); with lateral inhibition / cross-atom inhibition and for the other
-        reconstruction modes through tnmf_hip_update_H_ex -- the separable convolution, the lateral terms, the pad, the
-        fold and the update all run as kernels of the library."""
+        reconstruction modes through tnmf_hip_update_H_ex, for beta != 2 through tnmf_hip_update_H_beta -- the separable
+        convolution, the lateral terms, the pad, the fold, the beta-divergence fields and the update all run as kernels
+        of the library."""
+        self._check_beta(beta)
         ls = self._local(s)
         Hs, Vs = H[ls], self._V_dev[ls]
         if Hs.shape[0] == 0:
             return
         self._check_W(W)
         self._check_H(Hs, W.shape[0])
+        Rs = self._R_scratch[ls]
         lateral = inhibition > 0 or cross_inhibition > 0
-        if self._mode != 0 or lateral:
+        if self._mode == 0 and not lateral and beta == 2.:
+            def run(Hc, ld):
+                g = self._geom(Hc.shape[0], W.shape[0], ld)
+                r_valid = 0
+                if self._timeline is not None:
+                    with self._timed('reconstruct'):
+                        rc = self._lib.tnmf_hip_reconstruct(self._ctx, ctypes.byref(g), _ptr(W), _ptr(Hc), _ptr(Rs),
+                                                            self._stream())
+                    if rc != 0:
+                        return rc, 'tnmf_hip_reconstruct'
+                    r_valid = 1
+                with self._timed('update_H'):
+                    rc = self._lib.tnmf_hip_update_H(self._ctx, ctypes.byref(g), _ptr(Vs), _ptr(W), _ptr(Hc), _ptr(Rs),
+                                                     r_valid, float(eps), float(sparsity), self._stream())
+                return rc, 'tnmf_hip_update_H'
+        else:
             k = len(self.atom_shape)
             ks = [np.ascontiguousarray(kk, dtype=np.float64) for kk in (inhibition_kernels or ())]
             if lateral and len(ks) != k:
                 raise ValueError('one inhibition kernel per shift axis')
             kp = [kk.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) for kk in ks] + [None, None, None]
             kl = [len(kk) for kk in ks] + [0, 0, 0]
-            Rs = self._R_scratch[ls]
-            if self._mode == 0:
-                self._validate_H_cache(Hs, W)   # (the library drops the spectra of the samples it updates itself)
-            else:
-                self._foreign_H()
 
-            def run_ex(Hc, ld):
-                with self._timed('update_H'):
-                    rc = self._lib.tnmf_hip_update_H_ex(
-                        self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)), self._mode, _ptr(Vs), _ptr(W),
+            def run(Hc, ld):
+                args = (self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)), self._mode, _ptr(Vs), _ptr(W),
                         _ptr(Hc), _ptr(Rs), float(eps), float(sparsity), float(inhibition), float(cross_inhibition),
-                        kp[0], kl[0], kp[1], kl[1], kp[2], kl[2], self._stream())
-                return rc, 'tnmf_hip_update_H_ex'
-
-            # (inhibition kernels too long for the lateral-term kernel's LDS tile, or planes beyond its 32-bit offsets: the
-            # library answers TNMF_E_UNSUPPORTED before it writes H, and the front end walks the reference's own lines)
-            try:
-                if self._mode != 0:
-                    assert Hs.is_contiguous()
-                    rc, where = run_ex(Hs, 0)
-                    _lib.check(rc, where)
-                    self._foreign_H()
-                elif self._call_H(Hs, True, run_ex):
-                    self._foreign_H()   # the library updated (and kept spectra of) a temporary copy
-                else:
-                    self._note_H_cache(Hs, W)
-            except _lib.TnmfHipError as exc:
-                self._foreign_H()
-                if exc.code == _lib.E_UNSUPPORTED and lateral:
-                    raise NotImplementedError('lateral terms outside the fused kernel') from exc
-                raise
-            return
-        Rs = self._R_scratch[ls]
-        self._validate_H_cache(Hs, W)
-
-        def run(Hc, ld):
-            g = self._geom(Hc.shape[0], W.shape[0], ld)
-            r_valid = 0
-            if self._timeline is not None:
-                with self._timed('reconstruct'):
-                    rc = self._lib.tnmf_hip_reconstruct(self._ctx, ctypes.byref(g), _ptr(W), _ptr(Hc), _ptr(Rs),
-                                                        self._stream())
-                if rc != 0:
-                    return rc, 'tnmf_hip_reconstruct'
-                r_valid = 1
-            with self._timed('update_H'):
-                rc = self._lib.tnmf_hip_update_H(self._ctx, ctypes.byref(g), _ptr(Vs), _ptr(W), _ptr(Hc), _ptr(Rs),
-                                                 r_valid, float(eps), float(sparsity), self._stream())
-            return rc, 'tnmf_hip_update_H'
-
-        if self._call_H(Hs, True, run):
-            self._foreign_H()   # the library updated (and kept spectra of) a temporary copy
-        else:
-            self._note_H_cache(Hs, W)
-
-    # -- beta-divergence objectives (tnmf_hip_update_H_beta / _grad_W_beta / _energy_beta) ---------------------------
-    # The multiplicative updates of D_beta are those of the Frobenius objective with (V, R) replaced by the fields
-    # Q = V * R~^(beta-2), P = R~^(beta-1) of R~ = R + eps (include/tnmf_hip.h, "beta-divergence objectives"); beta == 2
-    # is the Frobenius call itself.  Volumes are not covered.
-    def _check_beta_geometry(self):
-        if len(self.atom_shape) == 3:
-            raise NotImplementedError('beta-divergence objectives other than the Frobenius norm: 1 or 2 shift axes only')
-
-    def fused_update_H_beta(self, V, W: torch.Tensor, H: torch.Tensor, s: slice = sliceNone, beta: float = 2.,
-                            sparsity: float = 0., eps: float = 1e-9, inhibition: float = 0., cross_inhibition: float = 0.,
-                            inhibition_kernels: Optional[Sequence[np.ndarray]] = None) -> None:
-        """One H half step of the D_beta objective, in place, for every reconstruction mode and lateral term."""
-        self._check_beta_geometry()
-        ls = self._local(s)
-        Hs, Vs = H[ls], self._V_dev[ls]
-        if Hs.shape[0] == 0:
-            return
-        self._check_W(W)
-        self._check_H(Hs, W.shape[0])
-        lateral = inhibition > 0 or cross_inhibition > 0
-        k = len(self.atom_shape)
-        ks = [np.ascontiguousarray(kk, dtype=np.float64) for kk in (inhibition_kernels or ())] if lateral else []
-        if lateral and len(ks) != k:
-            raise ValueError('one inhibition kernel per shift axis')
-        kp = [kk.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) for kk in ks] + [None, None, None]
-        kl = [len(kk) for kk in ks] + [0, 0, 0]
-        Rs = self._R_scratch[ls]
-        if self._mode == 0:
-            self._validate_H_cache(Hs, W)   # (the library drops the spectra of the samples it updates itself)
-        else:
-            self._foreign_H()
-
-        def run(Hc, ld):
-            with self._timed('update_H'):
-                rc = self._lib.tnmf_hip_update_H_beta(
-                    self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)), self._mode, _ptr(Vs), _ptr(W),
-                    _ptr(Hc), _ptr(Rs), float(eps), float(sparsity), float(inhibition), float(cross_inhibition),
-                    kp[0], kl[0], kp[1], kl[1], kp[2], kl[2], float(beta), self._stream())
-            return rc, 'tnmf_hip_update_H_beta'
-
-        try:
-            if self._mode != 0:
-                assert Hs.is_contiguous()
-                rc, where = run(Hs, 0)
-                _lib.check(rc, where)
-                self._foreign_H()
-            elif self._call_H(Hs, True, run):
-                self._foreign_H()   # the library updated (and kept spectra of) a temporary copy
-            else:
-                self._note_H_cache(Hs, W)
-        except _lib.TnmfHipError as exc:
-            self._foreign_H()
-            if exc.code == _lib.E_UNSUPPORTED and lateral:
-                raise NotImplementedError('lateral terms outside the fused kernel') from exc
-            raise
-
-    def local_gradient_W_beta(self, V, W: torch.Tensor, H: torch.Tensor, s: slice = sliceNone, beta: float = 2.,
-                              eps: float = 1e-9) -> torch.Tensor:
-        """This rank's [neg | pos] = [corr_H(H, Q) | corr_H(H, P)] as one [2, M, C, *A] buffer, NOT yet summed over ranks."""
-        self._check_beta_geometry()
-        ls = self._local(s)
-        Hs, Vs = H[ls], self._V_dev[ls]
-        self._check_W(W)
-        self._check_H(Hs, W.shape[0])
-        if self._mode == 0:
-            self._validate_H_cache(Hs, W)
-        else:
-            self._foreign_H()
-        Hs = self._pad(Hs)
-        negpos = torch.empty_like(self._negpos)
-        Rs = self._R_scratch[ls] if Hs.shape[0] else None
-
-        def run(Hc, ld):
-            with self._timed('grad_W'):
-                rc = self._lib.tnmf_hip_grad_W_beta(self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)),
-                                                    _ptr(Vs), _ptr(W), _ptr(Hc), _ptr(Rs), 0, _ptr(negpos), float(beta),
-                                                    float(eps), self._stream())
-            return rc, 'tnmf_hip_grad_W_beta'
-
-        copied = self._call_H(Hs, False, run)
-        if copied or self._mode != 0:
-            self._foreign_H()   # the spectra the library may have kept belong to a temporary
-        elif Hs.shape[0]:
-            self._note_H_cache(Hs, W)
-        return negpos
-
-    def fused_update_W_beta(self, V, W: torch.Tensor, H: torch.Tensor, s: slice = sliceNone, beta: float = 2.,
-                            eps: float = 1e-9) -> None:
-        """One W half step of the D_beta objective, in place: local gradient, the same collective as fused_update_W
-        (only the [neg | pos] buffer crosses ranks), MU + normalise."""
-        negpos = self.local_gradient_W_beta(V, W, H, s, beta=beta, eps=eps)
-        self._all_reduce(negpos)
-        self.apply_W(W, negpos, eps)
-
-    def reconstruction_energy_beta(self, V, W: torch.Tensor, H: torch.Tensor, beta: float = 2.,
-                                   eps: float = 1e-9) -> float:
-        """sum D_beta(V | R + eps) (beta == 2: 1/2 sum (V - R)^2) -> tnmf_hip_energy_beta (+ all-reduce)."""
-        self._check_beta_geometry()
-        self._check_W(W)
-        self._foreign_H()
-        self._check_H(H, W.shape[0])
-        H = self._pad(H)
-        out = ctypes.c_double(0.0)
-        self._call_H(H, False, lambda Hc, ld: (self._lib.tnmf_hip_energy_beta(
-            self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)), float(beta), float(eps),
-            _ptr(self._V_dev), _ptr(W), _ptr(Hc), ctypes.byref(out), self._stream()), 'tnmf_hip_energy_beta'))
-        if self._world > 1:
-            t = torch.tensor([out.value], dtype=torch.float64, device=self._device)
-            self._all_reduce(t)
-            return float(t.item())
-        return float(out.value)
+                        kp[0], kl[0], kp[1], kl[1], kp[2], kl[2])
+                with self._timed('update_H'):
+                    if beta == 2.:
+                        return self._lib.tnmf_hip_update_H_ex(*args, self._stream()), 'tnmf_hip_update_H_ex'
+                    return self._lib.tnmf_hip_update_H_beta(*args, float(beta), self._stream()), 'tnmf_hip_update_H_beta'
+        self._call_resident_H(Hs, W, True, run, lateral)
 
     # -- a whole mini-batch epoch in one call -------------------------------------------------------------------
     @property
@@ -815,13 +677,14 @@ class HIP_Backend(Backend):
                 arr[i].kind = _lib.OP_UPDATE_H
             else:
                 arr[i].kind, arr[i].a, arr[i].b = _lib.OP_GRAD_W, float(op[2]), float(op[3])
-        self._validate_H_cache(H, W)
-        with self._timed('schedule'):
-            _lib.check(self._lib.tnmf_hip_run_schedule(
-                self._ctx, ctypes.byref(self._geom(H.shape[0], W.shape[0], ld)), _ptr(self._V_dev), _ptr(W), _ptr(H),
-                _ptr(self._R_scratch), _ptr(acc), arr, len(ops), float(eps), float(sparsity), self._stream()),
-                'tnmf_hip_run_schedule')
-        self._note_H_cache(H, W)
+
+        def run(Hc, ld):
+            with self._timed('schedule'):
+                return self._lib.tnmf_hip_run_schedule(
+                    self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)), _ptr(self._V_dev), _ptr(W),
+                    _ptr(Hc), _ptr(self._R_scratch), _ptr(acc), arr, len(ops), float(eps), float(sparsity),
+                    self._stream()), 'tnmf_hip_run_schedule'
+        self._call_resident_H(H, W, True, run)
 
     def apply_W(self, W: torch.Tensor, negpos: torch.Tensor, eps: float = 1e-9) -> None:
         """W = W * neg / (pos + eps), then normalise over the atom axes (TransformInvariantNMF.py:232-238)."""
@@ -833,18 +696,45 @@ class HIP_Backend(Backend):
             _lib.check(self._lib.tnmf_hip_apply_W(self._ctx, ctypes.byref(g), _ptr(W), _ptr(negpos), float(eps),
                                                   self._stream()), 'tnmf_hip_apply_W')
 
-    def local_gradient_W(self, V, W: torch.Tensor, H: torch.Tensor, s: slice = sliceNone) -> torch.Tensor:
-        """This rank's [neg | pos] of the W gradient as one [2, M, C, *A] buffer, NOT yet summed over ranks."""
-        return self._local_grad_W(W, H, s)
+    def local_gradient_W(self, V, W: torch.Tensor, H: torch.Tensor, s: slice = sliceNone, beta: float = 2.,
+                         eps: float = 1e-9) -> torch.Tensor:
+        """This rank's [neg | pos] of the W gradient as one [2, M, C, *A] buffer, NOT yet summed over ranks
+        -> tnmf_hip_grad_W_beta (beta == 2: tnmf_hip_grad_W_fused)."""
+        self._check_beta(beta)
+        ls = self._local(s)
+        Hs, Vs = H[ls], self._V_dev[ls]
+        self._check_W(W)
+        self._check_H(Hs, W.shape[0])
+        Hs = self._pad(Hs)
+        negpos = torch.empty_like(self._negpos)
+        Rs = self._R_scratch[ls] if Hs.shape[0] else None
+
+        def run(Hc, ld):
+            g = self._geom(Hc.shape[0], W.shape[0], ld)
+            r_valid = 0
+            if self._timeline is not None and Hc.shape[0]:
+                with self._timed('reconstruct'):
+                    rc = self._lib.tnmf_hip_reconstruct(self._ctx, ctypes.byref(g), _ptr(W), _ptr(Hc), _ptr(Rs),
+                                                        self._stream())
+                if rc != 0:
+                    return rc, 'tnmf_hip_reconstruct'
+                r_valid = 1
+            with self._timed('grad_W'):
+                rc = self._lib.tnmf_hip_grad_W_beta(self._ctx, ctypes.byref(g), _ptr(Vs), _ptr(W), _ptr(Hc), _ptr(Rs),
+                                                    r_valid, _ptr(negpos), float(beta), float(eps), self._stream())
+            return rc, 'tnmf_hip_grad_W_beta'
+        self._call_resident_H(Hs, W, False, run)
+        return negpos
 
     def all_reduce_gradient_W(self, negpos: torch.Tensor) -> torch.Tensor:
         """Sum a [neg | pos] buffer over the ranks of the process group (one RCCL all-reduce over xGMI)."""
         self._all_reduce(negpos)
         return negpos
 
-    def fused_update_W(self, V, W: torch.Tensor, H: torch.Tensor, s: slice = sliceNone, eps: float = 1e-9) -> None:
+    def fused_update_W(self, V, W: torch.Tensor, H: torch.Tensor, s: slice = sliceNone, eps: float = 1e-9,
+                       beta: float = 2.) -> None:
         """One W half step, in place: local gradient, all-reduce over the ranks, MU + normalise
         (reference: TransformInvariantNMF.py:240-244)."""
-        negpos = self._local_grad_W(W, H, s)
+        negpos = self.local_gradient_W(V, W, H, s, beta=beta, eps=eps)
         self._all_reduce(negpos)
         self.apply_W(W, negpos, eps)

@@ -768,9 +768,9 @@ int tnmf_hip_normalize_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, void *W, 
     return launch_apply_normalize_W(g, dtype, W, nullptr, nullptr, 0.0, false, s);
 }
 
-int tnmf_hip_energy(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *W, const void *H,
-                    double *out_host, void *stream) {
-    if (is_vol(geom)) return vol_api_energy(ctx, geom, V, W, H, out_host, stream);
+// the energy on one or two shift axes: 1/2 sum (V - R)^2, or with beta != NULL sum D_beta(V | R + eps) (*beta != 2)
+static int energy_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *W, const void *H,
+                     double *out_host, const double *beta, double eps, void *stream) {
     ENTER(ctx, geom);
     if (!out_host) return TNMF_E_NULL;
     if (g.N == 0) {
@@ -782,11 +782,19 @@ int tnmf_hip_energy(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V,
     CHECK(ensure_scratch(ctx, sc.total));
     void *Rs = ws_at(ctx, sc.r_off);
     CHECK(do_reconstruct(ctx, g, dtype, W, H, Rs, s));
-    double *red = reinterpret_cast<double *>(ws_at(ctx, sc.red_off));
-    CHECK(launch_half_sqdiff(ctx, dtype, V, Rs, (size_t)g.N * g.C * g.Dy * g.Dx, red, red + kEnergyPartials, s));
+    double *red = reinterpret_cast<double *>(ws_at(ctx, sc.red_off));   // (kEnergyPartials >= kBetaPartials words + result)
+    const size_t n = (size_t)g.N * g.C * g.Dy * g.Dx;
+    CHECK(beta ? launch_beta_energy(ctx, dtype, *beta, eps, V, Rs, n, red, red + kEnergyPartials, s)
+               : launch_half_sqdiff(ctx, dtype, V, Rs, n, red, red + kEnergyPartials, s));
     TNMF_HIP_TRY(hipMemcpyAsync(out_host, red + kEnergyPartials, sizeof(double), hipMemcpyDeviceToHost, s));
     TNMF_HIP_TRY(hipStreamSynchronize(s));
     return TNMF_OK;
+}
+
+int tnmf_hip_energy(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *W, const void *H,
+                    double *out_host, void *stream) {
+    if (is_vol(geom)) return vol_api_energy(ctx, geom, V, W, H, out_host, stream);
+    return energy_2d(ctx, geom, V, W, H, out_host, nullptr, 0.0, stream);
 }
 
 int tnmf_hip_energy_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, double beta, double eps, const void *V,
@@ -794,22 +802,7 @@ int tnmf_hip_energy_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, double be
     if (beta == 2.0) return tnmf_hip_energy(ctx, geom, V, W, H, out_host, stream);
     if (!ctx || !geom) return TNMF_E_NULL;
     if (is_vol(geom) || !beta_ok(beta)) return TNMF_E_UNSUPPORTED;
-    ENTER(ctx, geom);
-    if (!out_host) return TNMF_E_NULL;
-    if (g.N == 0) {
-        *out_host = 0.0;
-        return TNMF_OK;
-    }
-    if (!V || !W || !H) return TNMF_E_NULL;
-    const Scratch sc = plan_scratch(ctx, g, dtype);
-    CHECK(ensure_scratch(ctx, sc.total));
-    void *Rs = ws_at(ctx, sc.r_off);
-    CHECK(do_reconstruct(ctx, g, dtype, W, H, Rs, s));
-    double *red = reinterpret_cast<double *>(ws_at(ctx, sc.red_off));   // (kEnergyPartials == kBetaPartials words + result)
-    CHECK(launch_beta_energy(ctx, dtype, beta, eps, V, Rs, (size_t)g.N * g.C * g.Dy * g.Dx, red, red + kEnergyPartials, s));
-    TNMF_HIP_TRY(hipMemcpyAsync(out_host, red + kEnergyPartials, sizeof(double), hipMemcpyDeviceToHost, s));
-    TNMF_HIP_TRY(hipStreamSynchronize(s));
-    return TNMF_OK;
+    return energy_2d(ctx, geom, V, W, H, out_host, &beta, eps, stream);
 }
 
 int tnmf_hip_beta_fields(tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *R, void *Q,
@@ -868,29 +861,11 @@ int tnmf_hip_fold_H(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, cons
     return launch_pad_fold(ctx, g, dtype, mode, true, Gpad, G, s);
 }
 
-int tnmf_hip_update_H(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *W, void *H_inout,
-                      void *R_scratch, int r_is_valid, double eps, double sparsity, void *stream) {
-    if (is_vol(geom)) return vol_api_update_H(ctx, geom, V, W, H_inout, R_scratch, r_is_valid, eps, sparsity, stream);
-    ENTER(ctx, geom);
-    if (g.N == 0) return TNMF_OK;
-    if (!V || !W || !H_inout) return TNMF_E_NULL;
-    void *Rs = R_scratch;
-    if (!Rs) {
-        if (r_is_valid) return TNMF_E_NULL;
-        const Scratch sc = plan_scratch(ctx, g, dtype);
-        CHECK(ensure_scratch(ctx, sc.total));
-        Rs = ws_at(ctx, sc.r_off);
-    }
-    if (!r_is_valid) CHECK(do_reconstruct(ctx, g, dtype, W, H_inout, Rs, s));
-    double reg = eps;
-    if (sparsity > 0) reg += sparsity;  // TransformInvariantNMF.py:227-230
-    return do_corr_W(ctx, g, dtype, V, Rs, W, H_inout, nullptr, nullptr, true, reg, s);
-}
-
-// the H half step of tnmf_hip_update_H_ex on one or two shift axes; beta != NULL: of the beta-divergence (*beta != 2),
-// the fields (Q, P) of the reconstruction standing in for (V, R) in every correlation
+// the H half step of tnmf_hip_update_H / _update_H_ex on one or two shift axes; beta != NULL: of the beta-divergence
+// (*beta != 2), the fields (Q, P) of the reconstruction standing in for (V, R) in every correlation.  r_is_valid ('valid'
+// mode only): R_scratch already holds the reconstruction of H_inout
 static int update_H_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *V, const void *W,
-                       void *H_inout, void *R_scratch, double eps, double sparsity, double inhibition,
+                       void *H_inout, void *R_scratch, int r_is_valid, double eps, double sparsity, double inhibition,
                        double cross_inhibition, const double *kernel0, int len0, const double *kernel1, int len1,
                        const double *beta, void *stream) {
     ENTER(ctx, geom);
@@ -905,6 +880,7 @@ static int update_H_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, c
     const size_t es = esize(dtype);
     void *Rs = R_scratch;
     if (!Rs) {
+        if (r_is_valid) return TNMF_E_NULL;
         const Scratch sc = plan_scratch(ctx, g, dtype);
         CHECK(ensure_scratch(ctx, sc.total));
         Rs = ws_at(ctx, sc.r_off);
@@ -924,7 +900,7 @@ static int update_H_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, c
             E = ctx->hw;
             CHECK(launch_inhibition(ctx, dtype, g.N, g.M, g.Hy, g.Hs, H_inout, E, ky, ly, kx, lx, inhibition, xc, s));
         }
-        CHECK(do_reconstruct(ctx, g, dtype, W, H_inout, Rs, s));
+        if (!r_is_valid) CHECK(do_reconstruct(ctx, g, dtype, W, H_inout, Rs, s));
         if (beta) CHECK(beta_fields_of(ctx, g, dtype, *beta, eps, V, Rs, &V, s));
         int rc = do_corr_W(ctx, g, dtype, V, Rs, W, H_inout, nullptr, nullptr, true, reg, s, E);
         if (!E || (rc != TNMF_E_UNSUPPORTED && rc != TNMF_E_STRIDE)) return rc;
@@ -963,6 +939,13 @@ static int update_H_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, c
     return launch_fold_update(ctx, g, dtype, mode, Sy, Sx, H_inout, negp, posp, E, reg, s);
 }
 
+int tnmf_hip_update_H(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *W, void *H_inout,
+                      void *R_scratch, int r_is_valid, double eps, double sparsity, void *stream) {
+    if (is_vol(geom)) return vol_api_update_H(ctx, geom, V, W, H_inout, R_scratch, r_is_valid, eps, sparsity, stream);
+    return update_H_2d(ctx, geom, TNMF_MODE_VALID, V, W, H_inout, R_scratch, r_is_valid, eps, sparsity, 0.0, 0.0, nullptr,
+                       0, nullptr, 0, nullptr, stream);
+}
+
 int tnmf_hip_update_H_ex(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *V, const void *W,
                          void *H_inout, void *R_scratch, double eps, double sparsity, double inhibition,
                          double cross_inhibition, const double *kernel0, int len0, const double *kernel1, int len1,
@@ -973,8 +956,8 @@ int tnmf_hip_update_H_ex(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode,
         return vol_api_update_H_ex(ctx, geom, mode, V, W, H_inout, R_scratch, eps, sparsity, inhibition, cross_inhibition,
                                    kern, klen, stream);
     }
-    return update_H_2d(ctx, geom, mode, V, W, H_inout, R_scratch, eps, sparsity, inhibition, cross_inhibition, kernel0,
-                       len0, kernel1, len1, nullptr, stream);
+    return update_H_2d(ctx, geom, mode, V, W, H_inout, R_scratch, 0, eps, sparsity, inhibition, cross_inhibition,
+                       kernel0, len0, kernel1, len1, nullptr, stream);
 }
 
 int tnmf_hip_update_H_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *V, const void *W,
@@ -986,8 +969,25 @@ int tnmf_hip_update_H_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mod
                                     cross_inhibition, kernel0, len0, kernel1, len1, kernel2, len2, stream);
     if (!ctx || !geom) return TNMF_E_NULL;
     if (is_vol(geom) || !beta_ok(beta)) return TNMF_E_UNSUPPORTED;
-    return update_H_2d(ctx, geom, mode, V, W, H_inout, R_scratch, eps, sparsity, inhibition, cross_inhibition, kernel0,
-                       len0, kernel1, len1, &beta, stream);
+    return update_H_2d(ctx, geom, mode, V, W, H_inout, R_scratch, 0, eps, sparsity, inhibition, cross_inhibition,
+                       kernel0, len0, kernel1, len1, &beta, stream);
+}
+
+// the W gradient into [neg | pos] on one or two shift axes; beta != NULL: of the beta-divergence (*beta != 2), the fields
+// (Q, P) of the reconstruction standing in for (V, R)
+static int grad_W_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *W, const void *H,
+                     void *R_scratch, int r_is_valid, void *negpos, const double *beta, double eps, void *stream) {
+    ENTER(ctx, geom);
+    if (!negpos || !W || (g.N > 0 && (!V || !H))) return TNMF_E_NULL;
+    const Scratch sc = plan_scratch(ctx, g, dtype);
+    CHECK(ensure_scratch(ctx, sc.total));
+    if (r_is_valid && !R_scratch) return TNMF_E_NULL;
+    void *Rs = R_scratch ? R_scratch : ws_at(ctx, sc.r_off);
+    if (!r_is_valid) CHECK(do_reconstruct(ctx, g, dtype, W, H, Rs, s));
+    if (beta && g.N > 0) CHECK(beta_fields_of(ctx, g, dtype, *beta, eps, V, Rs, &V, s));
+    char *np = static_cast<char *>(negpos);
+    const size_t wbytes = (size_t)g.M * g.C * g.Ay * g.Ax * esize(dtype);
+    return do_corr_H(ctx, g, dtype, sc, V, Rs, H, np, np + wbytes, s);
 }
 
 int tnmf_hip_grad_W_fused(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *W, const void *H,
@@ -1000,16 +1000,7 @@ int tnmf_hip_grad_W_fused(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const vo
         return vol_api_grad_W(ctx, geom, V, R_scratch, r_is_valid, W, H, np3,
                               np3 + (size_t)vv.M * vv.C * vol_avox(vv) * esize(geom->dtype), stream);
     }
-    ENTER(ctx, geom);
-    if (!negpos || !W || (g.N > 0 && (!V || !H))) return TNMF_E_NULL;
-    const Scratch sc = plan_scratch(ctx, g, dtype);
-    CHECK(ensure_scratch(ctx, sc.total));
-    if (r_is_valid && !R_scratch) return TNMF_E_NULL;
-    void *Rs = R_scratch ? R_scratch : ws_at(ctx, sc.r_off);
-    if (!r_is_valid) CHECK(do_reconstruct(ctx, g, dtype, W, H, Rs, s));
-    char *np = static_cast<char *>(negpos);
-    const size_t wbytes = (size_t)g.M * g.C * g.Ay * g.Ax * esize(dtype);
-    return do_corr_H(ctx, g, dtype, sc, V, Rs, H, np, np + wbytes, s);
+    return grad_W_2d(ctx, geom, V, W, H, R_scratch, r_is_valid, negpos, nullptr, 0.0, stream);
 }
 
 int tnmf_hip_grad_W_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *W, const void *H,
@@ -1017,20 +1008,7 @@ int tnmf_hip_grad_W_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const voi
     if (beta == 2.0) return tnmf_hip_grad_W_fused(ctx, geom, V, W, H, R_scratch, r_is_valid, negpos, stream);
     if (!ctx || !geom) return TNMF_E_NULL;
     if (is_vol(geom) || !beta_ok(beta)) return TNMF_E_UNSUPPORTED;
-    ENTER(ctx, geom);
-    if (!negpos || !W || (g.N > 0 && (!V || !H))) return TNMF_E_NULL;
-    const Scratch sc = plan_scratch(ctx, g, dtype);
-    CHECK(ensure_scratch(ctx, sc.total));
-    if (r_is_valid && !R_scratch) return TNMF_E_NULL;
-    void *Rs = R_scratch ? R_scratch : ws_at(ctx, sc.r_off);
-    const void *Q = V;
-    if (g.N > 0) {
-        if (!r_is_valid) CHECK(do_reconstruct(ctx, g, dtype, W, H, Rs, s));
-        CHECK(beta_fields_of(ctx, g, dtype, beta, eps, V, Rs, &Q, s));
-    }
-    char *np = static_cast<char *>(negpos);
-    const size_t wbytes = (size_t)g.M * g.C * g.Ay * g.Ax * esize(dtype);
-    return do_corr_H(ctx, g, dtype, sc, Q, Rs, H, np, np + wbytes, s);
+    return grad_W_2d(ctx, geom, V, W, H, R_scratch, r_is_valid, negpos, &beta, eps, stream);
 }
 
 int tnmf_hip_run_schedule(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, void *W_inout, void *H_inout,
