@@ -29,6 +29,8 @@
 extern "C" {
 #endif
 
+/* 8 since the beta-divergence entry points; the weighted entry points came later as a purely additive change (no
+ * existing signature or return code changed), so the version stayed 8. */
 #define TNMF_HIP_ABI_VERSION 8
 
 enum {
@@ -313,6 +315,42 @@ int tnmf_hip_grad_W_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const voi
  * V/R~ - log(V/R~) - 1), deterministic two-stage reduction.  beta == 2: tnmf_hip_energy.  Synchronises. */
 int tnmf_hip_energy_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, double beta, double eps, const void *V,
                          const void *W, const void *H, double *out_host, void *stream);
+
+/* ---- weighted objectives (ABI 8, additive: the version stays 8) ------------------------------------------------------
+ * sum G * D_beta(V | R) for an elementwise weight G >= 0 of V's shape and element type (a 0/1 mask of missing or
+ * untrusted samples is the common case).  Its multiplicative updates are those above with both fields multiplied by G:
+ *   beta != 2:  Q = G * V * R~^(beta-2),   P = G * R~^(beta-1)
+ *   beta == 2:  Q = G * V,                 P = G * R          (no clamp, no eps: G == 1 is the Frobenius step)
+ * Entries with G == 0 give Q = P = 0 by selection, and add exactly 0 to the energy: V may hold anything there (NaN and
+ * inf included).  G is a device pointer laid out like V (mini-batch slices offset it like V).
+ *   - G == NULL: each step / energy entry below IS its _beta counterpart (same call, same bits);
+ *   - otherwise any finite beta, 2 included, runs reconstruct -> weighted fields -> the correlations on (Q, P), with
+ *     everything the beta-divergence block above says about Q, P, R_scratch and the spectrum cache (the spectra of V
+ *     are never used for a weighted step);
+ *   - volumes (ndim == 3) and non-finite beta answer TNMF_E_UNSUPPORTED before anything is written.
+ * tnmf_hip_run_schedule stays unweighted. */
+
+/* G * (Q, P) elementwise over n_elems elements of type dtype (forms above).  G must not be NULL.  P may alias R; nothing
+ * else may alias. */
+int tnmf_hip_weighted_fields(tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *G,
+                             const void *R, void *Q, void *P, size_t n_elems, void *stream);
+
+/* tnmf_hip_update_H_beta for the weighted objective. */
+int tnmf_hip_update_H_weighted(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *V, const void *G,
+                               const void *W, void *H_inout, void *R_scratch, double eps, double sparsity,
+                               double inhibition, double cross_inhibition, const double *kernel0, int len0,
+                               const double *kernel1, int len1, const double *kernel2, int len2, double beta,
+                               void *stream);
+
+/* tnmf_hip_grad_W_beta for the weighted objective (the same [neg | pos] buffer). */
+int tnmf_hip_grad_W_weighted(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *G, const void *W,
+                             const void *H, void *R_scratch, int r_is_valid, void *negpos, double beta, double eps,
+                             void *stream);
+
+/* *out_host = sum G * D_beta(V | max(R, 0) + eps), at beta == 2 sum 1/2 G (V - R)^2, in double with the deterministic
+ * two-stage reduction of tnmf_hip_energy_beta.  Synchronises. */
+int tnmf_hip_energy_weighted(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, double beta, double eps, const void *V,
+                             const void *G, const void *W, const void *H, double *out_host, void *stream);
 
 #ifdef __cplusplus
 }

@@ -108,6 +108,11 @@ class TransformInvariantNMF:
                 ``'itakura-saito'`` / 0 or any finite float (scikit-learn's names).  beta != 2 runs the multiplicative
                 updates of Serizel et al. 2016 on the backend's beta hooks, step by step (no one-call schedules), and the
                 energy reports D_beta of R + eps; it needs V > 0 for beta <= 0.
+    ``fit`` / ``fit_batch`` / ``fit_minibatches`` take ``weights``: a finite, non-negative array that broadcasts to V's shape
+    (e.g. ``[N, 1, *D]`` a pixel mask shared by the channels, ``[N, 1, 1, 1]`` per-sample weights), for the weighted
+    objective sum G * D_beta(V | R).  Entries of V whose weight is 0 are not data and may hold anything.  A weighted fit
+    runs on the backend's hooks step by step, like beta != 2; each fit stands alone (a later fit without weights is
+    unweighted).  Not for volumes, not for ``fit_stream``.
     **kwargs : forwarded to the backend constructor (``reconstruction_mode``, ``device``, ``path``, ``init``,
                ``process_group``)
     """
@@ -148,6 +153,7 @@ class TransformInvariantNMF:
         self._use_fused = bool(use_fused_updates)
         self._use_schedules = bool(use_fused_updates)   # mini-batch epochs as one backend call where the backend can
         self._iteration_acc = None
+        self._weighted = False   # the current fit has weights (set by every fit)
 
         self._W = None
         self._H = None
@@ -180,10 +186,16 @@ class TransformInvariantNMF:
         """beta of the objective D_beta (2: Frobenius)."""
         return self._beta
 
+    @property
+    def _plain_frobenius(self) -> bool:
+        """The objective is the plain Frobenius one (beta == 2, no weights): the only one the reference's own lines, the
+        backend's Frobenius-only primitives and the one-call schedules compute."""
+        return self._beta == 2. and not self._weighted
+
     def _objective(self, **kwargs) -> dict:
-        """Keyword arguments of a backend hook, plus ``beta`` and ``eps`` for an objective other than the Frobenius norm
-        (at beta == 2 the hooks are called exactly as on a Frobenius-only backend)."""
-        if self._beta != 2.:
+        """Keyword arguments of a backend hook, plus ``beta`` and ``eps`` for any objective but the plain Frobenius one
+        (for that one the hooks are called exactly as on a Frobenius-only backend)."""
+        if not self._plain_frobenius:
             kwargs.update(beta=self._beta, eps=self.eps)
         return kwargs
 
@@ -209,8 +221,9 @@ class TransformInvariantNMF:
         return getattr(self._backend, name, None) if self._use_fused else None
 
     def _step_hook(self, name: str):
-        """_fused(name); beta != 2 always takes the backend's hook (the reference's Frobenius lines do not apply to it)."""
-        return getattr(self._backend, name) if self._beta != 2. else self._fused(name)
+        """_fused(name); any objective but the plain Frobenius one always takes the backend's hook (the reference's
+        Frobenius lines do not apply to it)."""
+        return getattr(self._backend, name) if not self._plain_frobenius else self._fused(name)
 
     def _update_W(self, s: slice = sliceNone):
         fused = self._step_hook('fused_update_W')
@@ -232,9 +245,10 @@ class TransformInvariantNMF:
                 return
             except NotImplementedError:
                 # (inhibition kernels longer than the backend's fused kernel takes; lateral terms or reconstruction modes
-                # of volumes: nothing has been written, the reference's own lines below do the step -- for the Frobenius
-                # objective only: beta != 2 has no fall-back, a step the backend cannot take raises)
-                if self._beta != 2.:
+                # of volumes: nothing has been written, the reference's own lines below do the step -- for the plain
+                # Frobenius objective only: beta != 2 and weighted fits have no fall-back, a step the backend cannot take
+                # raises)
+                if not self._plain_frobenius:
                     raise
         neg, pos = self._backend.reconstruction_gradient_H(self._V, self._W, self._H, s)
         Hs = self._H[s]
@@ -268,11 +282,21 @@ class TransformInvariantNMF:
         if update_W:
             self._update_W()
 
-    def _initialize_matrices(self, V: np.ndarray, keep_W: bool):
+    def _initialize_matrices(self, V: np.ndarray, keep_W: bool, weights: Optional[np.ndarray] = None):
+        """weights: None, or the materialised weights of _weights_of (the backend receives the keyword only then)."""
         self._V = V
         self._iteration_acc = None    # (sized and typed for the W of ONE fit: a refit may change dtype or device)
+        self._weighted = weights is not None
+        kw = {} if weights is None else {'weights': weights}
         self._W, self._H = self._backend.initialize(self._V, self.atom_shape, self.n_atoms,
-                                                    self._W if keep_W else None, self._axes_W_normalization)
+                                                    self._W if keep_W else None, self._axes_W_normalization, **kw)
+
+    def _init_fit(self, V: np.ndarray, keep_W: bool, G: Optional[np.ndarray]) -> None:
+        # (the existing call form when unweighted: callers that wrap _initialize_matrices keep working)
+        if G is None:
+            self._initialize_matrices(V, keep_W)
+        else:
+            self._initialize_matrices(V, keep_W, weights=G)
 
     def _report(self, what: str, step: int, progress_callback: Optional[ProgressCallback]) -> bool:
         """Returns False when the callback asks to stop."""
@@ -282,20 +306,52 @@ class TransformInvariantNMF:
             self._logger.info(f'{what}: {step}\tEnergy function: {self._energy_function()}')
         return True
 
-    def _check_beta_samples(self, V: np.ndarray):
+    def _weights_of(self, V: np.ndarray, weights) -> Optional[np.ndarray]:
+        """None, or ``weights`` broadcast to V's shape and materialised in V's dtype -- after the checks: a backend without
+        weighted objectives and volumes raise NotImplementedError; weights that do not broadcast, negative, NaN or inf
+        (in V's dtype) raise ValueError."""
+        if weights is None:
+            return None
+        if not getattr(self._backend, 'supports_weights', False):
+            raise NotImplementedError(f'weights: the backend {type(self._backend).__name__} does not support weighted '
+                                      f'objectives')
+        if len(self.atom_shape) == 3:
+            raise NotImplementedError('weights: weighted objectives cover 1 or 2 shift axes, not volumes')
+        try:
+            G = np.broadcast_to(np.asarray(weights), V.shape)
+        except ValueError as exc:
+            raise ValueError(f'weights of shape {np.shape(weights)} do not broadcast to V.shape {V.shape}') from exc
+        if G.dtype.kind not in 'biuf':
+            raise ValueError(f'weights must be real numbers, not {G.dtype}')
+        with np.errstate(over='ignore', invalid='ignore'):
+            G = G.astype(V.dtype)   # (a copy: the backend owns it)
+        if not np.all(np.isfinite(G)):
+            raise ValueError(f'weights must be finite (in {V.dtype.name})')
+        if np.any(G < 0):
+            raise ValueError('weights must be non-negative')
+        return G
+
+    @staticmethod
+    def _check_samples(V: np.ndarray, G: Optional[np.ndarray]):
+        # (entries of zero weight are not data: any value, NaN included, is accepted there)
+        assert np.all(V >= 0) if G is None else np.all((V >= 0) | (G == 0))
+
+    def _check_beta_samples(self, V: np.ndarray, G: Optional[np.ndarray] = None):
         # (R^(beta-1) and V / R of a zero sample: the divergence is not defined there -- scikit-learn refuses the same)
-        if self._beta <= 0 and np.any(V == 0):
+        if self._beta <= 0 and np.any(V == 0 if G is None else (V == 0) & (G > 0)):
             raise ValueError(f'beta_loss={self._beta} <= 0 needs V without zeros')
 
     # -- full batch (reference :282-348) ------------------------------------------------------------------------
     def fit_batch(self, V: np.ndarray, n_iterations: int = 1000, update_H: bool = True, update_W: bool = True,
                   keep_W: bool = False, sparsity_H: float = 0., inhibition_strength: float = 0.,
-                  cross_atom_inhibition_strength: float = 0., progress_callback: ProgressCallback = None):
-        assert np.all(V >= 0)
+                  cross_atom_inhibition_strength: float = 0., progress_callback: ProgressCallback = None,
+                  weights=None):
+        G = self._weights_of(V, weights)
+        self._check_samples(V, G)
         assert update_H or update_W
         assert sparsity_H >= 0 and inhibition_strength >= 0 and cross_atom_inhibition_strength >= 0
-        self._check_beta_samples(V)
-        self._initialize_matrices(V, keep_W)
+        self._check_beta_samples(V, G)
+        self._init_fit(V, keep_W, G)
         h_args = dict(sparsity=sparsity_H, inhibition=inhibition_strength,
                       cross_inhibition=cross_atom_inhibition_strength)
         for iteration in range(n_iterations):
@@ -308,14 +364,16 @@ class TransformInvariantNMF:
     def fit_minibatches(self, V: np.ndarray, algorithm: MiniBatchAlgorithm = MiniBatchAlgorithm.ASG_MU,
                         batch_size: int = 3, n_epochs: int = 1000, sag_lambda: float = 0.2, keep_W: bool = False,
                         sparsity_H: float = 0., inhibition_strength: float = 0.,
-                        cross_atom_inhibition_strength: float = 0., progress_callback: ProgressCallback = None):
-        assert np.all(V >= 0)
+                        cross_atom_inhibition_strength: float = 0., progress_callback: ProgressCallback = None,
+                        weights=None):
+        G = self._weights_of(V, weights)
+        self._check_samples(V, G)
         assert sparsity_H >= 0 and inhibition_strength >= 0 and cross_atom_inhibition_strength >= 0
         assert isinstance(algorithm, MiniBatchAlgorithm)
-        self._check_beta_samples(V)
+        self._check_beta_samples(V, G)
         # The reference decides whether to shuffle V with `algorithm in (5, 6, 7, 8)` (:410), an Enum-vs-int test
         # that is never true, so V is never shuffled; this front end keeps that behaviour.
-        self._initialize_matrices(V, keep_W)
+        self._init_fit(V, keep_W, G)
         plan = getattr(self._backend, 'minibatch_slices', None)
         batches = plan(batch_size) if plan is not None else _sequential_minibatches(len(self._V), batch_size)
         h_args = dict(sparsity=sparsity_H, inhibition=inhibition_strength,
@@ -336,13 +394,13 @@ class TransformInvariantNMF:
 
     def _local_gradient_W(self):
         """The backend's hook for this rank's [neg | pos] of the W gradient (not yet summed over ranks), or None."""
-        if self._beta != 2.:
+        if not self._plain_frobenius:
             return lambda V, W, H, s: self._backend.local_gradient_W(V, W, H, s, **self._objective())
         return self._fused('local_gradient_W')
 
     def _blend_gradient_W(self, acc, lam: float, s: slice):
         """acc <- (1 - lam) * acc + lam * grad_W(batch s); lam == 1 is a plain sum (reference :444-455)."""
-        if self._beta != 2.:
+        if not self._plain_frobenius:
             negpos = self._backend.all_reduce_gradient_W(self._local_gradient_W()(self._V, self._W, self._H, s))
             neg, pos = negpos[0], negpos[1]
         else:
@@ -371,7 +429,7 @@ class TransformInvariantNMF:
     # acc = a * acc + b * gradient_W(batch), ('W',) for the W update from acc -- where the backend offers that and no
     # lateral term is on (those go through tnmf_hip_update_H_ex batch by batch).
     def _scheduler(self, h_args):
-        run = self._fused('run_schedule') if self._use_schedules and self._beta == 2. else None
+        run = self._fused('run_schedule') if self._use_schedules and self._plain_frobenius else None
         if run is None or not getattr(self._backend, 'supports_schedules', False):
             return None
         if h_args['inhibition'] > 0 or h_args['cross_inhibition'] > 0:
@@ -492,6 +550,8 @@ class TransformInvariantNMF:
 
     # -- streaming (reference :506-523) ---------------------------------------------------------------------------
     def fit_stream(self, V: Iterator[np.ndarray], subsample_size: int = 3, max_subsamples: int = None, **kwargs):
+        if kwargs.get('weights') is not None:
+            raise ValueError('fit_stream takes no weights (an iterator of samples has no matching weights)')
         for isub in itertools.count(0):
             subsample = list(itertools.islice(V, subsample_size))
             if not subsample:

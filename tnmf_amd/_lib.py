@@ -25,6 +25,7 @@ EXPORTS = (
     'tnmf_hip_ctx_cache_counters', 'tnmf_hip_sum_parts',
     'tnmf_hip_update_H_ex', 'tnmf_hip_run_schedule', 'tnmf_hip_axpby', 'tnmf_hip_convolve_axis',
     'tnmf_hip_beta_fields', 'tnmf_hip_update_H_beta', 'tnmf_hip_grad_W_beta', 'tnmf_hip_energy_beta',
+    'tnmf_hip_weighted_fields', 'tnmf_hip_update_H_weighted', 'tnmf_hip_grad_W_weighted', 'tnmf_hip_energy_weighted',
 )
 
 MODES = {'valid': 0, 'full': 1, 'circular': 2, 'reflect': 3}
@@ -115,6 +116,11 @@ def load() -> ctypes.CDLL:
                                            ctypes.POINTER(cd), ci, ctypes.POINTER(cd), ci, cd, vp]
     lib.tnmf_hip_grad_W_beta.argtypes = [vp, gp, vp, vp, vp, vp, ci, vp, cd, cd, vp]
     lib.tnmf_hip_energy_beta.argtypes = [vp, gp, cd, cd, vp, vp, vp, ctypes.POINTER(cd), vp]
+    lib.tnmf_hip_weighted_fields.argtypes = [vp, ci, cd, cd, vp, vp, vp, vp, vp, sz, vp]
+    lib.tnmf_hip_update_H_weighted.argtypes = [vp, gp, ci, vp, vp, vp, vp, vp, cd, cd, cd, cd, ctypes.POINTER(cd), ci,
+                                               ctypes.POINTER(cd), ci, ctypes.POINTER(cd), ci, cd, vp]
+    lib.tnmf_hip_grad_W_weighted.argtypes = [vp, gp, vp, vp, vp, vp, vp, ci, vp, cd, cd, vp]
+    lib.tnmf_hip_energy_weighted.argtypes = [vp, gp, cd, cd, vp, vp, vp, vp, ctypes.POINTER(cd), vp]
     lib.tnmf_hip_pad_H.argtypes = [vp, gp, ci, vp, vp, vp]
     lib.tnmf_hip_fold_H.argtypes = [vp, gp, ci, vp, vp, vp]
     for name in EXPORTS:

@@ -138,6 +138,7 @@ class HIP_Backend(Backend):
         self._torch_dtype = None
         self._dtype_code = None
         self._V_dev = None          # this rank's samples, device resident
+        self._G_dev = None          # this rank's weights (weighted fit), laid out like _V_dev; None: unweighted
         self._shard = (0, 0)        # [n0, n1) of the global sample axis held by this rank
         self._R_scratch = None
         self._negpos = None
@@ -320,6 +321,14 @@ class HIP_Backend(Backend):
         if beta != 2. and len(self.atom_shape) == 3:
             raise NotImplementedError('beta-divergence objectives other than the Frobenius norm: 1 or 2 shift axes only')
 
+    # weighted objectives (initialize(..., weights=G)): sum G * D_beta(V | R), the fields above multiplied by G
+    # (include/tnmf_hip.h, "weighted objectives").  While weights are bound every half step and the energy use G[s] of the
+    # resident weights, at any beta; the unweighted gradient primitive of H refuses.  Volumes are not covered.
+    supports_weights = True
+
+    def _G(self, ls: slice):
+        return None if self._G_dev is None else _ptr(self._G_dev[ls])
+
     def _local(self, s: slice) -> slice:
         """Slices address this rank's resident samples (all samples when there is no process group)."""
         lo, hi, step = s.indices(self._shard[1] - self._shard[0])
@@ -398,11 +407,19 @@ class HIP_Backend(Backend):
         self._counts_pending = [int(round(c)) for c in counts.tolist()]
         return self._counts_pending
 
-    def _initialize_matrices(self, V: np.ndarray, atom_shape, n_atoms: int, W=None, axes_W_normalization=None):
+    def _initialize_matrices(self, V: np.ndarray, atom_shape, n_atoms: int, W=None, axes_W_normalization=None,
+                             weights: Optional[np.ndarray] = None):
         if V.dtype not in _DTYPES:
             raise TypeError(f'the hip backend computes in float32 or float64, V has dtype {V.dtype}')
         if len(atom_shape) not in (1, 2, 3):   # (3: volumes, on the direct kernels of tnmf_amd/csrc/volume.hip)
             raise NotImplementedError('the hip backend supports 1, 2 or 3 shift dimensions')
+        if weights is not None:
+            if len(atom_shape) == 3:
+                raise NotImplementedError('weighted objectives: 1 or 2 shift axes only')
+            if weights.shape != V.shape or weights.dtype != V.dtype:
+                raise ValueError(f'weights must have the shape {V.shape} and dtype {V.dtype} of V (the front end '
+                                 f'broadcasts them)')
+        self._G_dev = None
         self._torch_dtype, self._dtype_code = _DTYPES[V.dtype]
         self._foreign_H()
         if self._sharded_input and self._world > 1:
@@ -415,14 +432,17 @@ class HIP_Backend(Backend):
             self.n_samples = N = sum(self._counts)
             n0 = sum(self._counts[:self._rank])
             n0, n1 = self._shard = (n0, n0 + self._counts[self._rank])
-            V_local = V
+            V_local, G_local = V, weights
         else:
             N = self.n_samples
             n0, n1 = self._shard = sharding.shard_bounds(N, self._rank, self._world)
             self._counts = None
-            V_local = V[n0:n1]
+            V_local, G_local = V[n0:n1], None if weights is None else weights[n0:n1]
         with torch.cuda.device(self._device):
             self._V_dev = torch.as_tensor(np.ascontiguousarray(V_local)).to(self._device)
+            if G_local is not None:
+                self._G_dev = torch.as_tensor(np.ascontiguousarray(G_local)).to(self._device)
+                self._V_dev.masked_fill_(self._G_dev == 0, 0)   # (never data: whatever V held there is not kept)
             ld = ctypes.c_int(0)
             if self._mode == 0 and len(atom_shape) == 2 and n1 > n0:
                 _lib.check(self._lib.tnmf_hip_ctx_h_row_stride(self._ctx, ctypes.byref(self._geom(n1 - n0, n_atoms)),
@@ -477,7 +497,11 @@ class HIP_Backend(Backend):
 
     def reconstruction_gradient_H(self, V, W: torch.Tensor, H: torch.Tensor, s: slice = sliceNone):
         """(neg, pos) of H[s]'s shape (reference: NumPy.py:93-120) -> tnmf_hip_grad_H.  `V` is the array given to
-        initialize(); the device-resident copy is used (precedent: NumPy_CachingFFT.py:259,273)."""
+        initialize(); the device-resident copy is used (precedent: NumPy_CachingFFT.py:259,273).  The gradient of the
+        unweighted objective: refused while weights are bound (fused_update_H takes the weighted step)."""
+        if self._G_dev is not None:
+            raise NotImplementedError('reconstruction_gradient_H is unweighted; a weighted fit steps H through '
+                                      'fused_update_H')
         self._check_W(W)
         self._foreign_H()
         ls = self._local(s)
@@ -501,16 +525,22 @@ class HIP_Backend(Backend):
 
     def reconstruction_energy(self, V, W: torch.Tensor, H: torch.Tensor, beta: float = 2., eps: float = 1e-9) -> float:
         """1/2 sum (V - R)^2 (reference: _Backend.py:127-130), or for beta != 2 sum D_beta(V | R + eps)
-        -> tnmf_hip_energy_beta (+ all-reduce)."""
+        -> tnmf_hip_energy_beta (+ all-reduce); with weights bound the weighted sum -> tnmf_hip_energy_weighted."""
         self._check_beta(beta)
         self._check_W(W)
         self._foreign_H()
         self._check_H(H, W.shape[0])
         H = self._pad(H)
         out = ctypes.c_double(0.0)
-        self._call_H(H, False, lambda Hc, ld: (self._lib.tnmf_hip_energy_beta(
-            self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)), float(beta), float(eps),
-            _ptr(self._V_dev), _ptr(W), _ptr(Hc), ctypes.byref(out), self._stream()), 'tnmf_hip_energy_beta'))
+        if self._G_dev is None:
+            self._call_H(H, False, lambda Hc, ld: (self._lib.tnmf_hip_energy_beta(
+                self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)), float(beta), float(eps),
+                _ptr(self._V_dev), _ptr(W), _ptr(Hc), ctypes.byref(out), self._stream()), 'tnmf_hip_energy_beta'))
+        else:
+            self._call_H(H, False, lambda Hc, ld: (self._lib.tnmf_hip_energy_weighted(
+                self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)), float(beta), float(eps),
+                _ptr(self._V_dev), _ptr(self._G_dev), _ptr(W), _ptr(Hc), ctypes.byref(out), self._stream()),
+                'tnmf_hip_energy_weighted'))
         if self._world > 1:
             t = torch.tensor([out.value], dtype=torch.float64, device=self._device)
             self._all_reduce(t)
@@ -586,9 +616,9 @@ class HIP_Backend(Backend):
                        inhibition_kernels: Optional[Sequence[np.ndarray]] = None, beta: float = 2.) -> None:
         """One H half step, in place (reference: TransformInvariantNMF.py:246-271): 'valid' mode without lateral terms on
         the fused kernels (tnmf_hip_update_H); with lateral inhibition / cross-atom inhibition and for the other
-        reconstruction modes through tnmf_hip_update_H_ex, for beta != 2 through tnmf_hip_update_H_beta -- the separable
-        convolution, the lateral terms, the pad, the fold, the beta-divergence fields and the update all run as kernels
-        of the library."""
+        reconstruction modes through tnmf_hip_update_H_ex, for beta != 2 through tnmf_hip_update_H_beta, with weights
+        bound through tnmf_hip_update_H_weighted -- the separable convolution, the lateral terms, the pad, the fold, the
+        (weighted) beta-divergence fields and the update all run as kernels of the library."""
         self._check_beta(beta)
         ls = self._local(s)
         Hs, Vs = H[ls], self._V_dev[ls]
@@ -598,7 +628,8 @@ class HIP_Backend(Backend):
         self._check_H(Hs, W.shape[0])
         Rs = self._R_scratch[ls]
         lateral = inhibition > 0 or cross_inhibition > 0
-        if self._mode == 0 and not lateral and beta == 2.:
+        Gs = self._G(ls)
+        if self._mode == 0 and not lateral and beta == 2. and Gs is None:
             def run(Hc, ld):
                 g = self._geom(Hc.shape[0], W.shape[0], ld)
                 r_valid = 0
@@ -626,6 +657,9 @@ class HIP_Backend(Backend):
                         _ptr(Hc), _ptr(Rs), float(eps), float(sparsity), float(inhibition), float(cross_inhibition),
                         kp[0], kl[0], kp[1], kl[1], kp[2], kl[2])
                 with self._timed('update_H'):
+                    if Gs is not None:
+                        return self._lib.tnmf_hip_update_H_weighted(*args[:4], Gs, *args[4:], float(beta),
+                                                                    self._stream()), 'tnmf_hip_update_H_weighted'
                     if beta == 2.:
                         return self._lib.tnmf_hip_update_H_ex(*args, self._stream()), 'tnmf_hip_update_H_ex'
                     return self._lib.tnmf_hip_update_H_beta(*args, float(beta), self._stream()), 'tnmf_hip_update_H_beta'
@@ -660,6 +694,8 @@ class HIP_Backend(Backend):
         b * gradient_W(slice), W update from acc (reference: TransformInvariantNMF.py:444-504) -- issued by ONE call of
         the library (tnmf_hip_run_schedule): no interpreter time and no host round trip between the batch steps."""
         assert self.supports_schedules
+        if self._G_dev is not None:
+            raise NotImplementedError('run_schedule is unweighted; a weighted fit runs its epochs step by step')
         self._check_W(W)
         self._check_H(H, W.shape[0])
         ld = self._row_stride(H)
@@ -699,7 +735,7 @@ class HIP_Backend(Backend):
     def local_gradient_W(self, V, W: torch.Tensor, H: torch.Tensor, s: slice = sliceNone, beta: float = 2.,
                          eps: float = 1e-9) -> torch.Tensor:
         """This rank's [neg | pos] of the W gradient as one [2, M, C, *A] buffer, NOT yet summed over ranks
-        -> tnmf_hip_grad_W_beta (beta == 2: tnmf_hip_grad_W_fused)."""
+        -> tnmf_hip_grad_W_beta (beta == 2: tnmf_hip_grad_W_fused); with weights bound tnmf_hip_grad_W_weighted."""
         self._check_beta(beta)
         ls = self._local(s)
         Hs, Vs = H[ls], self._V_dev[ls]
@@ -708,6 +744,7 @@ class HIP_Backend(Backend):
         Hs = self._pad(Hs)
         negpos = torch.empty_like(self._negpos)
         Rs = self._R_scratch[ls] if Hs.shape[0] else None
+        Gs = self._G(ls)
 
         def run(Hc, ld):
             g = self._geom(Hc.shape[0], W.shape[0], ld)
@@ -720,6 +757,10 @@ class HIP_Backend(Backend):
                     return rc, 'tnmf_hip_reconstruct'
                 r_valid = 1
             with self._timed('grad_W'):
+                if Gs is not None:
+                    return self._lib.tnmf_hip_grad_W_weighted(
+                        self._ctx, ctypes.byref(g), _ptr(Vs), Gs, _ptr(W), _ptr(Hc), _ptr(Rs), r_valid, _ptr(negpos),
+                        float(beta), float(eps), self._stream()), 'tnmf_hip_grad_W_weighted'
                 rc = self._lib.tnmf_hip_grad_W_beta(self._ctx, ctypes.byref(g), _ptr(Vs), _ptr(W), _ptr(Hc), _ptr(Rs),
                                                     r_valid, _ptr(negpos), float(beta), float(eps), self._stream())
             return rc, 'tnmf_hip_grad_W_beta'

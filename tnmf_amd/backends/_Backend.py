@@ -19,7 +19,8 @@ to_ndarray                      _Backend.py:46-49                      backend-n
 ==============================  =====================================  ===========================================
 
 Optional hooks a backend may add (the front-end uses them when present):
-``multiplicative_update``, ``fused_update_H``, ``fused_update_W``.
+``multiplicative_update``, ``fused_update_H``, ``fused_update_W``.  A backend that declares ``supports_weights`` takes
+``initialize(..., weights=G)`` and then evaluates the weighted objective in its hooks and energy.
 """
 import abc
 from typing import Optional, Sequence, Tuple, Union
@@ -57,9 +58,15 @@ class Backend(abc.ABC):
 
     # -- set-up -------------------------------------------------------------------------------------------
     def initialize(self, V: np.ndarray, atom_shape: Tuple[int, ...], n_atoms: int, W=None,
-                   axes_W_normalization: Axes = None):
+                   axes_W_normalization: Axes = None, weights: Optional[np.ndarray] = None):
+        """``weights``: elementwise weights of V's shape and dtype for the weighted objective, only for a backend that
+        declares ``supports_weights`` (handed on to ``_initialize_matrices`` as the keyword ``weights``)."""
         self._set_dimensions(V, atom_shape)
-        return self._initialize_matrices(V, atom_shape, n_atoms, W, axes_W_normalization)
+        if weights is None:
+            return self._initialize_matrices(V, atom_shape, n_atoms, W, axes_W_normalization)
+        if not getattr(self, 'supports_weights', False):
+            raise NotImplementedError(f'the backend {type(self).__name__} does not support weighted objectives')
+        return self._initialize_matrices(V, atom_shape, n_atoms, W, axes_W_normalization, weights=weights)
 
     def _set_dimensions(self, V: np.ndarray, atom_shape: Tuple[int, ...]) -> None:
         self.atom_shape = tuple(atom_shape)

@@ -305,14 +305,15 @@ int do_corr_H(tnmf_hip_ctx *ctx, const Geo &g, int dtype, const Scratch &sc, con
 }
 
 
-// beta-divergence steps (beta != 2): the fields of R (ctx->qb receives Q, R is overwritten with P); *Q_out = Q.  Q sits at
-// a fixed address with new contents every call: the FFT family is told never to take it for the samples it caches.
-int beta_fields_of(tnmf_hip_ctx *ctx, const Geo &g, int dtype, double beta, double eps, const void *V, void *R,
-                   const void **Q_out, hipStream_t s) {
+// beta-divergence (beta != NULL, *beta != 2) and weighted (G != NULL, any beta) steps: the fields of R (ctx->qb receives Q,
+// R is overwritten with P); *Q_out = Q.  Q sits at a fixed address with new contents every call: the FFT family is told
+// never to take it for the samples it caches.
+int beta_fields_of(tnmf_hip_ctx *ctx, const Geo &g, int dtype, const double *beta, double eps, const void *V,
+                   const void *G, void *R, const void **Q_out, hipStream_t s) {
     const size_t n = (size_t)g.N * g.C * g.Dy * g.Dx;
     CHECK(ensure_buffer(&ctx->qb, &ctx->qb_bytes, align_up(n * esize(dtype), 256), false));
     ctx->fft.V_volatile = ctx->qb;
-    CHECK(launch_beta_fields(ctx, dtype, beta, eps, V, R, ctx->qb, R, n, s));
+    CHECK(launch_beta_fields(ctx, dtype, beta ? *beta : 2.0, eps, V, G, R, ctx->qb, R, n, s));
     *Q_out = ctx->qb;
     return TNMF_OK;
 }
@@ -768,9 +769,10 @@ int tnmf_hip_normalize_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, void *W, 
     return launch_apply_normalize_W(g, dtype, W, nullptr, nullptr, 0.0, false, s);
 }
 
-// the energy on one or two shift axes: 1/2 sum (V - R)^2, or with beta != NULL sum D_beta(V | R + eps) (*beta != 2)
-static int energy_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *W, const void *H,
-                     double *out_host, const double *beta, double eps, void *stream) {
+// the energy on one or two shift axes: 1/2 sum (V - R)^2, or with beta != NULL sum D_beta(V | R + eps) (*beta != 2); with
+// G != NULL the weighted sum of either
+static int energy_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *G, const void *W,
+                     const void *H, double *out_host, const double *beta, double eps, void *stream) {
     ENTER(ctx, geom);
     if (!out_host) return TNMF_E_NULL;
     if (g.N == 0) {
@@ -784,8 +786,8 @@ static int energy_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V
     CHECK(do_reconstruct(ctx, g, dtype, W, H, Rs, s));
     double *red = reinterpret_cast<double *>(ws_at(ctx, sc.red_off));   // (kEnergyPartials >= kBetaPartials words + result)
     const size_t n = (size_t)g.N * g.C * g.Dy * g.Dx;
-    CHECK(beta ? launch_beta_energy(ctx, dtype, *beta, eps, V, Rs, n, red, red + kEnergyPartials, s)
-               : launch_half_sqdiff(ctx, dtype, V, Rs, n, red, red + kEnergyPartials, s));
+    CHECK(beta || G ? launch_beta_energy(ctx, dtype, beta ? *beta : 2.0, eps, V, G, Rs, n, red, red + kEnergyPartials, s)
+                    : launch_half_sqdiff(ctx, dtype, V, Rs, n, red, red + kEnergyPartials, s));
     TNMF_HIP_TRY(hipMemcpyAsync(out_host, red + kEnergyPartials, sizeof(double), hipMemcpyDeviceToHost, s));
     TNMF_HIP_TRY(hipStreamSynchronize(s));
     return TNMF_OK;
@@ -794,7 +796,7 @@ static int energy_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V
 int tnmf_hip_energy(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *W, const void *H,
                     double *out_host, void *stream) {
     if (is_vol(geom)) return vol_api_energy(ctx, geom, V, W, H, out_host, stream);
-    return energy_2d(ctx, geom, V, W, H, out_host, nullptr, 0.0, stream);
+    return energy_2d(ctx, geom, V, nullptr, W, H, out_host, nullptr, 0.0, stream);
 }
 
 int tnmf_hip_energy_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, double beta, double eps, const void *V,
@@ -802,7 +804,15 @@ int tnmf_hip_energy_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, double be
     if (beta == 2.0) return tnmf_hip_energy(ctx, geom, V, W, H, out_host, stream);
     if (!ctx || !geom) return TNMF_E_NULL;
     if (is_vol(geom) || !beta_ok(beta)) return TNMF_E_UNSUPPORTED;
-    return energy_2d(ctx, geom, V, W, H, out_host, &beta, eps, stream);
+    return energy_2d(ctx, geom, V, nullptr, W, H, out_host, &beta, eps, stream);
+}
+
+int tnmf_hip_energy_weighted(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, double beta, double eps, const void *V,
+                             const void *G, const void *W, const void *H, double *out_host, void *stream) {
+    if (!G) return tnmf_hip_energy_beta(ctx, geom, beta, eps, V, W, H, out_host, stream);
+    if (!ctx || !geom) return TNMF_E_NULL;
+    if (is_vol(geom) || !beta_ok(beta)) return TNMF_E_UNSUPPORTED;
+    return energy_2d(ctx, geom, V, G, W, H, out_host, beta == 2.0 ? nullptr : &beta, eps, stream);
 }
 
 int tnmf_hip_beta_fields(tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *R, void *Q,
@@ -813,7 +823,18 @@ int tnmf_hip_beta_fields(tnmf_hip_ctx *ctx, int dtype, double beta, double eps, 
     if (n_elems > 0 && (!V || !R || !Q || !P)) return TNMF_E_NULL;
     if (n_elems > 0 && (Q == V || Q == R || P == V)) return TNMF_E_NULL;   // (only P may alias R)
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
-    return launch_beta_fields(ctx, dtype, beta, eps, V, R, Q, P, n_elems, static_cast<hipStream_t>(stream));
+    return launch_beta_fields(ctx, dtype, beta, eps, V, nullptr, R, Q, P, n_elems, static_cast<hipStream_t>(stream));
+}
+
+int tnmf_hip_weighted_fields(tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *G,
+                             const void *R, void *Q, void *P, size_t n_elems, void *stream) {
+    if (!ctx || !G) return TNMF_E_NULL;
+    if (dtype != 0 && dtype != 1) return TNMF_E_DTYPE;
+    if (!beta_ok(beta)) return TNMF_E_UNSUPPORTED;
+    if (n_elems > 0 && (!V || !R || !Q || !P)) return TNMF_E_NULL;
+    if (n_elems > 0 && (Q == V || Q == G || Q == R || P == V || P == G)) return TNMF_E_NULL;   // (only P may alias R)
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return launch_beta_fields(ctx, dtype, beta, eps, V, G, R, Q, P, n_elems, static_cast<hipStream_t>(stream));
 }
 
 int tnmf_hip_convolve_multi_1d(tnmf_hip_ctx *ctx, int dtype, int ndim, size_t rows, const int *shape,
@@ -862,12 +883,12 @@ int tnmf_hip_fold_H(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, cons
 }
 
 // the H half step of tnmf_hip_update_H / _update_H_ex on one or two shift axes; beta != NULL: of the beta-divergence
-// (*beta != 2), the fields (Q, P) of the reconstruction standing in for (V, R) in every correlation.  r_is_valid ('valid'
-// mode only): R_scratch already holds the reconstruction of H_inout
-static int update_H_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *V, const void *W,
-                       void *H_inout, void *R_scratch, int r_is_valid, double eps, double sparsity, double inhibition,
-                       double cross_inhibition, const double *kernel0, int len0, const double *kernel1, int len1,
-                       const double *beta, void *stream) {
+// (*beta != 2), G != NULL: of the weighted objective -- either way the fields (Q, P) of the reconstruction standing in for
+// (V, R) in every correlation.  r_is_valid ('valid' mode only): R_scratch already holds the reconstruction of H_inout
+static int update_H_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *V, const void *G,
+                       const void *W, void *H_inout, void *R_scratch, int r_is_valid, double eps, double sparsity,
+                       double inhibition, double cross_inhibition, const double *kernel0, int len0,
+                       const double *kernel1, int len1, const double *beta, void *stream) {
     ENTER(ctx, geom);
     if (mode < TNMF_MODE_VALID || mode > TNMF_MODE_REFLECT) return TNMF_E_UNSUPPORTED;
     if (g.N == 0) return TNMF_OK;
@@ -901,7 +922,7 @@ static int update_H_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, c
             CHECK(launch_inhibition(ctx, dtype, g.N, g.M, g.Hy, g.Hs, H_inout, E, ky, ly, kx, lx, inhibition, xc, s));
         }
         if (!r_is_valid) CHECK(do_reconstruct(ctx, g, dtype, W, H_inout, Rs, s));
-        if (beta) CHECK(beta_fields_of(ctx, g, dtype, *beta, eps, V, Rs, &V, s));
+        if (beta || G) CHECK(beta_fields_of(ctx, g, dtype, beta, eps, V, G, Rs, &V, s));
         int rc = do_corr_W(ctx, g, dtype, V, Rs, W, H_inout, nullptr, nullptr, true, reg, s, E);
         if (!E || (rc != TNMF_E_UNSUPPORTED && rc != TNMF_E_STRIDE)) return rc;
         // this kernel family has no epilogue for the extra term (nothing has been written): unfused gradient into the
@@ -932,7 +953,7 @@ static int update_H_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, c
     fft_invalidate(ctx);   // the padded copy lives at the same address every call, with new contents
     CHECK(launch_pad_fold(ctx, g, dtype, mode, false, H_inout, Hp, s));
     CHECK(do_reconstruct(ctx, g, dtype, W, Hp, Rs, s));
-    if (beta) CHECK(beta_fields_of(ctx, g, dtype, *beta, eps, V, Rs, &V, s));
+    if (beta || G) CHECK(beta_fields_of(ctx, g, dtype, beta, eps, V, G, Rs, &V, s));
     CHECK(do_corr_W(ctx, g, dtype, V, Rs, W, nullptr, negp, posp, false, 0.0, s));
     if (lateral) CHECK(launch_inhibition(ctx, dtype, g.N, g.M, Sy, Sx, H_inout, E, ky, ly, kx, lx, inhibition, xc, s));
     fft_invalidate(ctx);
@@ -942,8 +963,8 @@ static int update_H_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, c
 int tnmf_hip_update_H(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *W, void *H_inout,
                       void *R_scratch, int r_is_valid, double eps, double sparsity, void *stream) {
     if (is_vol(geom)) return vol_api_update_H(ctx, geom, V, W, H_inout, R_scratch, r_is_valid, eps, sparsity, stream);
-    return update_H_2d(ctx, geom, TNMF_MODE_VALID, V, W, H_inout, R_scratch, r_is_valid, eps, sparsity, 0.0, 0.0, nullptr,
-                       0, nullptr, 0, nullptr, stream);
+    return update_H_2d(ctx, geom, TNMF_MODE_VALID, V, nullptr, W, H_inout, R_scratch, r_is_valid, eps, sparsity, 0.0, 0.0,
+                       nullptr, 0, nullptr, 0, nullptr, stream);
 }
 
 int tnmf_hip_update_H_ex(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *V, const void *W,
@@ -956,8 +977,8 @@ int tnmf_hip_update_H_ex(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode,
         return vol_api_update_H_ex(ctx, geom, mode, V, W, H_inout, R_scratch, eps, sparsity, inhibition, cross_inhibition,
                                    kern, klen, stream);
     }
-    return update_H_2d(ctx, geom, mode, V, W, H_inout, R_scratch, 0, eps, sparsity, inhibition, cross_inhibition,
-                       kernel0, len0, kernel1, len1, nullptr, stream);
+    return update_H_2d(ctx, geom, mode, V, nullptr, W, H_inout, R_scratch, 0, eps, sparsity, inhibition,
+                       cross_inhibition, kernel0, len0, kernel1, len1, nullptr, stream);
 }
 
 int tnmf_hip_update_H_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *V, const void *W,
@@ -969,14 +990,29 @@ int tnmf_hip_update_H_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mod
                                     cross_inhibition, kernel0, len0, kernel1, len1, kernel2, len2, stream);
     if (!ctx || !geom) return TNMF_E_NULL;
     if (is_vol(geom) || !beta_ok(beta)) return TNMF_E_UNSUPPORTED;
-    return update_H_2d(ctx, geom, mode, V, W, H_inout, R_scratch, 0, eps, sparsity, inhibition, cross_inhibition,
-                       kernel0, len0, kernel1, len1, &beta, stream);
+    return update_H_2d(ctx, geom, mode, V, nullptr, W, H_inout, R_scratch, 0, eps, sparsity, inhibition,
+                       cross_inhibition, kernel0, len0, kernel1, len1, &beta, stream);
 }
 
-// the W gradient into [neg | pos] on one or two shift axes; beta != NULL: of the beta-divergence (*beta != 2), the fields
-// (Q, P) of the reconstruction standing in for (V, R)
-static int grad_W_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *W, const void *H,
-                     void *R_scratch, int r_is_valid, void *negpos, const double *beta, double eps, void *stream) {
+int tnmf_hip_update_H_weighted(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *V, const void *G,
+                               const void *W, void *H_inout, void *R_scratch, double eps, double sparsity,
+                               double inhibition, double cross_inhibition, const double *kernel0, int len0,
+                               const double *kernel1, int len1, const double *kernel2, int len2, double beta,
+                               void *stream) {
+    if (!G)
+        return tnmf_hip_update_H_beta(ctx, geom, mode, V, W, H_inout, R_scratch, eps, sparsity, inhibition,
+                                      cross_inhibition, kernel0, len0, kernel1, len1, kernel2, len2, beta, stream);
+    if (!ctx || !geom) return TNMF_E_NULL;
+    if (is_vol(geom) || !beta_ok(beta)) return TNMF_E_UNSUPPORTED;
+    return update_H_2d(ctx, geom, mode, V, G, W, H_inout, R_scratch, 0, eps, sparsity, inhibition, cross_inhibition,
+                       kernel0, len0, kernel1, len1, beta == 2.0 ? nullptr : &beta, stream);
+}
+
+// the W gradient into [neg | pos] on one or two shift axes; beta != NULL: of the beta-divergence (*beta != 2), G != NULL:
+// of the weighted objective -- the fields (Q, P) of the reconstruction standing in for (V, R)
+static int grad_W_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *G, const void *W,
+                     const void *H, void *R_scratch, int r_is_valid, void *negpos, const double *beta, double eps,
+                     void *stream) {
     ENTER(ctx, geom);
     if (!negpos || !W || (g.N > 0 && (!V || !H))) return TNMF_E_NULL;
     const Scratch sc = plan_scratch(ctx, g, dtype);
@@ -984,7 +1020,7 @@ static int grad_W_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V
     if (r_is_valid && !R_scratch) return TNMF_E_NULL;
     void *Rs = R_scratch ? R_scratch : ws_at(ctx, sc.r_off);
     if (!r_is_valid) CHECK(do_reconstruct(ctx, g, dtype, W, H, Rs, s));
-    if (beta && g.N > 0) CHECK(beta_fields_of(ctx, g, dtype, *beta, eps, V, Rs, &V, s));
+    if ((beta || G) && g.N > 0) CHECK(beta_fields_of(ctx, g, dtype, beta, eps, V, G, Rs, &V, s));
     char *np = static_cast<char *>(negpos);
     const size_t wbytes = (size_t)g.M * g.C * g.Ay * g.Ax * esize(dtype);
     return do_corr_H(ctx, g, dtype, sc, V, Rs, H, np, np + wbytes, s);
@@ -1000,7 +1036,7 @@ int tnmf_hip_grad_W_fused(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const vo
         return vol_api_grad_W(ctx, geom, V, R_scratch, r_is_valid, W, H, np3,
                               np3 + (size_t)vv.M * vv.C * vol_avox(vv) * esize(geom->dtype), stream);
     }
-    return grad_W_2d(ctx, geom, V, W, H, R_scratch, r_is_valid, negpos, nullptr, 0.0, stream);
+    return grad_W_2d(ctx, geom, V, nullptr, W, H, R_scratch, r_is_valid, negpos, nullptr, 0.0, stream);
 }
 
 int tnmf_hip_grad_W_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *W, const void *H,
@@ -1008,7 +1044,16 @@ int tnmf_hip_grad_W_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const voi
     if (beta == 2.0) return tnmf_hip_grad_W_fused(ctx, geom, V, W, H, R_scratch, r_is_valid, negpos, stream);
     if (!ctx || !geom) return TNMF_E_NULL;
     if (is_vol(geom) || !beta_ok(beta)) return TNMF_E_UNSUPPORTED;
-    return grad_W_2d(ctx, geom, V, W, H, R_scratch, r_is_valid, negpos, &beta, eps, stream);
+    return grad_W_2d(ctx, geom, V, nullptr, W, H, R_scratch, r_is_valid, negpos, &beta, eps, stream);
+}
+
+int tnmf_hip_grad_W_weighted(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, const void *G, const void *W,
+                             const void *H, void *R_scratch, int r_is_valid, void *negpos, double beta, double eps,
+                             void *stream) {
+    if (!G) return tnmf_hip_grad_W_beta(ctx, geom, V, W, H, R_scratch, r_is_valid, negpos, beta, eps, stream);
+    if (!ctx || !geom) return TNMF_E_NULL;
+    if (is_vol(geom) || !beta_ok(beta)) return TNMF_E_UNSUPPORTED;
+    return grad_W_2d(ctx, geom, V, G, W, H, R_scratch, r_is_valid, negpos, beta == 2.0 ? nullptr : &beta, eps, stream);
 }
 
 int tnmf_hip_run_schedule(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V, void *W_inout, void *H_inout,

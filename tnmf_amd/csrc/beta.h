@@ -8,12 +8,19 @@
 #pragma once
 #include "common.h"
 
-// beta in {0, 1, 2} runs exact arithmetic (divisions and products, no pow); beta = 1 writes P = 1 without reading R
-// for it.  P may alias R.  n elements of type dtype.
-int launch_beta_fields(const tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *R,
-                       void *Q, void *P, size_t n, hipStream_t s);
-// *out_dev = D_beta(V | max(R, 0) + eps) summed in double (beta != 2), deterministic: per-block partials, then one block
-// sums them in a fixed order.  partials: at least kBetaPartials doubles.
+//
+// The weighted objective sum G * D_beta(V | R) (G >= 0 elementwise, of V's type) multiplies both fields by G:
+//   Q = G * V * R~^(beta - 2),  P = G * R~^(beta - 1)   (beta = 2: Q = G * V, P = G * R -- no clamp, no eps)
+// and entries with G == 0 give Q = P = 0 by selection, whatever V and R hold there.
+
+// beta in {0, 1, 2} runs exact arithmetic (divisions and products, no pow); beta = 1 writes P = 1 (weighted: P = G)
+// without reading R for it.  G == nullptr: unweighted (beta != 2); else weighted, any finite beta.  P may alias R.
+// n elements of type dtype.
+int launch_beta_fields(const tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *G,
+                       const void *R, void *Q, void *P, size_t n, hipStream_t s);
+// *out_dev = D_beta(V | max(R, 0) + eps) summed in double (G == nullptr: beta != 2; else sum G * D_beta, at beta = 2
+// 1/2 G (V - R)^2, with G == 0 entries adding exactly 0), deterministic: per-block partials, then one block sums them in a
+// fixed order.  partials: at least kBetaPartials doubles.
 constexpr int kBetaPartials = 2048;
-int launch_beta_energy(const tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *R,
-                       size_t n, double *partials, double *out_dev, hipStream_t s);
+int launch_beta_energy(const tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *G,
+                       const void *R, size_t n, double *partials, double *out_dev, hipStream_t s);

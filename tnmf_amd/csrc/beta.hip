@@ -1,5 +1,5 @@
-// beta.hip -- the elementwise kernels of the beta-divergence objective (beta.h): the fields Q, P that stand in for V, R
-// in the correlations of a multiplicative update, and the D_beta energy.  Streaming kernels: 16-byte loads and stores
+// beta.hip -- the elementwise kernels of the beta-divergence and weighted objectives (beta.h): the fields Q, P that stand
+// in for V, R in the correlations of a multiplicative update, and the (weighted) D_beta energy.  Streaming kernels: 16-byte loads and stores
 // for aligned operands, a scalar tail for lengths that are not a whole number of vectors.
 #include <cmath>
 #include <cstdint>
@@ -29,6 +29,23 @@ __device__ __forceinline__ void field(T v, T r, T eps, T bm2, T bm1, T &q, T &p)
     }
 }
 
+// the weighted fields G * (Q, P); K == 2 is the weighted Frobenius step itself (Q = G V, P = G R: no clamp, no eps).
+// g <= 0 selects 0: what V and R~^(beta-2) hold there (NaN, inf, an overflow) never reaches Q or P.
+template <int K, typename T>
+__device__ __forceinline__ void wfield(T v, T g, T r, T eps, T bm2, T bm1, T &q, T &p) {
+    T q0, p0;
+    if constexpr (K == 2) {
+        q0 = g * v;
+        p0 = g * r;
+    } else {
+        field<K, T>(v, r, eps, bm2, bm1, q0, p0);
+        q0 = g * q0;
+        p0 = K == 1 ? g : g * p0;
+    }
+    q = g > T(0) ? q0 : T(0);
+    p = g > T(0) ? p0 : T(0);
+}
+
 template <typename T> struct Vec;
 template <> struct Vec<float> { using type = float4; static constexpr int n = 4; };
 template <> struct Vec<double> { using type = double2; static constexpr int n = 2; };
@@ -36,10 +53,11 @@ template <> struct Vec<double> { using type = double2; static constexpr int n = 
 template <typename VT, typename T>
 __device__ __forceinline__ T &lane(VT &v, int i) { return reinterpret_cast<T *>(&v)[i]; }
 
-// vec: all four operands 16-byte aligned -> n / L vector iterations, then the scalar tail; else everything scalar
-template <int K, typename T, bool kVec>
-__global__ __launch_bounds__(kBlock) void k_beta_fields(const T *__restrict__ V, const T *R, T *__restrict__ Q, T *P,
-                                                        size_t n, T eps, T bm2, T bm1) {
+// vec: every operand 16-byte aligned -> n / L vector iterations, then the scalar tail; else everything scalar.
+// kW: weighted (G read on the same path as V and R); else G is not read.
+template <int K, typename T, bool kVec, bool kW>
+__global__ __launch_bounds__(kBlock) void k_beta_fields(const T *__restrict__ V, const T *__restrict__ G, const T *R,
+                                                        T *__restrict__ Q, T *P, size_t n, T eps, T bm2, T bm1) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     size_t done = 0;
@@ -51,9 +69,18 @@ __global__ __launch_bounds__(kBlock) void k_beta_fields(const T *__restrict__ V,
             VT v = reinterpret_cast<const VT *>(V)[i];
             VT r = reinterpret_cast<const VT *>(R)[i];   // (read once: P may alias R)
             VT q, p;
+            if constexpr (kW) {
+                VT g = reinterpret_cast<const VT *>(G)[i];
 #pragma unroll
-            for (int j = 0; j < L; ++j)
-                field<K, T>(lane<VT, T>(v, j), lane<VT, T>(r, j), eps, bm2, bm1, lane<VT, T>(q, j), lane<VT, T>(p, j));
+                for (int j = 0; j < L; ++j)
+                    wfield<K, T>(lane<VT, T>(v, j), lane<VT, T>(g, j), lane<VT, T>(r, j), eps, bm2, bm1,
+                                 lane<VT, T>(q, j), lane<VT, T>(p, j));
+            } else {
+#pragma unroll
+                for (int j = 0; j < L; ++j)
+                    field<K, T>(lane<VT, T>(v, j), lane<VT, T>(r, j), eps, bm2, bm1, lane<VT, T>(q, j),
+                                lane<VT, T>(p, j));
+            }
             reinterpret_cast<VT *>(Q)[i] = q;
             reinterpret_cast<VT *>(P)[i] = p;
         }
@@ -61,7 +88,10 @@ __global__ __launch_bounds__(kBlock) void k_beta_fields(const T *__restrict__ V,
     }
     for (size_t i = done + tid; i < n; i += stride) {
         T q, p;
-        field<K, T>(V[i], R[i], eps, bm2, bm1, q, p);
+        if constexpr (kW)
+            wfield<K, T>(V[i], G[i], R[i], eps, bm2, bm1, q, p);
+        else
+            field<K, T>(V[i], R[i], eps, bm2, bm1, q, p);
         Q[i] = q;
         P[i] = p;
     }
@@ -92,14 +122,29 @@ __device__ __forceinline__ double divergence(double v, double r, double eps, dou
     }
 }
 
-template <int K, typename T>
-__global__ __launch_bounds__(kBlock) void k_beta_energy(const T *__restrict__ V, const T *__restrict__ R, size_t n,
-                                                        double eps, double beta, double *__restrict__ partial) {
+// kW: G * D_beta, and K == 2 (weighted only) 1/2 G (V - R)^2; entries with G <= 0 add exactly 0 (selected, whatever V holds)
+template <int K, typename T, bool kW>
+__global__ __launch_bounds__(kBlock) void k_beta_energy(const T *__restrict__ V, const T *__restrict__ G,
+                                                        const T *__restrict__ R, size_t n, double eps, double beta,
+                                                        double *__restrict__ partial) {
     __shared__ double sh[kBlock / 64];
     double acc = 0.0;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        acc += divergence<K>((double)V[i], (double)R[i], eps, beta);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        if constexpr (kW) {
+            const double g = (double)G[i];
+            double d;
+            if constexpr (K == 2) {
+                const double e = (double)V[i] - (double)R[i];
+                d = 0.5 * e * e;
+            } else {
+                d = divergence<K>((double)V[i], (double)R[i], eps, beta);
+            }
+            acc += g > 0.0 ? g * d : 0.0;
+        } else {
+            acc += divergence<K>((double)V[i], (double)R[i], eps, beta);
+        }
+    }
     const double tot = block_sum(acc, sh);
     if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
@@ -118,63 +163,78 @@ inline int grid_of(size_t work, const tnmf_hip_ctx *ctx) {
     return (int)(want < cap ? (want ? want : 1) : cap);
 }
 
-template <int K, typename T>
-int fields_as(const tnmf_hip_ctx *ctx, double beta, double eps, const void *V, const void *R, void *Q, void *P, size_t n,
-              hipStream_t s) {
-    const bool vec = ((reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(Q) |
-                       reinterpret_cast<uintptr_t>(P)) & 15) == 0;
+template <int K, typename T, bool kW>
+int fields_as(const tnmf_hip_ctx *ctx, double beta, double eps, const void *V, const void *G, const void *R, void *Q,
+              void *P, size_t n, hipStream_t s) {
+    const bool vec = ((reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(G) | reinterpret_cast<uintptr_t>(R) |
+                       reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(P)) & 15) == 0;
     const int grid = grid_of(vec ? n / Vec<T>::n + 1 : n, ctx);
     const T e = (T)eps, bm2 = (T)(beta - 2.0), bm1 = (T)(beta - 1.0);
     if (vec)
-        hipLaunchKernelGGL((k_beta_fields<K, T, true>), dim3(grid), dim3(kBlock), 0, s, (const T *)V, (const T *)R,
-                           (T *)Q, (T *)P, n, e, bm2, bm1);
+        hipLaunchKernelGGL((k_beta_fields<K, T, true, kW>), dim3(grid), dim3(kBlock), 0, s, (const T *)V, (const T *)G,
+                           (const T *)R, (T *)Q, (T *)P, n, e, bm2, bm1);
     else
-        hipLaunchKernelGGL((k_beta_fields<K, T, false>), dim3(grid), dim3(kBlock), 0, s, (const T *)V, (const T *)R,
-                           (T *)Q, (T *)P, n, e, bm2, bm1);
+        hipLaunchKernelGGL((k_beta_fields<K, T, false, kW>), dim3(grid), dim3(kBlock), 0, s, (const T *)V, (const T *)G,
+                           (const T *)R, (T *)Q, (T *)P, n, e, bm2, bm1);
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
 
-template <typename T>
-int fields_typed(const tnmf_hip_ctx *ctx, double beta, double eps, const void *V, const void *R, void *Q, void *P,
-                 size_t n, hipStream_t s) {
-    if (beta == 0.0) return fields_as<0, T>(ctx, beta, eps, V, R, Q, P, n, s);
-    if (beta == 1.0) return fields_as<1, T>(ctx, beta, eps, V, R, Q, P, n, s);
-    if (beta == 2.0) return fields_as<2, T>(ctx, beta, eps, V, R, Q, P, n, s);
-    return fields_as<3, T>(ctx, beta, eps, V, R, Q, P, n, s);
+template <typename T, bool kW>
+int fields_weighted_as(const tnmf_hip_ctx *ctx, double beta, double eps, const void *V, const void *G, const void *R,
+                       void *Q, void *P, size_t n, hipStream_t s) {
+    if (beta == 0.0) return fields_as<0, T, kW>(ctx, beta, eps, V, G, R, Q, P, n, s);
+    if (beta == 1.0) return fields_as<1, T, kW>(ctx, beta, eps, V, G, R, Q, P, n, s);
+    if (beta == 2.0) return fields_as<2, T, kW>(ctx, beta, eps, V, G, R, Q, P, n, s);
+    return fields_as<3, T, kW>(ctx, beta, eps, V, G, R, Q, P, n, s);
 }
 
 template <typename T>
-int energy_typed(const tnmf_hip_ctx *ctx, double beta, double eps, const void *V, const void *R, size_t n, double *partials,
+int fields_typed(const tnmf_hip_ctx *ctx, double beta, double eps, const void *V, const void *G, const void *R, void *Q,
+                 void *P, size_t n, hipStream_t s) {
+    return G ? fields_weighted_as<T, true>(ctx, beta, eps, V, G, R, Q, P, n, s)
+             : fields_weighted_as<T, false>(ctx, beta, eps, V, G, R, Q, P, n, s);
+}
+
+template <int K, typename T, bool kW>
+void energy_as(double beta, double eps, const void *V, const void *G, const void *R, size_t n, double *partials,
+               int grid, hipStream_t s) {
+    hipLaunchKernelGGL((k_beta_energy<K, T, kW>), dim3(grid), dim3(kBlock), 0, s, (const T *)V, (const T *)G,
+                       (const T *)R, n, eps, beta, partials);
+}
+
+template <typename T>
+int energy_typed(double beta, double eps, const void *V, const void *G, const void *R, size_t n, double *partials,
                  int grid, hipStream_t s) {
-    if (beta == 0.0)
-        hipLaunchKernelGGL((k_beta_energy<0, T>), dim3(grid), dim3(kBlock), 0, s, (const T *)V, (const T *)R, n, eps, beta,
-                           partials);
-    else if (beta == 1.0)
-        hipLaunchKernelGGL((k_beta_energy<1, T>), dim3(grid), dim3(kBlock), 0, s, (const T *)V, (const T *)R, n, eps, beta,
-                           partials);
-    else
-        hipLaunchKernelGGL((k_beta_energy<3, T>), dim3(grid), dim3(kBlock), 0, s, (const T *)V, (const T *)R, n, eps, beta,
-                           partials);
+    if (G) {
+        if (beta == 0.0) energy_as<0, T, true>(beta, eps, V, G, R, n, partials, grid, s);
+        else if (beta == 1.0) energy_as<1, T, true>(beta, eps, V, G, R, n, partials, grid, s);
+        else if (beta == 2.0) energy_as<2, T, true>(beta, eps, V, G, R, n, partials, grid, s);
+        else energy_as<3, T, true>(beta, eps, V, G, R, n, partials, grid, s);
+    } else {
+        if (beta == 0.0) energy_as<0, T, false>(beta, eps, V, G, R, n, partials, grid, s);
+        else if (beta == 1.0) energy_as<1, T, false>(beta, eps, V, G, R, n, partials, grid, s);
+        else energy_as<3, T, false>(beta, eps, V, G, R, n, partials, grid, s);
+    }
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
 
 }  // namespace
 
-int launch_beta_fields(const tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *R,
-                       void *Q, void *P, size_t n, hipStream_t s) {
+int launch_beta_fields(const tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *G,
+                       const void *R, void *Q, void *P, size_t n, hipStream_t s) {
     if (n == 0) return TNMF_OK;
-    return dtype == 0 ? fields_typed<float>(ctx, beta, eps, V, R, Q, P, n, s)
-                      : fields_typed<double>(ctx, beta, eps, V, R, Q, P, n, s);
+    return dtype == 0 ? fields_typed<float>(ctx, beta, eps, V, G, R, Q, P, n, s)
+                      : fields_typed<double>(ctx, beta, eps, V, G, R, Q, P, n, s);
 }
 
-int launch_beta_energy(const tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *R,
-                       size_t n, double *partials, double *out_dev, hipStream_t s) {
+int launch_beta_energy(const tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *G,
+                       const void *R, size_t n, double *partials, double *out_dev, hipStream_t s) {
     int grid = grid_of(n, ctx);
     if (grid > kBetaPartials) grid = kBetaPartials;
-    const int rc = dtype == 0 ? energy_typed<float>(ctx, beta, eps, V, R, n, partials, grid, s)
-                              : energy_typed<double>(ctx, beta, eps, V, R, n, partials, grid, s);
+    const int rc = dtype == 0 ? energy_typed<float>(beta, eps, V, G, R, n, partials, grid, s)
+                              : energy_typed<double>(beta, eps, V, G, R, n, partials, grid, s);
     if (rc != TNMF_OK) return rc;
     hipLaunchKernelGGL(k_beta_sum, dim3(1), dim3(kBlock), 0, s, partials, grid, out_dev);
     TNMF_LAUNCH_CHECK();
