@@ -352,6 +352,39 @@ int tnmf_hip_grad_W_weighted(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const
 int tnmf_hip_energy_weighted(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, double beta, double eps, const void *V,
                              const void *G, const void *W, const void *H, double *out_host, void *stream);
 
+/* ---- transform groups: rotation and mirror invariance (ABI 8, additive: the version stays 8) -------------------------
+ * A dictionary W[M,C,*A] stands for M * T effective atoms W_eff[m*T + t] = T_t(W[m]), every T_t a permutation of the
+ * atom's pixels.  The groups, with t in the order below (numpy, a = W[m, c]):
+ *   TNMF_GROUP_FLIP      T = 2   a, a[..., ::-1]                       (1 or 2 shift axes; 2: mirror along x)
+ *   TNMF_GROUP_MIRRORS   T = 4   a, a[:, ::-1], a[::-1, :], a[::-1, ::-1]   (2 shift axes)
+ *   TNMF_GROUP_ROT90     T = 4   np.rot90(a, k), k = 0..3             (2 shift axes, square atoms)
+ *   TNMF_GROUP_DIHEDRAL  T = 8   np.rot90(a, k), k = 0..3, then np.rot90(a[:, ::-1], k), k = 0..3   (likewise)
+ * Every other entry point runs the effective problem as it is: H[N, M*T, *shift], W_eff[M*T, C, *A].  The W half step
+ * takes the gradient of W_eff (tnmf_hip_grad_W_fused / _beta / _weighted on W_eff), folds it onto W with the adjoint of
+ * the expansion, neg[m] = sum_t T_t^-1(neg_eff[m*T + t]) and likewise pos -- BEFORE the collective, which then carries
+ * the M-atom buffer -- and updates W as tnmf_hip_apply_W does, then expands W into W_eff again.
+ * `geom` describes the dictionary: M atoms (the effective count follows from the group), C, ndim and A; N and D are not
+ * read.  Volumes (ndim == 3), unknown groups, groups of two axes on one, and ROT90 / DIHEDRAL on non-square atoms answer
+ * TNMF_E_UNSUPPORTED before anything is written.  Every entry that writes W_eff drops the FFT family's cached spectra of
+ * the dictionary (W_eff keeps its address and changes its contents), as tnmf_hip_apply_W does.
+ * tnmf_hip_run_schedule has no transformed form. */
+enum { TNMF_GROUP_FLIP = 0, TNMF_GROUP_MIRRORS = 1, TNMF_GROUP_ROT90 = 2, TNMF_GROUP_DIHEDRAL = 3 };
+
+/* W_eff[M*T,C,*A] = the expansion of W[M,C,*A] (a permutation: exact). */
+int tnmf_hip_group_expand_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int group, const void *W, void *W_eff,
+                            void *stream);
+
+/* negpos[2,M,C,*A] = the fold of negpos_eff[2,M*T,C,*A]: the T terms of each element summed in ascending t in double,
+ * rounded once to the element type (the float64 fold, rounded). */
+int tnmf_hip_group_fold_grad_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int group, const void *negpos_eff,
+                               void *negpos, void *stream);
+
+/* The single-rank W step after the gradient of W_eff, in one launch: fold, W = W * neg / (pos + eps), W /= its sum over
+ * the atom axes, W_eff = the expansion of the new W.  Same bits as tnmf_hip_group_fold_grad_W, tnmf_hip_apply_W and
+ * tnmf_hip_group_expand_W in a row; negpos_eff is only read (the folded pos + eps is not kept). */
+int tnmf_hip_group_apply_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int group, void *W_inout, void *W_eff_out,
+                           const void *negpos_eff, double eps, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@ from typing import Callable, Iterable, Iterator, List, Optional, Tuple, Union
 
 import numpy as np
 
+from . import transforms as _transforms
 from .backends._Backend import Backend, sliceNone
 
 
@@ -113,16 +114,28 @@ class TransformInvariantNMF:
     objective sum G * D_beta(V | R).  Entries of V whose weight is 0 are not data and may hold anything.  A weighted fit
     runs on the backend's hooks step by step, like beta != 2; each fit stands alone (a later fit without weights is
     unweighted).  Not for volumes, not for ``fit_stream``.
+    transforms : ``None`` (default: shifts only), or a group of atom transforms the model is invariant to as well --
+                 ``'flip'`` (T = 2: the atom and its mirror along the last axis; 1 or 2 shift axes), ``'mirrors'`` (T = 4:
+                 the mirrors along x, y and both), ``'rot90'`` (T = 4: rotations by k * 90 degrees, ``np.rot90(a, k)``;
+                 square atoms) or ``'dihedral'`` (T = 8: the rotations, then the rotations of the mirror along x; square
+                 atoms); tnmf_amd/transforms.py.  Each of the ``n_atoms`` atoms then stands for T effective atoms
+                 ``T_t(W[m])``: ``W`` stays ``[M, C, *A]``, ``H`` is ``[N, M, T, *shift]``, ``transformed_atoms`` is
+                 ``[M, T, C, *A]``.  The effective atoms are atoms for everything on the H side (sparsity, lateral and
+                 cross-atom inhibition over all M * T of them); the W step folds their gradient back onto W.  A transformed
+                 fit runs on the backend's hooks step by step, like beta != 2.  Not for volumes.
     **kwargs : forwarded to the backend constructor (``reconstruction_mode``, ``device``, ``path``, ``init``,
                ``process_group``)
     """
 
     def __init__(self, n_atoms: int, atom_shape: Tuple[int, ...], inhibition_range: Union[int, Tuple[int, ...]] = None,
                  backend: Union[str, Backend] = 'hip', logger: logging.Logger = None, verbose: int = 0,
-                 use_fused_updates: bool = True, beta_loss: Union[str, float] = 2., **kwargs):
+                 use_fused_updates: bool = True, beta_loss: Union[str, float] = 2., transforms: Optional[str] = None,
+                 **kwargs):
         self._beta = beta_loss_value(beta_loss)
         self.atom_shape = tuple(atom_shape)
         self.n_atoms = n_atoms
+        self._transforms = _transforms.check(transforms, self.atom_shape)   # (before anything is built)
+        self.n_transforms = 1 if self._transforms is None else _transforms.size(self._transforms)
         k = len(self.atom_shape)
         if inhibition_range is None:
             self._inhibition_range = tuple(a - 1 for a in self.atom_shape)
@@ -147,6 +160,9 @@ class TransformInvariantNMF:
         if self._beta != 2. and not getattr(self._backend, 'supports_beta_loss', False):
             raise NotImplementedError(f'beta_loss={beta_loss!r}: the backend {type(self._backend).__name__} does not '
                                       f'support beta-divergence objectives')
+        if self._transforms is not None and not getattr(self._backend, 'supports_transforms', False):
+            raise NotImplementedError(f'transforms={transforms!r}: the backend {type(self._backend).__name__} does not '
+                                      f'support transform groups')
 
         self._logger = logger if logger is not None else logging.getLogger(self.__class__.__name__)
         self._logger.setLevel([logging.ERROR, logging.WARNING, logging.INFO, logging.DEBUG][verbose])
@@ -156,6 +172,7 @@ class TransformInvariantNMF:
         self._weighted = False   # the current fit has weights (set by every fit)
 
         self._W = None
+        self._W_eff = None   # with transforms: the M * T effective atoms, expanded from W after every change of W
         self._H = None
         self._V = None
         self._shuffle_idx = None
@@ -168,7 +185,21 @@ class TransformInvariantNMF:
     @property
     def H(self) -> np.ndarray:
         H = self._backend.to_ndarray(self._H)
-        return H if self._shuffle_idx is None else H[np.argsort(self._shuffle_idx)]
+        H = H if self._shuffle_idx is None else H[np.argsort(self._shuffle_idx)]
+        if self._transforms is not None:
+            H = H.reshape((H.shape[0], self.n_atoms, self.n_transforms) + H.shape[2:])
+        return H
+
+    @property
+    def transforms(self) -> Optional[str]:
+        """The transform group (None: shifts only)."""
+        return self._transforms
+
+    @property
+    def transformed_atoms(self) -> np.ndarray:
+        """[M, T, C, *A]: atom m in orientation t, ``T_t(W[m])`` (T = 1 without transforms)."""
+        W = self._backend.to_ndarray(self._W_dict)
+        return W.reshape((self.n_atoms, self.n_transforms) + W.shape[1:])
 
     @property
     def V(self) -> np.ndarray:
@@ -176,10 +207,24 @@ class TransformInvariantNMF:
 
     @property
     def R(self) -> np.ndarray:
-        return self._backend.to_ndarray(self._backend.reconstruct(self._W, self._H))
+        return self._backend.to_ndarray(self._backend.reconstruct(self._W_dict, self._H))
 
     def R_partial(self, i_atom: int) -> np.ndarray:
-        return self._backend.to_ndarray(self._backend.partial_reconstruct(self._W, self._H, i_atom))
+        """Atom ``i_atom``'s contribution to R (with transforms: in all its orientations)."""
+        if self._transforms is None:
+            return self._backend.to_ndarray(self._backend.partial_reconstruct(self._W, self._H, i_atom))
+        eff = slice(i_atom * self.n_transforms, (i_atom + 1) * self.n_transforms)
+        return self._backend.to_ndarray(self._backend.reconstruct(self._W_eff[eff], self._H[:, eff]))
+
+    @property
+    def _W_dict(self):
+        """The dictionary the H side works with: W, or with transforms the M * T effective atoms."""
+        return self._W if self._transforms is None else self._W_eff
+
+    def _expand_W(self) -> None:
+        """W has changed: expand it into the effective atoms again (no-op without transforms)."""
+        if self._transforms is not None:
+            self._backend.expand_W(self._W, self._transforms, self._W_eff)
 
     @property
     def beta_loss(self) -> float:
@@ -188,9 +233,9 @@ class TransformInvariantNMF:
 
     @property
     def _plain_frobenius(self) -> bool:
-        """The objective is the plain Frobenius one (beta == 2, no weights): the only one the reference's own lines, the
-        backend's Frobenius-only primitives and the one-call schedules compute."""
-        return self._beta == 2. and not self._weighted
+        """The objective is the plain Frobenius one (beta == 2, no weights) of a model without transforms: the only one the
+        reference's own lines, the backend's Frobenius-only primitives and the one-call schedules compute."""
+        return self._beta == 2. and not self._weighted and self._transforms is None
 
     def _objective(self, **kwargs) -> dict:
         """Keyword arguments of a backend hook, plus ``beta`` and ``eps`` for any objective but the plain Frobenius one
@@ -200,7 +245,7 @@ class TransformInvariantNMF:
         return kwargs
 
     def _energy_function(self) -> float:
-        return self._backend.reconstruction_energy(self._V, self._W, self._H, **self._objective())
+        return self._backend.reconstruction_energy(self._V, self._W_dict, self._H, **self._objective())
 
     # -- elementwise multiplicative update (reference :217-238) ----------------------------------------------
     def _multiplicative_update(self, arr, neg, pos, sparsity: float = 0., normalization_axes=None):
@@ -226,6 +271,11 @@ class TransformInvariantNMF:
         return getattr(self._backend, name) if not self._plain_frobenius else self._fused(name)
 
     def _update_W(self, s: slice = sliceNone):
+        if self._transforms is not None:
+            # gradient of W_eff, folded onto W (before any collective), MU + normalise, expanded again
+            self._backend.fused_update_W_transformed(self._V, self._W, self._W_eff, self._H, s, self._transforms,
+                                                     **self._objective(eps=self.eps))
+            return
         fused = self._step_hook('fused_update_W')
         if fused is not None:
             fused(self._V, self._W, self._H, s, **self._objective(eps=self.eps))
@@ -241,7 +291,7 @@ class TransformInvariantNMF:
             kw = dict(inhibition=inhibition, cross_inhibition=cross_inhibition,
                       inhibition_kernels=self._inhibition_kernels_1D) if lateral else {}
             try:
-                fused(self._V, self._W, self._H, s, sparsity=sparsity, **self._objective(eps=self.eps, **kw))
+                fused(self._V, self._W_dict, self._H, s, sparsity=sparsity, **self._objective(eps=self.eps, **kw))
                 return
             except NotImplementedError:
                 # (inhibition kernels longer than the backend's fused kernel takes; lateral terms or reconstruction modes
@@ -250,7 +300,7 @@ class TransformInvariantNMF:
                 # raises)
                 if not self._plain_frobenius:
                     raise
-        neg, pos = self._backend.reconstruction_gradient_H(self._V, self._W, self._H, s)
+        neg, pos = self._backend.reconstruction_gradient_H(self._V, self._W_dict, self._H, s)
         Hs = self._H[s]
         assert neg.shape == Hs.shape and pos.shape == Hs.shape
         if lateral:
@@ -262,7 +312,7 @@ class TransformInvariantNMF:
                 pos += term
             if cross_inhibition > 0:
                 term = g.sum(axis=1, keepdims=True) - g   # what all OTHER atoms contribute at this shift
-                term *= cross_inhibition / (self.n_atoms - 1)
+                term *= cross_inhibition / (Hs.shape[1] - 1)
                 pos += term
         self._multiplicative_update(Hs, neg, pos, sparsity=sparsity)
 
@@ -288,8 +338,11 @@ class TransformInvariantNMF:
         self._iteration_acc = None    # (sized and typed for the W of ONE fit: a refit may change dtype or device)
         self._weighted = weights is not None
         kw = {} if weights is None else {'weights': weights}
+        if self._transforms is not None:
+            kw['transforms'] = self._transforms
         self._W, self._H = self._backend.initialize(self._V, self.atom_shape, self.n_atoms,
                                                     self._W if keep_W else None, self._axes_W_normalization, **kw)
+        self._W_eff = None if self._transforms is None else self._backend.expand_W(self._W, self._transforms)
 
     def _init_fit(self, V: np.ndarray, keep_W: bool, G: Optional[np.ndarray]) -> None:
         # (the existing call form when unweighted: callers that wrap _initialize_matrices keep working)
@@ -393,7 +446,12 @@ class TransformInvariantNMF:
         self._logger.info('MiniBatch TNMF finished.')
 
     def _local_gradient_W(self):
-        """The backend's hook for this rank's [neg | pos] of the W gradient (not yet summed over ranks), or None."""
+        """The backend's hook for this rank's [neg | pos] of the W gradient (not yet summed over ranks), or None.  With
+        transforms: the gradient of the effective atoms folded onto W (M-atom buffers from here on: the accumulators and
+        the collective never see the effective ones)."""
+        if self._transforms is not None:
+            return lambda V, W, H, s: self._backend.fold_gradient_W(
+                self._backend.local_gradient_W(V, self._W_eff, H, s, **self._objective()), self._transforms)
         if not self._plain_frobenius:
             return lambda V, W, H, s: self._backend.local_gradient_W(V, W, H, s, **self._objective())
         return self._fused('local_gradient_W')
@@ -423,6 +481,7 @@ class TransformInvariantNMF:
     def _apply_accumulated_W(self, acc):
         # NB: like the reference (:232), the update adds eps to the `pos` accumulator in place
         self._multiplicative_update(self._W, acc[0], acc[1], normalization_axes=self._axes_W_normalization)
+        self._expand_W()
 
     # One epoch of a mini-batch schedule as ONE call of the backend (HIP_Backend.run_schedule -> tnmf_hip_run_schedule):
     # the epoch functions below describe the epoch as a list of operations -- ('H', batch), ('G', batch, a, b) for
@@ -470,6 +529,7 @@ class TransformInvariantNMF:
                     total += part
             total = self._backend.all_reduce_gradient_W(total)
             self._backend.apply_W(self._W, total, eps=self.eps)
+            self._expand_W()
             return None
         acc = None
         for batch in batches:

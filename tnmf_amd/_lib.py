@@ -26,9 +26,13 @@ EXPORTS = (
     'tnmf_hip_update_H_ex', 'tnmf_hip_run_schedule', 'tnmf_hip_axpby', 'tnmf_hip_convolve_axis',
     'tnmf_hip_beta_fields', 'tnmf_hip_update_H_beta', 'tnmf_hip_grad_W_beta', 'tnmf_hip_energy_beta',
     'tnmf_hip_weighted_fields', 'tnmf_hip_update_H_weighted', 'tnmf_hip_grad_W_weighted', 'tnmf_hip_energy_weighted',
+    'tnmf_hip_group_expand_W', 'tnmf_hip_group_fold_grad_W', 'tnmf_hip_group_apply_W',
 )
 
 MODES = {'valid': 0, 'full': 1, 'circular': 2, 'reflect': 3}
+
+# transform groups (TNMF_GROUP_*): name -> id; tnmf_amd/transforms.py defines them
+GROUPS = {'flip': 0, 'mirrors': 1, 'rot90': 2, 'dihedral': 3}
 
 PATHS = {'auto': 0, 'generic': 1, 'mfma': 2, 'fft': 3, 'hybrid': 4, 'split': 5}
 
@@ -121,6 +125,9 @@ def load() -> ctypes.CDLL:
                                                ctypes.POINTER(cd), ci, ctypes.POINTER(cd), ci, cd, vp]
     lib.tnmf_hip_grad_W_weighted.argtypes = [vp, gp, vp, vp, vp, vp, vp, ci, vp, cd, cd, vp]
     lib.tnmf_hip_energy_weighted.argtypes = [vp, gp, cd, cd, vp, vp, vp, vp, ctypes.POINTER(cd), vp]
+    lib.tnmf_hip_group_expand_W.argtypes = [vp, gp, ci, vp, vp, vp]
+    lib.tnmf_hip_group_fold_grad_W.argtypes = [vp, gp, ci, vp, vp, vp]
+    lib.tnmf_hip_group_apply_W.argtypes = [vp, gp, ci, vp, vp, vp, cd, vp]
     lib.tnmf_hip_pad_H.argtypes = [vp, gp, ci, vp, vp, vp]
     lib.tnmf_hip_fold_H.argtypes = [vp, gp, ci, vp, vp, vp]
     for name in EXPORTS:

@@ -17,7 +17,7 @@ import weakref
 import numpy as np
 import torch
 
-from .. import _lib, sharding
+from .. import _lib, sharding, transforms as _transforms
 from ._Backend import Backend, sliceNone
 
 _DTYPES = {np.dtype('float32'): (torch.float32, 0), np.dtype('float64'): (torch.float64, 1)}
@@ -326,6 +326,17 @@ class HIP_Backend(Backend):
     # resident weights, at any beta; the unweighted gradient primitive of H refuses.  Volumes are not covered.
     supports_weights = True
 
+    # transform groups (initialize(..., transforms=name)): the resident activations have n_atoms * T effective atoms, W
+    # keeps n_atoms; the front end holds W_eff = expand_W(W) and hands it to every hook in the place of W.  The W step is
+    # fused_update_W_transformed: gradient of W_eff, folded onto W before the collective, MU + normalise, expanded again
+    # (include/tnmf_hip.h, "transform groups").  Volumes are not covered.
+    supports_transforms = True
+
+    def _group_id(self, transforms: str) -> int:
+        if len(self.atom_shape) == 3:
+            raise NotImplementedError('transforms: 1 or 2 shift axes only')
+        return _lib.GROUPS[_transforms.check(transforms, self.atom_shape)]
+
     def _G(self, ls: slice):
         return None if self._G_dev is None else _ptr(self._G_dev[ls])
 
@@ -408,7 +419,13 @@ class HIP_Backend(Backend):
         return self._counts_pending
 
     def _initialize_matrices(self, V: np.ndarray, atom_shape, n_atoms: int, W=None, axes_W_normalization=None,
-                             weights: Optional[np.ndarray] = None):
+                             weights: Optional[np.ndarray] = None, transforms: Optional[str] = None):
+        """With ``transforms``: H (and everything sized by it) has n_atoms * T effective atoms, W has n_atoms; H is drawn
+        first, then W, as without."""
+        if transforms is not None:
+            self._group_id(transforms)
+        n_dict = n_atoms
+        n_atoms = n_atoms * (1 if transforms is None else _transforms.size(transforms))
         if V.dtype not in _DTYPES:
             raise TypeError(f'the hip backend computes in float32 or float64, V has dtype {V.dtype}')
         if len(atom_shape) not in (1, 2, 3):   # (3: volumes, on the direct kernels of tnmf_amd/csrc/volume.hip)
@@ -462,14 +479,15 @@ class HIP_Backend(Backend):
                     H[i].copy_(torch.from_numpy(h))
             if W is None:
                 if self._init_mode == 'device' and self._world == 1:
-                    W = torch.empty((n_atoms, self.n_channels) + self.atom_shape, dtype=self._torch_dtype,
+                    W = torch.empty((n_dict, self.n_channels) + self.atom_shape, dtype=self._torch_dtype,
                                     device=self._device).uniform_(0, 1).neg_().add_(1)
                     self.normalize(W, axes_W_normalization)
                 else:
-                    W = torch.from_numpy(sharding.reference_init_W(n_atoms, self.n_channels, self.atom_shape,
+                    W = torch.from_numpy(sharding.reference_init_W(n_dict, self.n_channels, self.atom_shape,
                                                                    V.dtype)).to(self._device)
             else:
                 self._check_W(W)
+                assert W.shape[0] == n_dict
             self._R_scratch = torch.empty_like(self._V_dev)
             self._negpos = torch.empty((2, n_atoms, self.n_channels) + self.atom_shape, dtype=self._torch_dtype,
                                        device=self._device)
@@ -779,3 +797,65 @@ class HIP_Backend(Backend):
         negpos = self.local_gradient_W(V, W, H, s, beta=beta, eps=eps)
         self._all_reduce(negpos)
         self.apply_W(W, negpos, eps)
+
+    # -- transform groups ---------------------------------------------------------------------------------------------
+    def expand_W(self, W: torch.Tensor, transforms: str, W_eff: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """W_eff[m * T + t] = T_t(W[m]) -> tnmf_hip_group_expand_W (into W_eff when given; it drops the cached spectra of
+        the dictionary)."""
+        group = self._group_id(transforms)
+        self._check_W(W)
+        shape = (W.shape[0] * _transforms.size(transforms),) + tuple(W.shape[1:])
+        if W_eff is None:
+            W_eff = torch.empty(shape, dtype=W.dtype, device=W.device)
+        self._check_W(W_eff)
+        assert tuple(W_eff.shape) == shape
+        g = self._geom(0, W.shape[0])
+        with self._timed('group_expand_W'):
+            _lib.check(self._lib.tnmf_hip_group_expand_W(self._ctx, ctypes.byref(g), group, _ptr(W), _ptr(W_eff),
+                                                         self._stream()), 'tnmf_hip_group_expand_W')
+        return W_eff
+
+    def fold_gradient_W(self, negpos_eff: torch.Tensor, transforms: str) -> torch.Tensor:
+        """[neg | pos] of W_eff ([2, M * T, C, *A]) -> [neg | pos] of W ([2, M, C, *A]) -> tnmf_hip_group_fold_grad_W."""
+        group = self._group_id(transforms)
+        T = _transforms.size(transforms)
+        assert negpos_eff.is_contiguous() and negpos_eff.dtype == self._torch_dtype and negpos_eff.shape[1] % T == 0
+        assert tuple(negpos_eff.shape[2:]) == (self.n_channels,) + self.atom_shape and negpos_eff.shape[0] == 2
+        M = negpos_eff.shape[1] // T
+        negpos = torch.empty((2, M) + tuple(negpos_eff.shape[2:]), dtype=negpos_eff.dtype, device=negpos_eff.device)
+        g = self._geom(0, M)
+        with self._timed('group_fold_grad_W'):
+            _lib.check(self._lib.tnmf_hip_group_fold_grad_W(self._ctx, ctypes.byref(g), group, _ptr(negpos_eff),
+                                                            _ptr(negpos), self._stream()), 'tnmf_hip_group_fold_grad_W')
+        return negpos
+
+    def apply_W_transformed(self, W: torch.Tensor, W_eff: torch.Tensor, negpos_eff: torch.Tensor, transforms: str,
+                            eps: float = 1e-9) -> None:
+        """Fold, W = W * neg / (pos + eps), normalise, expand into W_eff: one launch (tnmf_hip_group_apply_W), the same
+        bits as fold_gradient_W -> apply_W -> expand_W."""
+        group = self._group_id(transforms)
+        self._check_W(W)
+        self._check_W(W_eff)
+        T = _transforms.size(transforms)
+        assert W_eff.shape[0] == W.shape[0] * T
+        assert negpos_eff.is_contiguous() and tuple(negpos_eff.shape) == (2,) + tuple(W_eff.shape)
+        assert negpos_eff.dtype == W.dtype and negpos_eff.device == W.device
+        g = self._geom(0, W.shape[0])
+        with self._timed('group_apply_W'):
+            _lib.check(self._lib.tnmf_hip_group_apply_W(self._ctx, ctypes.byref(g), group, _ptr(W), _ptr(W_eff),
+                                                        _ptr(negpos_eff), float(eps), self._stream()),
+                       'tnmf_hip_group_apply_W')
+
+    def fused_update_W_transformed(self, V, W: torch.Tensor, W_eff: torch.Tensor, H: torch.Tensor, s: slice = sliceNone,
+                                   transforms: str = None, eps: float = 1e-9, beta: float = 2.) -> None:
+        """One W half step of a transformed model, in place on W and W_eff: the local gradient of W_eff; on one rank the
+        fused fold + MU + normalise + expand; on several the fold, the all-reduce of the M-atom buffer, apply_W and
+        expand_W."""
+        negpos_eff = self.local_gradient_W(V, W_eff, H, s, beta=beta, eps=eps)
+        if self._world == 1:
+            self.apply_W_transformed(W, W_eff, negpos_eff, transforms, eps)
+            return
+        negpos = self.fold_gradient_W(negpos_eff, transforms)
+        self._all_reduce(negpos)
+        self.apply_W(W, negpos, eps)
+        self.expand_W(W, transforms, W_eff)

@@ -20,7 +20,11 @@ to_ndarray                      _Backend.py:46-49                      backend-n
 
 Optional hooks a backend may add (the front-end uses them when present):
 ``multiplicative_update``, ``fused_update_H``, ``fused_update_W``.  A backend that declares ``supports_weights`` takes
-``initialize(..., weights=G)`` and then evaluates the weighted objective in its hooks and energy.
+``initialize(..., weights=G)`` and then evaluates the weighted objective in its hooks and energy.  A backend that
+declares ``supports_transforms`` takes ``initialize(..., transforms=name)`` (tnmf_amd/transforms.py): H then has
+``n_atoms * T`` effective atoms while W keeps ``n_atoms``, and it offers ``expand_W(W, name, W_eff=None) -> W_eff``,
+``fold_gradient_W(negpos_eff, name) -> negpos`` and ``fused_update_W_transformed(V, W, W_eff, H, s, name, eps, beta)``;
+every other hook is called with W_eff in the place of W.
 """
 import abc
 from typing import Optional, Sequence, Tuple, Union
@@ -58,15 +62,23 @@ class Backend(abc.ABC):
 
     # -- set-up -------------------------------------------------------------------------------------------
     def initialize(self, V: np.ndarray, atom_shape: Tuple[int, ...], n_atoms: int, W=None,
-                   axes_W_normalization: Axes = None, weights: Optional[np.ndarray] = None):
+                   axes_W_normalization: Axes = None, weights: Optional[np.ndarray] = None,
+                   transforms: Optional[str] = None):
         """``weights``: elementwise weights of V's shape and dtype for the weighted objective, only for a backend that
-        declares ``supports_weights`` (handed on to ``_initialize_matrices`` as the keyword ``weights``)."""
+        declares ``supports_weights`` (handed on to ``_initialize_matrices`` as the keyword ``weights``).  ``transforms``:
+        a transform group, only for a backend that declares ``supports_transforms`` (handed on as the keyword
+        ``transforms``)."""
         self._set_dimensions(V, atom_shape)
-        if weights is None:
-            return self._initialize_matrices(V, atom_shape, n_atoms, W, axes_W_normalization)
-        if not getattr(self, 'supports_weights', False):
-            raise NotImplementedError(f'the backend {type(self).__name__} does not support weighted objectives')
-        return self._initialize_matrices(V, atom_shape, n_atoms, W, axes_W_normalization, weights=weights)
+        kw = {}
+        if weights is not None:
+            if not getattr(self, 'supports_weights', False):
+                raise NotImplementedError(f'the backend {type(self).__name__} does not support weighted objectives')
+            kw['weights'] = weights
+        if transforms is not None:
+            if not getattr(self, 'supports_transforms', False):
+                raise NotImplementedError(f'the backend {type(self).__name__} does not support transform groups')
+            kw['transforms'] = transforms
+        return self._initialize_matrices(V, atom_shape, n_atoms, W, axes_W_normalization, **kw)
 
     def _set_dimensions(self, V: np.ndarray, atom_shape: Tuple[int, ...]) -> None:
         self.atom_shape = tuple(atom_shape)

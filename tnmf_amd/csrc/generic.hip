@@ -7,6 +7,7 @@
 //   corr_W      :101-119   O[n,m,u,v] = sum_c sum_{a,b} W[m,c,a,b] * X[n,c,u+a-(Ay-1),v+b-(Ax-1)]      X in {V, R}
 //   corr_H      :77-90     G[m,c,a,b] = sum_n sum_{y,x} H[n,m,y+Ay-1-a,x+Ax-1-b] * X[n,c,y,x]          X in {V, R}
 #include "generic.h"
+#include "rowsum.h"
 
 namespace {
 
@@ -536,19 +537,6 @@ __global__ void k_axpby(T *__restrict__ acc, const T *__restrict__ g, T a, T b, 
         const T t = b == T(1) ? g[i] : b * g[i];
         acc[i] = a == T(0) ? t : (a == T(1) ? acc[i] + t : a * acc[i] + t);
     }
-}
-
-template <typename T>
-__device__ double block_sum(double v, double *sh) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    double tot = 0.0;
-    const int nw = (blockDim.x + 63) >> 6;
-    for (int w = 0; w < nw; ++w) tot += sh[w];  // every thread, same order
-    return tot;
 }
 
 // W[mc, :] = (W * neg) / (pos + eps) if APPLY, then W[mc, :] /= sum.  One block per (m, c) row.
