@@ -385,6 +385,45 @@ int tnmf_hip_group_fold_grad_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int
 int tnmf_hip_group_apply_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int group, void *W_inout, void *W_eff_out,
                            const void *negpos_eff, double eps, void *stream);
 
+/* ---- atom operators: arbitrary-angle rotation and scale invariance (ABI 8, additive: the version stays 8) -------------
+ * The transform groups above widened to any T non-negative linear maps L_t of an atom's pixels, the same for every
+ * channel: W_eff[m*T + t, c] = L_t W[m, c], and the W half step folds with the transpose, neg[m, c] = sum_t
+ * L_t^T neg_eff[m*T + t, c] (pos likewise) -- before the collective, as for the groups.  Every other entry point runs the
+ * effective problem as it is.  The maps live in a handle made for one context:
+ *   tnmf_hip_atom_ops_create takes the entries (t[k], out_px[k], in_px[k], w[k]), k < nnz, of (L_t a)[out] =
+ *   sum w * a[in] -- pixels as flat C-order indices of the atom of `ndim` axes `A`, weights host doubles -- and builds two
+ *   gather tables on the device: per (t, out pixel) its taps in ascending in pixel, per in pixel its entries in ascending
+ *   (t, out pixel).  Refused before anything is allocated: volumes (ndim == 3: TNMF_E_UNSUPPORTED), other ndim, sizes
+ *   <= 0, T <= 0, nnz < 0, indices out of range and a triple (t, out, in) given twice (TNMF_E_GEOM), weights that are
+ *   not finite or negative (TNMF_E_UNSUPPORTED), NULL arrays (TNMF_E_NULL).  *out is written only on success.
+ *   tnmf_hip_atom_ops_destroy frees a handle (NULL: nothing to do); destroy the handles of a context before the context.
+ * Every output element is the sum of its products w * x in table order, in double with the multiplies and adds rounded
+ * separately, rounded once to the element type: deterministic, and for the tables of a group (weight 1, one tap, t in the
+ * group's order) the same bits as the tnmf_hip_group_* entry points.  `geom` describes the dictionary (M atoms, C, ndim,
+ * A; N and D are not read); an ndim or A other than the handle's answers TNMF_E_GEOM, a handle of another context and
+ * volumes TNMF_E_UNSUPPORTED, a NULL pointer TNMF_E_NULL, all before anything is written.  Every entry that writes W_eff
+ * drops the FFT family's cached spectra of the dictionary.  tnmf_hip_run_schedule has no operator form. */
+typedef struct tnmf_hip_atom_ops tnmf_hip_atom_ops;
+
+int tnmf_hip_atom_ops_create(tnmf_hip_ctx *ctx, int ndim, const int *A, int T, int nnz, const int *t,
+                             const int *out_px, const int *in_px, const double *w, tnmf_hip_atom_ops **out);
+int tnmf_hip_atom_ops_destroy(tnmf_hip_atom_ops *ops);
+
+/* W_eff[M*T,C,*A] = the expansion of W[M,C,*A]. */
+int tnmf_hip_ops_expand_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const tnmf_hip_atom_ops *ops, const void *W,
+                          void *W_eff, void *stream);
+
+/* negpos[2,M,C,*A] = the fold of negpos_eff[2,M*T,C,*A] (the adjoint of the expansion). */
+int tnmf_hip_ops_fold_grad_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const tnmf_hip_atom_ops *ops,
+                             const void *negpos_eff, void *negpos, void *stream);
+
+/* The single-rank W step after the gradient of W_eff, in one launch of one workgroup per (m, c) row: fold, W = W * neg /
+ * (pos + eps), W /= its sum over the atom axes (the reduction of tnmf_hip_apply_W), W_eff = the expansion of the new W
+ * (the row staged in LDS: rows of more than 64 KiB answer TNMF_E_GEOM).  Same bits as tnmf_hip_ops_fold_grad_W,
+ * tnmf_hip_apply_W and tnmf_hip_ops_expand_W in a row; negpos_eff is only read. */
+int tnmf_hip_ops_apply_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const tnmf_hip_atom_ops *ops, void *W_inout,
+                         void *W_eff_out, const void *negpos_eff, double eps, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,14 +123,19 @@ class TransformInvariantNMF:
                  ``[M, T, C, *A]``.  The effective atoms are atoms for everything on the H side (sparsity, lateral and
                  cross-atom inhibition over all M * T of them); the W step folds their gradient back onto W.  A transformed
                  fit runs on the backend's hooks step by step, like beta != 2.  Not for volumes.
+                 Or an ``AtomOperators`` on atoms of ``atom_shape`` (tnmf_amd/transforms.py: ``rotations(A, n)`` by any
+                 angle, ``scales(A, factors)``, ``compose(outer, inner)``, ``from_dense(L)``, ``from_group(name, A)``):
+                 T non-negative linear maps ``L_t``, ``W_eff[m * T + t, c] = L_t W[m, c]``, everything above with
+                 T = ``ops.T`` and the W gradient folded with the transposes; the backend must declare
+                 ``supports_atom_operators``.
     **kwargs : forwarded to the backend constructor (``reconstruction_mode``, ``device``, ``path``, ``init``,
                ``process_group``)
     """
 
     def __init__(self, n_atoms: int, atom_shape: Tuple[int, ...], inhibition_range: Union[int, Tuple[int, ...]] = None,
                  backend: Union[str, Backend] = 'hip', logger: logging.Logger = None, verbose: int = 0,
-                 use_fused_updates: bool = True, beta_loss: Union[str, float] = 2., transforms: Optional[str] = None,
-                 **kwargs):
+                 use_fused_updates: bool = True, beta_loss: Union[str, float] = 2.,
+                 transforms: Union[None, str, _transforms.AtomOperators] = None, **kwargs):
         self._beta = beta_loss_value(beta_loss)
         self.atom_shape = tuple(atom_shape)
         self.n_atoms = n_atoms
@@ -163,6 +168,10 @@ class TransformInvariantNMF:
         if self._transforms is not None and not getattr(self._backend, 'supports_transforms', False):
             raise NotImplementedError(f'transforms={transforms!r}: the backend {type(self._backend).__name__} does not '
                                       f'support transform groups')
+        if (isinstance(self._transforms, _transforms.AtomOperators)
+                and not getattr(self._backend, 'supports_atom_operators', False)):
+            raise NotImplementedError(f'transforms={transforms!r}: the backend {type(self._backend).__name__} does not '
+                                      f'support atom operators')
 
         self._logger = logger if logger is not None else logging.getLogger(self.__class__.__name__)
         self._logger.setLevel([logging.ERROR, logging.WARNING, logging.INFO, logging.DEBUG][verbose])
@@ -191,8 +200,8 @@ class TransformInvariantNMF:
         return H
 
     @property
-    def transforms(self) -> Optional[str]:
-        """The transform group (None: shifts only)."""
+    def transforms(self) -> Union[None, str, _transforms.AtomOperators]:
+        """The transform group or the atom operators (None: shifts only)."""
         return self._transforms
 
     @property

@@ -27,6 +27,8 @@ EXPORTS = (
     'tnmf_hip_beta_fields', 'tnmf_hip_update_H_beta', 'tnmf_hip_grad_W_beta', 'tnmf_hip_energy_beta',
     'tnmf_hip_weighted_fields', 'tnmf_hip_update_H_weighted', 'tnmf_hip_grad_W_weighted', 'tnmf_hip_energy_weighted',
     'tnmf_hip_group_expand_W', 'tnmf_hip_group_fold_grad_W', 'tnmf_hip_group_apply_W',
+    'tnmf_hip_atom_ops_create', 'tnmf_hip_atom_ops_destroy', 'tnmf_hip_ops_expand_W', 'tnmf_hip_ops_fold_grad_W',
+    'tnmf_hip_ops_apply_W',
 )
 
 MODES = {'valid': 0, 'full': 1, 'circular': 2, 'reflect': 3}
@@ -128,6 +130,12 @@ def load() -> ctypes.CDLL:
     lib.tnmf_hip_group_expand_W.argtypes = [vp, gp, ci, vp, vp, vp]
     lib.tnmf_hip_group_fold_grad_W.argtypes = [vp, gp, ci, vp, vp, vp]
     lib.tnmf_hip_group_apply_W.argtypes = [vp, gp, ci, vp, vp, vp, cd, vp]
+    pi = ctypes.POINTER(ci)
+    lib.tnmf_hip_atom_ops_create.argtypes = [vp, ci, pi, ci, ci, pi, pi, pi, ctypes.POINTER(cd), ctypes.POINTER(vp)]
+    lib.tnmf_hip_atom_ops_destroy.argtypes = [vp]
+    lib.tnmf_hip_ops_expand_W.argtypes = [vp, gp, vp, vp, vp, vp]
+    lib.tnmf_hip_ops_fold_grad_W.argtypes = [vp, gp, vp, vp, vp, vp]
+    lib.tnmf_hip_ops_apply_W.argtypes = [vp, gp, vp, vp, vp, vp, cd, vp]
     lib.tnmf_hip_pad_H.argtypes = [vp, gp, ci, vp, vp, vp]
     lib.tnmf_hip_fold_H.argtypes = [vp, gp, ci, vp, vp, vp]
     for name in EXPORTS:

@@ -114,6 +114,7 @@ class HIP_Backend(Backend):
         self._counts = None         # samples per rank (sharded_input: as handed in; else sharding.shard_bounds)
         self._counts_pending = None
         self._ctx = ctypes.c_void_p()
+        self._ops_handles = {}      # AtomOperators.key -> (operators, library handle on self._ctx)
         _lib.check(self._lib.tnmf_hip_ctx_create(self._device.index, ctypes.byref(self._ctx)), 'tnmf_hip_ctx_create')
         _lib.check(self._lib.tnmf_hip_ctx_set_path(self._ctx, _lib.PATHS[path]), 'tnmf_hip_ctx_set_path')
         _lib.check(self._lib.tnmf_hip_ctx_set_split(self._ctx, 1 if split else 0), 'tnmf_hip_ctx_set_split')
@@ -148,6 +149,9 @@ class HIP_Backend(Backend):
 
     def __del__(self):
         try:
+            for _, handle in getattr(self, '_ops_handles', {}).values():
+                self._lib.tnmf_hip_atom_ops_destroy(handle)
+            self._ops_handles = {}
             if getattr(self, '_ctx', None) is not None and self._ctx.value:
                 self._lib.tnmf_hip_ctx_destroy(self._ctx)
                 self._ctx = ctypes.c_void_p()
@@ -332,10 +336,42 @@ class HIP_Backend(Backend):
     # (include/tnmf_hip.h, "transform groups").  Volumes are not covered.
     supports_transforms = True
 
+    # atom operators (initialize(..., transforms=AtomOperators)): the same hooks with arbitrary non-negative linear maps of
+    # the atoms (include/tnmf_hip.h, "atom operators").  One library handle per operator set and context, made at first
+    # use, reused across steps and fits, freed with the context.
+    supports_atom_operators = True
+
     def _group_id(self, transforms: str) -> int:
         if len(self.atom_shape) == 3:
             raise NotImplementedError('transforms: 1 or 2 shift axes only')
         return _lib.GROUPS[_transforms.check(transforms, self.atom_shape)]
+
+    def _ops_handle(self, ops) -> ctypes.c_void_p:
+        """The library handle of the operators ``ops`` on this context (made at first use)."""
+        if len(self.atom_shape) == 3:
+            raise NotImplementedError('transforms: 1 or 2 shift axes only')
+        _transforms.check(ops, self.atom_shape)
+        entry = self._ops_handles.get(ops.key)
+        if entry is None:
+            t, out_px, in_px, w = ops.entries
+            ci = ctypes.c_int
+            arr = [np.ascontiguousarray(a, dtype=np.int32) for a in (t, out_px, in_px)]
+            wd = np.ascontiguousarray(w, dtype=np.float64)
+            A = (ci * len(ops.atom_shape))(*ops.atom_shape)
+            handle = ctypes.c_void_p()
+            _lib.check(self._lib.tnmf_hip_atom_ops_create(
+                self._ctx, len(ops.atom_shape), A, ops.T, ops.nnz,
+                *[a.ctypes.data_as(ctypes.POINTER(ci)) for a in arr],
+                wd.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(handle)), 'tnmf_hip_atom_ops_create')
+            entry = self._ops_handles[ops.key] = (ops, handle)
+        return entry[1]
+
+    def _transform_arg(self, transforms):
+        """-> (entry point family, its argument): ('group', TNMF_GROUP_*) for a group name, ('ops', handle) for an
+        AtomOperators."""
+        if isinstance(transforms, _transforms.AtomOperators):
+            return 'ops', self._ops_handle(transforms)
+        return 'group', self._group_id(transforms)
 
     def _G(self, ls: slice):
         return None if self._G_dev is None else _ptr(self._G_dev[ls])
@@ -419,11 +455,11 @@ class HIP_Backend(Backend):
         return self._counts_pending
 
     def _initialize_matrices(self, V: np.ndarray, atom_shape, n_atoms: int, W=None, axes_W_normalization=None,
-                             weights: Optional[np.ndarray] = None, transforms: Optional[str] = None):
-        """With ``transforms``: H (and everything sized by it) has n_atoms * T effective atoms, W has n_atoms; H is drawn
-        first, then W, as without."""
+                             weights: Optional[np.ndarray] = None, transforms=None):
+        """With ``transforms`` (a group name or an AtomOperators): H (and everything sized by it) has n_atoms * T
+        effective atoms, W has n_atoms; H is drawn first, then W, as without."""
         if transforms is not None:
-            self._group_id(transforms)
+            self._transform_arg(transforms)
         n_dict = n_atoms
         n_atoms = n_atoms * (1 if transforms is None else _transforms.size(transforms))
         if V.dtype not in _DTYPES:
@@ -798,11 +834,12 @@ class HIP_Backend(Backend):
         self._all_reduce(negpos)
         self.apply_W(W, negpos, eps)
 
-    # -- transform groups ---------------------------------------------------------------------------------------------
-    def expand_W(self, W: torch.Tensor, transforms: str, W_eff: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """W_eff[m * T + t] = T_t(W[m]) -> tnmf_hip_group_expand_W (into W_eff when given; it drops the cached spectra of
-        the dictionary)."""
-        group = self._group_id(transforms)
+    # -- transform groups and atom operators --------------------------------------------------------------------------
+    # (transforms: a group name -> tnmf_hip_group_*, or an AtomOperators -> tnmf_hip_ops_* with this context's handle)
+    def expand_W(self, W: torch.Tensor, transforms, W_eff: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """W_eff[m * T + t] = T_t(W[m]) -> tnmf_hip_group_expand_W / tnmf_hip_ops_expand_W (into W_eff when given; it drops
+        the cached spectra of the dictionary)."""
+        kind, arg = self._transform_arg(transforms)
         self._check_W(W)
         shape = (W.shape[0] * _transforms.size(transforms),) + tuple(W.shape[1:])
         if W_eff is None:
@@ -810,30 +847,33 @@ class HIP_Backend(Backend):
         self._check_W(W_eff)
         assert tuple(W_eff.shape) == shape
         g = self._geom(0, W.shape[0])
-        with self._timed('group_expand_W'):
-            _lib.check(self._lib.tnmf_hip_group_expand_W(self._ctx, ctypes.byref(g), group, _ptr(W), _ptr(W_eff),
-                                                         self._stream()), 'tnmf_hip_group_expand_W')
+        name = f'tnmf_hip_{kind}_expand_W'
+        with self._timed(f'{kind}_expand_W'):
+            _lib.check(getattr(self._lib, name)(self._ctx, ctypes.byref(g), arg, _ptr(W), _ptr(W_eff), self._stream()),
+                       name)
         return W_eff
 
-    def fold_gradient_W(self, negpos_eff: torch.Tensor, transforms: str) -> torch.Tensor:
-        """[neg | pos] of W_eff ([2, M * T, C, *A]) -> [neg | pos] of W ([2, M, C, *A]) -> tnmf_hip_group_fold_grad_W."""
-        group = self._group_id(transforms)
+    def fold_gradient_W(self, negpos_eff: torch.Tensor, transforms) -> torch.Tensor:
+        """[neg | pos] of W_eff ([2, M * T, C, *A]) -> [neg | pos] of W ([2, M, C, *A]) -> tnmf_hip_group_fold_grad_W /
+        tnmf_hip_ops_fold_grad_W."""
+        kind, arg = self._transform_arg(transforms)
         T = _transforms.size(transforms)
         assert negpos_eff.is_contiguous() and negpos_eff.dtype == self._torch_dtype and negpos_eff.shape[1] % T == 0
         assert tuple(negpos_eff.shape[2:]) == (self.n_channels,) + self.atom_shape and negpos_eff.shape[0] == 2
         M = negpos_eff.shape[1] // T
         negpos = torch.empty((2, M) + tuple(negpos_eff.shape[2:]), dtype=negpos_eff.dtype, device=negpos_eff.device)
         g = self._geom(0, M)
-        with self._timed('group_fold_grad_W'):
-            _lib.check(self._lib.tnmf_hip_group_fold_grad_W(self._ctx, ctypes.byref(g), group, _ptr(negpos_eff),
-                                                            _ptr(negpos), self._stream()), 'tnmf_hip_group_fold_grad_W')
+        name = f'tnmf_hip_{kind}_fold_grad_W'
+        with self._timed(f'{kind}_fold_grad_W'):
+            _lib.check(getattr(self._lib, name)(self._ctx, ctypes.byref(g), arg, _ptr(negpos_eff), _ptr(negpos),
+                                                self._stream()), name)
         return negpos
 
-    def apply_W_transformed(self, W: torch.Tensor, W_eff: torch.Tensor, negpos_eff: torch.Tensor, transforms: str,
+    def apply_W_transformed(self, W: torch.Tensor, W_eff: torch.Tensor, negpos_eff: torch.Tensor, transforms,
                             eps: float = 1e-9) -> None:
-        """Fold, W = W * neg / (pos + eps), normalise, expand into W_eff: one launch (tnmf_hip_group_apply_W), the same
-        bits as fold_gradient_W -> apply_W -> expand_W."""
-        group = self._group_id(transforms)
+        """Fold, W = W * neg / (pos + eps), normalise, expand into W_eff: one launch (tnmf_hip_group_apply_W /
+        tnmf_hip_ops_apply_W), the same bits as fold_gradient_W -> apply_W -> expand_W."""
+        kind, arg = self._transform_arg(transforms)
         self._check_W(W)
         self._check_W(W_eff)
         T = _transforms.size(transforms)
@@ -841,13 +881,13 @@ class HIP_Backend(Backend):
         assert negpos_eff.is_contiguous() and tuple(negpos_eff.shape) == (2,) + tuple(W_eff.shape)
         assert negpos_eff.dtype == W.dtype and negpos_eff.device == W.device
         g = self._geom(0, W.shape[0])
-        with self._timed('group_apply_W'):
-            _lib.check(self._lib.tnmf_hip_group_apply_W(self._ctx, ctypes.byref(g), group, _ptr(W), _ptr(W_eff),
-                                                        _ptr(negpos_eff), float(eps), self._stream()),
-                       'tnmf_hip_group_apply_W')
+        name = f'tnmf_hip_{kind}_apply_W'
+        with self._timed(f'{kind}_apply_W'):
+            _lib.check(getattr(self._lib, name)(self._ctx, ctypes.byref(g), arg, _ptr(W), _ptr(W_eff), _ptr(negpos_eff),
+                                                float(eps), self._stream()), name)
 
     def fused_update_W_transformed(self, V, W: torch.Tensor, W_eff: torch.Tensor, H: torch.Tensor, s: slice = sliceNone,
-                                   transforms: str = None, eps: float = 1e-9, beta: float = 2.) -> None:
+                                   transforms=None, eps: float = 1e-9, beta: float = 2.) -> None:
         """One W half step of a transformed model, in place on W and W_eff: the local gradient of W_eff; on one rank the
         fused fold + MU + normalise + expand; on several the fold, the all-reduce of the M-atom buffer, apply_W and
         expand_W."""

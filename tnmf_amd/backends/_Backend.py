@@ -24,7 +24,8 @@ Optional hooks a backend may add (the front-end uses them when present):
 declares ``supports_transforms`` takes ``initialize(..., transforms=name)`` (tnmf_amd/transforms.py): H then has
 ``n_atoms * T`` effective atoms while W keeps ``n_atoms``, and it offers ``expand_W(W, name, W_eff=None) -> W_eff``,
 ``fold_gradient_W(negpos_eff, name) -> negpos`` and ``fused_update_W_transformed(V, W, W_eff, H, s, name, eps, beta)``;
-every other hook is called with W_eff in the place of W.
+every other hook is called with W_eff in the place of W.  A backend that declares ``supports_atom_operators`` as well
+takes an ``AtomOperators`` (tnmf_amd/transforms.py) wherever those hooks take a group name.
 """
 import abc
 from typing import Optional, Sequence, Tuple, Union
@@ -51,6 +52,9 @@ def shift_shape(reconstruction_mode: str, sample_shape: Sequence[int], atom_shap
 class Backend(abc.ABC):
     """Numerical back end of :class:`tnmf_amd.TransformInvariantNMF.TransformInvariantNMF`."""
 
+    # takes an AtomOperators as ``transforms`` (with ``supports_transforms``): arbitrary non-negative linear atom maps
+    supports_atom_operators = False
+
     def __init__(self, reconstruction_mode: str = 'valid'):
         self._reconstruction_mode = reconstruction_mode
         self.atom_shape = None
@@ -66,8 +70,8 @@ class Backend(abc.ABC):
                    transforms: Optional[str] = None):
         """``weights``: elementwise weights of V's shape and dtype for the weighted objective, only for a backend that
         declares ``supports_weights`` (handed on to ``_initialize_matrices`` as the keyword ``weights``).  ``transforms``:
-        a transform group, only for a backend that declares ``supports_transforms`` (handed on as the keyword
-        ``transforms``)."""
+        a transform group, only for a backend that declares ``supports_transforms``, or an ``AtomOperators``, only for one
+        that declares ``supports_atom_operators`` as well (handed on as the keyword ``transforms``)."""
         self._set_dimensions(V, atom_shape)
         kw = {}
         if weights is not None:
@@ -77,6 +81,8 @@ class Backend(abc.ABC):
         if transforms is not None:
             if not getattr(self, 'supports_transforms', False):
                 raise NotImplementedError(f'the backend {type(self).__name__} does not support transform groups')
+            if not isinstance(transforms, str) and not getattr(self, 'supports_atom_operators', False):
+                raise NotImplementedError(f'the backend {type(self).__name__} does not support atom operators')
             kw['transforms'] = transforms
         return self._initialize_matrices(V, atom_shape, n_atoms, W, axes_W_normalization, **kw)
 
