@@ -3,8 +3,8 @@
 bench.py -- MU-iterations/sec of the shift-invariant multiplicative-update loop on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--path auto|generic|mfma|split|fft|hybrid]
-                    [--algorithm full|cyclic --batch-size B] [--no-cpu-baseline] [--no-fft-variant] [--no-parity]
-                    [--dump-outputs DIR]
+                    [--algorithm full|cyclic --batch-size B] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-fft-variant] [--no-parity] [--legs ...]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -20,17 +20,23 @@ MU-iterations/sec of the 256-sample problem and at --gpus N the iterations/sec o
 
 `python bench.py --gpus N` WITHOUT WORLD_SIZE in the environment starts the N ranks itself (a child process running
 torch.distributed.run; this process never touches the GPU) and relays rank 0's line.  At N > 1 the line also carries
+  rccl_ranks_seen, distributed   an all-reduce of one 1.0 per rank (the ranks the collective reached), backend, rank /
+                   device / pid of every rank; with --full the latency of the gradient exchange beside them
+and with --full
   strong_scaling   config 3 as ONE problem (256 global samples, 256 / N per GPU), iterations/sec of the global problem, with the
                    same problem on one GPU in the same run (rank 0 alone) and the measured speed-up / efficiency beside it
   config4_cyclic, config5_cyclic   BASELINE configs[3] / configs[4] as worded: Cyclic-MU epochs, sample-sharded (the per-GPU
                    shards 256 x 3 x 256^2 / 128 x 3 x 512^2 on every rank), ONE collective per epoch
-  rccl_ranks_seen, distributed   an all-reduce of one 1.0 per rank (the ranks the collective reached), backend, latency of the
-                   gradient exchange, rank / device / pid of every rank
 (--legs selects them; TNMF_BENCH_DIST_BACKEND=gloo lets several ranks share the GPUs of a smaller box: a rehearsal.)
 
 --algorithm cyclic: one step = one Cyclic-MU epoch (reference TransformInvariantNMF.py:457-465) over the rank's samples in
 mini-batches of --batch-size (global batch = the union of the ranks' local batches; one all-reduce per epoch) -- the
 way BASELINE.json words configs 4 and 5.  Same kernels, same work per step as a full-batch iteration.
+
+A plain run does what the headline needs and nothing more: it sets up, warms up, times the steps, writes --dump-outputs
+and prints the line.  Everything that takes runs of its own -- parity, the variant legs, cpu_baseline, the further legs and
+the exchange latency of N > 1 -- comes with --full only (after the headline leg, which is the same in both forms); the
+--no-* options then leave single parts of it out.
 
 Extra objects on the JSON line:
   roofline      the dominant single KERNEL of the step (the fused H update: one kernel per launch, the longest single kernel
@@ -47,6 +53,7 @@ Extra objects on the JSON line:
                 launch of that kernel from the committed PMC passes (profiles/rNN_traffic_config<c>.json), null if none.
                 roofline_by_kernel prices every kernel group the same way; iteration.traffic_measured sums the PMC
                 traffic of all kernels of a step.
+With --full:
   parity        the other half of BASELINE.json's metric: the same code path (same --path) run for 5 iterations from
                 the reference's seeded start (np.random.seed(42), H drawn before W) on the first `samples` samples of
                 the workload, against the float64 C oracle on the same samples: max |dW| / max |W|, max |dH| / max |H|,
@@ -338,13 +345,17 @@ def main():
     ap.add_argument('--cross-inhibition', type=float, default=0., help='cross-atom inhibition strength')
     ap.add_argument('--reduce', default='all_reduce', choices=['all_reduce', 'ordered'],
                     help="cross-rank sum of the W gradient: one RCCL all-reduce, or all-gather + fixed rank-order sum")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-fft-variant', action='store_true', help='skip the extra timed legs on the other kernel families')
-    ap.add_argument('--no-parity', action='store_true', help='skip the parity leg against the float64 oracle')
+    ap.add_argument('--full', action='store_true', help='beside the headline, run the legs that take runs of their own: '
+                    'parity, the variants on the other kernel families, the CPU baseline, and at N > 1 the further legs '
+                    'and the exchange latency')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-fft-variant', action='store_true', help='--full: skip the extra timed legs on the other kernel '
+                    'families')
+    ap.add_argument('--no-parity', action='store_true', help='--full: skip the parity leg against the float64 oracle')
     ap.add_argument('--parity-samples', type=int, default=None)
     ap.add_argument('--cpu-budget', type=float, default=20.0)
     ap.add_argument('--legs', default='strong,config4,config5',
-                    help='--gpus N > 1: further timed legs beside the weak-scaling headline, comma separated: strong '
+                    help='--full at --gpus N > 1: further timed legs beside the weak-scaling headline, comma separated: strong '
                          '(config 3, 256 GLOBAL samples, 256 / N per GPU), config4 / config5 (Cyclic-MU epochs on the '
                          'per-GPU shards of BASELINE configs[3] / configs[4], one collective per epoch); "none" skips them')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
@@ -551,35 +562,39 @@ def main():
     energy = nmf._energy_function()     # collective when sharded; outside the timed region
     last_family = be.last_path
 
-    # N > 1: evidence that the collective saw every rank, the latency of the one exchange step, and the further legs the
-    # north star words (strong scaling of config 3; configs 4 and 5 as sample-sharded Cyclic-MU) -- all measured here,
-    # none estimated.  Outside the headline's timed region.
+    # N > 1: evidence that the collective saw every rank; with --full the latency of the one exchange step and the further
+    # legs the north star words (strong scaling of config 3; configs 4 and 5 as sample-sharded Cyclic-MU) -- all measured
+    # here, none estimated.  Outside the headline's timed region.
     dist_info, scaling_legs = None, {}
     if group is not None:
         ones = torch.ones(1, dtype=torch.float32, device=device)
         dist.all_reduce(ones)           # every rank contributes 1: the sum is the number of ranks the collective reached
-        buf = torch.zeros(2 * cfg['M'] * cfg['C'] * int(np.prod(cfg['A'])), dtype=torch.float32, device=device)
-        for _ in range(5):
-            be._all_reduce(buf)
-        torch.cuda.synchronize(device)
-        t0 = time.perf_counter()
-        for _ in range(50):
-            be._all_reduce(buf)
-        torch.cuda.synchronize(device)
-        exch_us = (time.perf_counter() - t0) / 50 * 1e6
         who = [None] * world
         dist.all_gather_object(who, {'rank': rank, 'device': dev_index, 'name': torch.cuda.get_device_name(dev_index),
                                      'pid': os.getpid()})
         dist_info = {'backend': dist.get_backend(), 'is_rccl': dist.get_backend() == 'nccl',
                      'rccl_ranks_seen': int(round(float(ones.item()))), 'world_size': world, 'reduce': args.reduce,
                      'what': 'all-reduce (sum) of one 1.0 per rank over the process group the W gradient uses',
-                     'exchange_bytes': buf.numel() * 4, 'exchange_us_avg_of_50': exch_us, 'ranks': who}
-        del buf, ones
+                     'ranks': who}
+        if args.full:
+            buf = torch.zeros(2 * cfg['M'] * cfg['C'] * int(np.prod(cfg['A'])), dtype=torch.float32, device=device)
+            for _ in range(5):
+                be._all_reduce(buf)
+            torch.cuda.synchronize(device)
+            t0 = time.perf_counter()
+            for _ in range(50):
+                be._all_reduce(buf)
+            torch.cuda.synchronize(device)
+            dist_info['exchange_bytes'] = buf.numel() * 4
+            dist_info['exchange_us_avg_of_50'] = (time.perf_counter() - t0) / 50 * 1e6
+            del buf
+        del ones
         del nmf, be
         nmf = be = None
         torch.cuda.empty_cache()
         from tnmf_amd import sharding
-        want = [] if args.legs in ('', 'none') or args.algorithm != 'full' else [x.strip() for x in args.legs.split(',')]
+        want = ([] if not args.full or args.legs in ('', 'none') or args.algorithm != 'full' else
+                [x.strip() for x in args.legs.split(',')])
         ls = args.leg_steps or min(args.steps, 20)
 
         def leg_kernels(sp, pth):
@@ -663,14 +678,15 @@ def main():
             if leg in want:
                 guarded(leg + '_cyclic', lambda cid=cid, local_batch=local_batch: leg_cyclic(cid, local_batch))
 
-    # Further legs (single GPU only): the same iterations from the same start on the other kernel families -- the
+    # Further legs (--full, single GPU only): the same iterations from the same start on the other kernel families -- the
     # direct-vs-FFT crossover of BASELINE.json configs[4].
     variants = {}
     fams = set(paths.values())
     main_family = ('hybrid' if 'fft' in fams and (fams & {'mfma', 'split', 'generic'}) else last_family)
     if 'split' in fams:
         main_family += '+split' if main_family != 'split' else ''
-    if world == 1 and group is None and not args.no_fft_variant and k == 2:   # (with a process group the main model is gone)
+    # (with a process group the main model is gone)
+    if args.full and world == 1 and group is None and not args.no_fft_variant and k == 2:
         W_main = nmf.W
         legs = [('mfma', 'direct_variant', True), ('fft', 'fft_variant', True)]
         if 'split' in fams:
@@ -698,9 +714,9 @@ def main():
             del m2
             torch.cuda.empty_cache()
 
-    # parity leg: the other half of BASELINE.json's metric (outside the timed region, rank 0, single GPU)
+    # parity leg (--full): the other half of BASELINE.json's metric (outside the timed region, rank 0, single GPU)
     parity = None
-    if world == 1 and not args.no_parity:
+    if args.full and world == 1 and not args.no_parity:
         from oracle import tnmf_oracle as orc
         # ~3.2 thread-seconds per config-3 sample and iteration for the float64 C oracle: keep the leg near 10-20 s
         rel_cost = conv_flops(cfg, 1) / conv_flops(CONFIGS[3], 1)
@@ -780,8 +796,8 @@ def main():
                 'kernel_families': paths, 'algorithm': args.algorithm, 'inhibition': args.inhibition,
                 'cross_inhibition': args.cross_inhibition,
                 'batch_size': batch_size if args.algorithm != 'full' else None,
-                'h_update_arithmetic': ('3 x bf16 operand splits on the bf16 matrix cores (float32-grade; parity '
-                                        'object and exact_f32_variant beside it)' if 'split' in fams else
+                'h_update_arithmetic': ('3 x bf16 operand splits on the bf16 matrix cores (float32-grade; with '
+                                        '--full the parity object and exact_f32_variant beside it)' if 'split' in fams else
                                         'exact f32' if paths.get('update_H') in ('mfma', 'generic') else 'fft'),
                 'parallelism': (f'sample-sharded x{world}, ' + ('all-reduce' if args.reduce == 'all_reduce' else
                                 'all-gather + rank-order sum') + ' of W num/den per step') if world > 1 else 'single GPU',
@@ -815,7 +831,7 @@ def main():
             line['parity'] = parity
             line['energy_gap_vs_oracle'] = parity['energy_gap_vs_oracle']
             line['W_rel_diff_vs_oracle'] = parity['W_rel_diff_vs_oracle']
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(cfg, args.cpu_budget)
             line['cpu_baseline']['gpu_over_cpu'] = line['value'] / line['cpu_baseline']['value']
             line['cpu_baseline']['fft_variant']['gpu_over_cpu'] = line['value'] / line['cpu_baseline']['fft_variant']['value']

@@ -564,16 +564,18 @@ def test_bench_two_rank_path_rehearsal(tmp_path):
 
 
 def test_bench_line_contract():
-    """The one JSON line of `python bench.py` (here on BASELINE config 2, a few steps, a two-second CPU leg): the keys the
-    driver reads, the roofline object of the dominant kernel (algorithmic work / measured launch time against the peak, PMC
-    traffic from the committed profile with its staleness stamp) and the CPU baseline timed on this box's host cores."""
+    """The one JSON line of `python bench.py --full` (here on BASELINE config 2, a few steps, a two-second CPU leg): the keys
+    the driver reads, the roofline object of the dominant kernel (algorithmic work / measured launch time against the peak,
+    PMC traffic from the committed profile with its staleness stamp), the CPU baseline timed on the host's cores and the
+    parity leg against the oracle."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--config', '2', '--steps', '4', '--warmup', '1',
-                          '--cpu-budget', '2', '--no-fft-variant'], env=env, capture_output=True, text=True, timeout=600, cwd=root)
+                          '--full', '--cpu-budget', '2', '--no-fft-variant'], env=env, capture_output=True, text=True, timeout=600,
+                         cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith('{')]
     assert len(lines) == 1
@@ -594,6 +596,27 @@ def test_bench_line_contract():
     assert c['kind'] == 'port' and c['cores'] == os.cpu_count() and c['value'] > 0 and 'samples' in c['sample']
     p = d['parity']
     assert p['W_rel_diff_vs_oracle'] < 1e-5 and p['H_rel_diff_vs_oracle'] < 1e-5 and p['energy_gap_vs_oracle'] < 1e-5
+
+
+def test_plain_bench_line_is_lean():
+    """`python bench.py` without --full runs the headline leg alone: the line has the headline keys and the roofline of
+    the timed steps, and none of the objects that take runs of their own (parity, variant legs, CPU baseline)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--config', '2', '--steps', '4', '--warmup', '1'],
+                         env=env, capture_output=True, text=True, timeout=300, cwd=root)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'roofline', 'kernels'):
+        assert key in d, key
+    assert d['steps'] == 4 and d['warmup'] == 1 and abs(d['value'] - 1e3 / d['ms_per_step']) < 1e-6 * d['value']
+    for key in ('parity', 'energy_gap_vs_oracle', 'cpu_baseline', 'exact_f32_variant', 'direct_variant', 'fft_variant'):
+        assert key not in d, key
 
 
 def test_bench_dump_outputs(tmp_path):
@@ -633,8 +656,9 @@ def test_bench_launches_its_own_ranks(tmp_path):
     bench.py starts the two ranks itself as CHILD processes (torch.distributed.run) before it touches the GPU and relays
     rank 0's line; the line carries the weak-scaling headline, the strong-scaling leg of the same configuration (global
     sample count fixed, half per rank, with the one-GPU run of the same problem beside it), the Cyclic-MU legs on the shards
-    of configs 4 and 5 (one collective per epoch), and the number of ranks the collective reached.  Two ranks share the one
-    GPU of the test box, so the collective is gloo (TNMF_BENCH_DIST_BACKEND) and no number here is a measurement."""
+    of configs 4 and 5 (one collective per epoch; these with --full), and the number of ranks the collective reached.  Two
+    ranks share the one GPU of the test box, so the collective is gloo (TNMF_BENCH_DIST_BACKEND) and no number here is a
+    measurement."""
     import json
     import subprocess
     import sys
@@ -642,7 +666,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     env['TNMF_BENCH_DIST_BACKEND'] = 'gloo'
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--config', '2',
-           '--samples', '8']
+           '--samples', '8', '--full']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith('{')]

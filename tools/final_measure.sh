@@ -13,10 +13,10 @@ cd $R
 python3 -c "import bench; print(bench.csrc_digest())" > $out/sources.sha16 || exit 1   # what these profiles are measured on
 Q="--no-cpu-baseline --no-fft-variant --no-parity"
 if [ "$3" != "nobench" ]; then
-  timeout -k 10 500 python3 bench.py > $out/bench_n1.json 2> $out/bench_n1.err || { echo "bench failed"; tail -3 $out/bench_n1.err; exit 1; }
+  timeout -k 10 500 python3 bench.py --full > $out/bench_n1.json 2> $out/bench_n1.err || { echo "bench failed"; tail -3 $out/bench_n1.err; exit 1; }
   echo "bench n1 done"
   for c in 2 4 5; do
-    timeout -k 10 400 python3 bench.py --config $c --no-cpu-baseline --steps 8 --warmup 2 > $out/bench_config$c.json 2> $out/bench_config$c.err || { echo "bench $c failed"; exit 1; }
+    timeout -k 10 400 python3 bench.py --config $c --full --no-cpu-baseline --steps 8 --warmup 2 > $out/bench_config$c.json 2> $out/bench_config$c.err || { echo "bench $c failed"; exit 1; }
     echo "bench config $c done"
   done
   timeout -k 10 300 python3 bench.py --config 4 $Q --steps 8 --warmup 2 --algorithm cyclic --batch-size 64 > $out/bench_config4_cyclic.json 2> $out/b.err || exit 1
