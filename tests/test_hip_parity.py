@@ -355,13 +355,17 @@ ADVERSARIAL_GEOMETRIES = {
     'a16_c3': (2, 3, (40, 72), 40, (16, 16), 'mfma', 0.),          # eight-wave <16,4> workgroups, W image restaged per channel, partial atom tile
     'a64_1d': (12, 2, (300,), 20, (64,), 'generic', 0.),           # 1-D instantiation <1,16>: tile rows = samples, partial sample block
     'a12_extra': (2, 1, (48, 56), 32, (12, 12), 'mfma', 0.1),      # EXTRA-term epilogue: lateral inhibition in the fused kernel's denominator
+    'a16_extra': (2, 1, (40, 72), 40, (16, 16), 'mfma', 0.1),      # EXTRA epilogue on the 16x16x32 form (one channel: lane_atom / q_atoms)
+    'a15x13_extra': (2, 1, (44, 70), 33, (15, 13), 'mfma', 0.1),   # the same on atoms the <16,4> instantiation pads
 }
 
 
 def _adversarial_case(kind, geometry='a12_c1'):
     """Operands the uniform-random cases never produce (parity is thin on dynamic range; r3: ... and on the
-    instantiations beyond 12 x 12 single-channel atoms)."""
-    N, C, D, M, A = ADVERSARIAL_GEOMETRIES[geometry][:5]
+    instantiations beyond 12 x 12 single-channel atoms).  geometry: a key of ADVERSARIAL_GEOMETRIES or (N, C, D, M, A)."""
+    if isinstance(geometry, str):
+        geometry = ADVERSARIAL_GEOMETRIES[geometry]
+    N, C, D, M, A = geometry[:5]
     k = len(A)
     axes = tuple(range(-k, 0))
     rng = np.random.default_rng(97)
