@@ -501,7 +501,7 @@ def test_non_finite_samples_propagate_on_both_h_update_kernels():
 # FFT kernel family (path='fft'): the frequency-domain formulation must give the same numbers as the direct one
 # ---------------------------------------------------------------------------------------------------------------
 FFT_SHAPES = [
-    # N, C, D, M, A, dtypes      transform lengths (y, x)
+    # N, C, D, M, A, dtypes      transform lengths (y, x), as tests/fft_dispatch.py computes them (test_fft_dispatch_cpu.py)
     (3, 1, (37, 45), 16, (9, 9), 'df'),        # 48, 64
     (2, 3, (33, 31), 7, (5, 8), 'df'),         # 48, 48
     (2, 2, (20, 70), 33, (16, 16), 'df'),      # 48, 96
@@ -511,8 +511,8 @@ FFT_SHAPES = [
     (2, 1, (40, 50), 4, (20, 6), 'df'),        # 64, 64; atoms taller than the mixed contractions take (16 rows)
     (2, 1, (128, 128), 16, (9, 9), 'df'),      # 144, 144
     (2, 3, (100, 170), 8, (12, 12), 'df'),     # 144, 192
-    (1, 3, (256, 200), 8, (12, 12), 'df'),     # 288, 288
-    (1, 1, (300, 500), 4, (16, 16), 'f'),      # 384, 576
+    (1, 3, (256, 200), 8, (12, 12), 'df'),     # 270, 270
+    (1, 1, (300, 500), 4, (16, 16), 'f'),      # 384, 540
 ]
 
 
@@ -595,7 +595,7 @@ HYBRID_SHAPES = [
     # N, C, D, M, A -- ragged against every tile size of the row, mixed and column kernels
     (3, 1, (130, 301), 5, (7, 10)),       # transform lengths 144 x 384, one channel: mixed contractions
     (2, 2, (77, 45), 9, (16, 3)),         # 96 x 48, two channels: column-transform contractions
-    (5, 1, (33, 500), 3, (1, 16)),        # atoms one row tall, long rows (576)
+    (5, 1, (33, 500), 3, (1, 16)),        # atoms one row tall, long rows (48 x 540)
     (1, 3, (260, 40), 40, (13, 9)),       # 288 x 48, three channels, more atoms than one tile
     (7, 1, (20, 20), 33, (5, 5)),         # tiny planes, many of them
     (2, 1, (40, 50), 4, (20, 6)),         # atoms taller than 16 rows: column-transform contractions with one channel
