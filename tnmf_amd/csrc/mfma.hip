@@ -1133,6 +1133,7 @@ static bool mfma_common(const Geo &g, int dtype) {
 
 bool mfma_has_reconstruct(const Geo &g, int dtype) {
     if (!mfma_common(g, dtype)) return false;
+    if (g.Hx < 4) return false;        // prefetch() loads 16 bytes from min(x, Hx - 4): a narrower row would start before it
     return g.Ay >= 3 && g.Ay <= 16;   // rows of the 16x16 tile = atom rows (utilisation Ay/16)
 }
 
