@@ -192,7 +192,9 @@ int tnmf_hip_convolve_axis(tnmf_hip_ctx *ctx, int dtype, size_t rows, int len, s
  * tnmf/backends/_PyTorchBackend.py:42-52, applied in tnmf/backends/PyTorch.py:36-43): 'full' pads A-1 zeros on both
  * sides, 'circular' / 'reflect' pad A-1 wrapped / mirrored elements on the left.  The activation tensor of mode `mode`
  * has shift shape S = D-A+1 ('full') or D ('circular', 'reflect'); the padded one always has D+A-1, which is what all
- * the primitives above take.  The H gradient of a mode is the 'valid' gradient folded back by the adjoint of the pad. */
+ * the primitives above take.  The H gradient of a mode is the 'valid' gradient folded back by the adjoint of the pad.
+ * TNMF_E_GEOM per shift axis: S < 1; 'circular' with A-1 > S (more than one wrap); 'reflect' with A-1 >= S (a mirror
+ * without the edge).  'full' has no further limit: an atom may be as long as the sample. */
 enum { TNMF_MODE_VALID = 0, TNMF_MODE_FULL = 1, TNMF_MODE_CIRCULAR = 2, TNMF_MODE_REFLECT = 3 };
 
 /* Hpad[N,M,*(D+A-1)] = pad(H[N,M,*S]) */

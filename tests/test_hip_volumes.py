@@ -181,3 +181,32 @@ def test_volume_half_steps_run_inside_the_library():
     np.testing.assert_allclose(nmf.H, ref.H, rtol=1e-9, atol=1e-12)
     np.testing.assert_allclose(nmf.W, ref.W, rtol=1e-9, atol=1e-12)
 
+
+
+@pytest.mark.parametrize('dtype,tol', [(np.float64, 1e-10), (np.float32, 2e-5)], ids=['f64', 'f32'])
+def test_volume_full_mode_with_atoms_longer_than_the_activations(dtype, tol):
+    """'full' pads zeros (F.pad mode='constant', _PyTorchBackend.py:42-52): an atom may be as long as the sample, however
+    few activations that leaves -- here 8 of 10 voxels along z (3 activations behind a pad of 7) and the whole of y (one
+    activation).  The wrap guard belongs to 'circular', the mirror guard to 'reflect'."""
+    N, C, D, M, A = 2, 1, (10, 4, 9), 3, (8, 4, 3)
+    rng = np.random.default_rng(11)
+    f32 = lambda x: np.asarray(x, dtype=np.float32).astype(np.float64)  # noqa: E731
+    V, Wn = f32(rng.random((N, C) + D)), rng.random((M, C) + A)
+    Wn = f32(Wn / Wn.sum(axis=(-3, -2, -1), keepdims=True))
+    Hn = f32(rng.random((N, M) + orc.transform_shape(D, A, 'full')))
+    assert Hn.shape[2:] == (3, 1, 7)
+    be = HIP_Backend(reconstruction_mode='full')
+    np.random.seed(1)
+    be.initialize(V.astype(dtype), A, M, None, (-3, -2, -1))
+    W, H = dev(Wn, dtype), dev(Hn, dtype)
+    assert relmax(be.to_ndarray(be.reconstruct(W, H)), orc.reconstruct(Wn, Hn, mode='full')) < tol
+    on, op = orc.gradient_H(V, Wn, Hn, mode='full')
+    neg, pos = be.reconstruction_gradient_H(V, W, H)
+    assert tuple(neg.shape) == on.shape
+    assert relmax(be.to_ndarray(neg), on) < tol and relmax(be.to_ndarray(pos), op) < tol
+    ref = orc.OracleNMF(n_atoms=M, atom_shape=A, reconstruction_mode='full')
+    ref.V, ref.W, ref.H = V, Wn, Hn.copy()
+    ref.update_H(slice(None), sparsity=0.05, inhibition=0.1, cross_inhibition=0.05)
+    be.fused_update_H(V, W, H, slice(None), sparsity=0.05, eps=1e-9, inhibition=0.1, cross_inhibition=0.05,
+                      inhibition_kernels=orc.inhibition_kernels(tuple(a - 1 for a in A)))
+    assert relmax(be.to_ndarray(H), ref.H) < 2 * tol

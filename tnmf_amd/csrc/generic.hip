@@ -1073,7 +1073,10 @@ static inline int mode_shift(int d, int a, int mode) {
 int launch_pad_fold(const tnmf_hip_ctx *ctx, const Geo &g, int dtype, int mode, bool fold, const void *in, void *out,
                     hipStream_t s) {
     const int Sy = g.Dy == 1 && g.Ay == 1 ? 1 : mode_shift(g.Dy, g.Ay, mode), Sx = mode_shift(g.Dx, g.Ax, mode);
-    if (Sy < 1 || Sx < 1 || g.Ay - 1 > Sy || g.Ax - 1 > Sx) return TNMF_E_GEOM;
+    if (Sy < 1 || Sx < 1) return TNMF_E_GEOM;
+    // 'circular' wraps at most once: a pad of A-1 needs A-1 <= S (torch's circular pad raises otherwise).  'full' pads
+    // zeros (F.pad mode='constant'): any atom up to the sample's length, however short that leaves the activations
+    if (mode == TNMF_MODE_CIRCULAR && (g.Ay - 1 > Sy || g.Ax - 1 > Sx)) return TNMF_E_GEOM;
     // 'reflect' mirrors without repeating the edge: a pad of A-1 needs A-1 < S (torch's reflect pad raises otherwise,
     // _PyTorchBackend.py:42-52 / torch.nn.functional.pad); pad == S would read one element past the activation row
     if (mode == TNMF_MODE_REFLECT && (g.Ay - 1 >= Sy || g.Ax - 1 >= Sx)) return TNMF_E_GEOM;

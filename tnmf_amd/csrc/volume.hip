@@ -325,8 +325,9 @@ int vol_pad_fold(const tnmf_hip_ctx *ctx, const Vol &v, int dtype, int mode, boo
         q.P[i] = v.H[i];
         q.S[i] = mode == TNMF_MODE_VALID ? v.H[i] : (mode == TNMF_MODE_FULL ? v.D[i] - v.A[i] + 1 : v.D[i]);
         if (q.S[i] < 1) return TNMF_E_GEOM;
-        // (the same limits as launch_pad_fold of generic.hip: at most one wrap; 'reflect' mirrors without the edge)
-        if (mode != TNMF_MODE_VALID && v.A[i] - 1 > q.S[i]) return TNMF_E_GEOM;
+        // (the same limits as launch_pad_fold of generic.hip: 'circular' wraps at most once, 'reflect' mirrors without
+        // the edge, 'full' pads zeros and has none)
+        if (mode == TNMF_MODE_CIRCULAR && v.A[i] - 1 > q.S[i]) return TNMF_E_GEOM;
         if (mode == TNMF_MODE_REFLECT && v.A[i] - 1 >= q.S[i]) return TNMF_E_GEOM;
     }
     const size_t planes = (size_t)v.N * v.M;
