@@ -354,6 +354,32 @@ int tnmf_hip_grad_W_weighted(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const
 int tnmf_hip_energy_weighted(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, double beta, double eps, const void *V,
                              const void *G, const void *W, const void *H, double *out_host, void *stream);
 
+/* ---- per-sample objective and the objective tap (ABI 8, additive: the version stays 8) -------------------------------
+ * The objective of one sample n is its share of what the energy entries above return: the sum over the sample's C * D
+ * elements of 1/2 (V - R)^2, of D_beta(V | max(R, 0) + eps), or of G times either (G <= 0 selects exactly 0).  It is
+ * summed in double by a two-stage reduction of fixed order without atomics; how a sample is cut into blocks depends on
+ * C * D alone, so a sample's value does not depend on which other samples share the call.  Every H half step
+ * materialises R = reconstruct(W, H as passed in) before it does anything else with it: the tap reads the objective off
+ * that R, which makes watching convergence cost one pass over (V, R[, G]) instead of a reconstruction of its own. */
+
+/* While per_sample_dev is not NULL, tnmf_hip_update_H, _update_H_ex, _update_H_beta and _update_H_weighted write
+ * per_sample_dev[n], n in [0, geom->N), the objective of sample n of the call at (W, H_inout as passed in) -- of the
+ * objective the entry point steps (Frobenius, D_beta, weighted), on 1, 2 or 3 shift axes, in every reconstruction mode,
+ * r_is_valid or not -- right after the reconstruction, on the call's stream, without a host copy or a synchronisation.  The
+ * step computes what it computes without the tap (the same bits in H_inout).  per_sample_dev: geom->N doubles on the device,
+ * which must stay valid until the tap is cleared; NULL clears the tap.  The partial sums live in a work buffer of the
+ * context that the first tapped call allocates (tnmf_hip_ctx_reserve does not size it).  tnmf_hip_run_schedule ignores
+ * the tap. */
+int tnmf_hip_ctx_set_objective_tap(tnmf_hip_ctx *ctx, double *per_sample_dev);
+
+/* per_sample_dev[n] = the objective of sample n at (W, H): a reconstruction of its own into the context's scratch, then
+ * the tap's kernel.  Asynchronous on the stream: no host copy, no synchronisation.  G_or_null != NULL: weighted.  The
+ * restrictions of tnmf_hip_energy_weighted: non-finite beta answers TNMF_E_UNSUPPORTED, and volumes (ndim == 3) anything
+ * but the unweighted Frobenius objective (beta == 2, G_or_null == NULL) likewise; a NULL operand or output answers
+ * TNMF_E_NULL -- all before anything is written. */
+int tnmf_hip_sample_objective(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, double beta, double eps, const void *V,
+                              const void *G_or_null, const void *W, const void *H, double *per_sample_dev, void *stream);
+
 /* ---- transform groups: rotation and mirror invariance (ABI 8, additive: the version stays 8) -------------------------
  * A dictionary W[M,C,*A] stands for M * T effective atoms W_eff[m*T + t] = T_t(W[m]), every T_t a permutation of the
  * atom's pixels.  The groups, with t in the order below (numpy, a = W[m, c]):

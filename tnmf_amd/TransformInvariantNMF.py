@@ -17,6 +17,9 @@ Differences from the reference, all deliberate:
 import enum
 import itertools
 import logging
+import math
+import numbers
+import warnings
 from typing import Callable, Iterable, Iterator, List, Optional, Tuple, Union
 
 import numpy as np
@@ -128,6 +131,16 @@ class TransformInvariantNMF:
                  T non-negative linear maps ``L_t``, ``W_eff[m * T + t, c] = L_t W[m, c]``, everything above with
                  T = ``ops.T`` and the W gradient folded with the transposes; the backend must declare
                  ``supports_atom_operators``.
+    ``fit_batch`` / ``fit_minibatches`` (and ``fit_stream`` for each of its subsample fits) take ``objective_every=k``: record
+    the objective every k iterations (epochs), i = 0, k, 2k, ...; and ``tol``: stop on its relative decrease (``tol`` alone
+    means ``objective_every=10``).  The value recorded at iteration i is the objective of the (W, H) that ENTERS iteration i
+    -- what ``objective()`` would return at that moment, so the first one is the objective of the initialisation.  It is the
+    data term only (1/2 ||V - R||^2, sum D_beta(V | R + eps), or their weighted sums; with transforms of the effective
+    problem): the sparsity and inhibition penalties are not part of it.  After the j-th record (j >= 1) the fit has
+    converged if ``E[j-1] - E[j] <= tol * E[0]`` (scikit-learn's criterion); that iteration is completed and the fit ends
+    with ``converged_ = True``.  A non-finite value ends the fit after its iteration with a RuntimeWarning.  Read-outs after
+    every fit: ``objective_history_`` ([n_records, 2]: iteration, value), ``n_iter_``, ``converged_``.  On a backend with
+    the objective tap a full-batch record costs one pass over (V, R) inside the H half step, not a reconstruction.
     **kwargs : forwarded to the backend constructor (``reconstruction_mode``, ``device``, ``path``, ``init``,
                ``process_group``)
     """
@@ -185,6 +198,10 @@ class TransformInvariantNMF:
         self._H = None
         self._V = None
         self._shuffle_idx = None
+        self.objective_history_ = np.empty((0, 2))
+        self.n_iter_ = 0
+        self.converged_ = False
+        self._objective_buf = None   # the tap's per-sample buffer of the current fit
 
     # -- read-outs (reference :188-215) ---------------------------------------------------------------------
     @property
@@ -256,6 +273,64 @@ class TransformInvariantNMF:
     def _energy_function(self) -> float:
         return self._backend.reconstruction_energy(self._V, self._W_dict, self._H, **self._objective())
 
+    def objective(self) -> float:
+        """The objective of the current (W, H): 1/2 ||V - R||^2, sum D_beta(V | R + eps), or the weighted sum of either --
+        the data term only, without the sparsity and inhibition penalties."""
+        return self._energy_function()
+
+    def sample_objective(self) -> np.ndarray:
+        """[N] float64: each sample's share of ``objective()``, in the order of ``V`` (with a process group: this rank's
+        samples, like ``H``).  Its sum is ``objective()``; for a fixed dictionary it is the anomaly score of a sample."""
+        hook = getattr(self._backend, 'sample_objective', None)
+        if hook is None:
+            raise NotImplementedError(f'the backend {type(self._backend).__name__} has no per-sample objective')
+        out = np.asarray(hook(self._V, self._W_dict, self._H, beta=self._beta, eps=self.eps), dtype=np.float64)
+        return out if self._shuffle_idx is None else out[np.argsort(self._shuffle_idx)]
+
+    # -- stopping on the objective ---------------------------------------------------------------------------------
+    @staticmethod
+    def _convergence_args(objective_every, tol) -> Tuple[Optional[int], Optional[float]]:
+        """(objective_every, tol) checked; ``tol`` alone records every 10 iterations (scikit-learn's cadence)."""
+        if tol is not None:
+            if isinstance(tol, (bool, np.bool_)) or not isinstance(tol, numbers.Real):
+                raise ValueError(f'tol must be a finite number >= 0, not {tol!r}')
+            tol = float(tol)
+            if not math.isfinite(tol) or tol < 0:
+                raise ValueError(f'tol must be a finite number >= 0, not {tol!r}')
+            if objective_every is None:
+                objective_every = 10
+        if objective_every is not None:
+            if isinstance(objective_every, (bool, np.bool_)) or not isinstance(objective_every, numbers.Integral):
+                raise ValueError(f'objective_every must be an int >= 1, not {objective_every!r}')
+            objective_every = int(objective_every)
+            if objective_every < 1:
+                raise ValueError(f'objective_every must be an int >= 1, not {objective_every!r}')
+        return objective_every, tol
+
+    def _begin_history(self) -> None:
+        self._history = []
+        self.objective_history_ = np.empty((0, 2))
+        self.n_iter_ = 0
+        self.converged_ = False
+        self._objective_buf = None
+
+    def _record(self, step: int, value: float, tol: Optional[float]) -> bool:
+        """Note the objective ``value`` of the state that entered ``step``; True when the fit ends with this step."""
+        self._history.append((step, value))
+        if not math.isfinite(value):
+            warnings.warn(f'the objective is {value} at step {step}: the fit stops', RuntimeWarning, stacklevel=3)
+            return True
+        if tol is not None and len(self._history) >= 2:
+            if self._history[-2][1] - value <= tol * self._history[0][1]:
+                self.converged_ = True
+                return True
+        return False
+
+    def _end_history(self, n_iter: int) -> None:
+        self.n_iter_ = n_iter
+        self.objective_history_ = np.asarray(self._history, dtype=np.float64).reshape(-1, 2)
+        self._objective_buf = None
+
     # -- elementwise multiplicative update (reference :217-238) ----------------------------------------------
     def _multiplicative_update(self, arr, neg, pos, sparsity: float = 0., normalization_axes=None):
         assert sparsity >= 0
@@ -293,15 +368,24 @@ class TransformInvariantNMF:
         assert neg.shape == self._W.shape and pos.shape == self._W.shape
         self._multiplicative_update(self._W, neg, pos, normalization_axes=self._axes_W_normalization)
 
-    def _update_H(self, s: slice = sliceNone, sparsity: float = 0., inhibition: float = 0., cross_inhibition: float = 0.):
+    def _update_H(self, s: slice = sliceNone, sparsity: float = 0., inhibition: float = 0., cross_inhibition: float = 0.,
+                  record: bool = False) -> Optional[float]:
+        """record: this step is to yield the objective of the state it starts from.  Returns None when the backend's H half
+        step taps it (into self._objective_buf, read later), else its value, evaluated before anything is written."""
         lateral = inhibition > 0 or cross_inhibition > 0
         fused = self._step_hook('fused_update_H')
+        tap = record and fused is not None and getattr(self._backend, 'supports_objective_tap', False)
+        value = self._energy_function() if record and not tap else None
         if fused is not None:
             kw = dict(inhibition=inhibition, cross_inhibition=cross_inhibition,
                       inhibition_kernels=self._inhibition_kernels_1D) if lateral else {}
+            if tap:   # (the keyword is passed only when the step records)
+                if self._objective_buf is None:
+                    self._objective_buf = self._backend.new_objective_buffer()
+                kw['objective_out'] = self._objective_buf
             try:
                 fused(self._V, self._W_dict, self._H, s, sparsity=sparsity, **self._objective(eps=self.eps, **kw))
-                return
+                return value
             except NotImplementedError:
                 # (inhibition kernels longer than the backend's fused kernel takes; lateral terms or reconstruction modes
                 # of volumes: nothing has been written, the reference's own lines below do the step -- for the plain
@@ -309,6 +393,8 @@ class TransformInvariantNMF:
                 # raises)
                 if not self._plain_frobenius:
                     raise
+                if tap:   # (nothing has been written, the tap included)
+                    value = self._energy_function()
         neg, pos = self._backend.reconstruction_gradient_H(self._V, self._W_dict, self._H, s)
         Hs = self._H[s]
         assert neg.shape == Hs.shape and pos.shape == Hs.shape
@@ -324,27 +410,36 @@ class TransformInvariantNMF:
                 term *= cross_inhibition / (Hs.shape[1] - 1)
                 pos += term
         self._multiplicative_update(Hs, neg, pos, sparsity=sparsity)
+        return value
 
-    def _iteration(self, h_args, update_H: bool = True, update_W: bool = True):
+    def _iteration(self, h_args, update_H: bool = True, update_W: bool = True, record: bool = False) -> Optional[float]:
         """One full-batch MU iteration (reference :334-340).  A problem small enough to be launch-latency bound goes to the
-        backend as one operation list (one persistent kernel launch per iteration, HIP_Backend.run_schedule)."""
+        backend as one operation list (one persistent kernel launch per iteration, HIP_Backend.run_schedule).
+        record: returns the objective of the (W, H) the iteration starts from -- tapped from the H half step where the
+        backend offers that, else (no tap, no H half step, or the one-call path, which keeps its persistent kernel)
+        evaluated before the iteration."""
         run = self._scheduler(h_args)
         if run is not None and getattr(self._backend, 'prefers_schedule', lambda *_: False)(self._H):
+            value = self._energy_function() if record else None
             ops = ([('H', sliceNone)] if update_H else []) + ([('G', sliceNone, 0., 1.), ('W',)] if update_W else [])
             acc = self._iteration_acc
             if acc is None or acc.shape[1:] != self._W.shape or acc.dtype != self._W.dtype or acc.device != self._W.device:
                 self._iteration_acc = self._backend.new_gradient_accumulator(self._W)
             run(self._V, self._W, self._H, ops, self._iteration_acc, sparsity=h_args['sparsity'], eps=self.eps)
-            return
-        if update_H:
-            self._update_H(**h_args)
+            return value
+        value = self._update_H(record=record, **h_args) if update_H else (self._energy_function() if record else None)
         if update_W:
             self._update_W()
+        if record and value is None:
+            # the H half step left every local sample's objective in the buffer: the one place that waits for it
+            value = self._backend.read_objective(self._objective_buf)
+        return value
 
     def _initialize_matrices(self, V: np.ndarray, keep_W: bool, weights: Optional[np.ndarray] = None):
         """weights: None, or the materialised weights of _weights_of (the backend receives the keyword only then)."""
         self._V = V
         self._iteration_acc = None    # (sized and typed for the W of ONE fit: a refit may change dtype or device)
+        self._objective_buf = None    # (one value per local sample of ONE fit)
         self._weighted = weights is not None
         kw = {} if weights is None else {'weights': weights}
         if self._transforms is not None:
@@ -407,7 +502,8 @@ class TransformInvariantNMF:
     def fit_batch(self, V: np.ndarray, n_iterations: int = 1000, update_H: bool = True, update_W: bool = True,
                   keep_W: bool = False, sparsity_H: float = 0., inhibition_strength: float = 0.,
                   cross_atom_inhibition_strength: float = 0., progress_callback: ProgressCallback = None,
-                  weights=None):
+                  weights=None, objective_every: Optional[int] = None, tol: Optional[float] = None):
+        every, tol = self._convergence_args(objective_every, tol)
         G = self._weights_of(V, weights)
         self._check_samples(V, G)
         assert update_H or update_W
@@ -416,10 +512,16 @@ class TransformInvariantNMF:
         self._init_fit(V, keep_W, G)
         h_args = dict(sparsity=sparsity_H, inhibition=inhibition_strength,
                       cross_inhibition=cross_atom_inhibition_strength)
+        self._begin_history()
+        n_done = 0
         for iteration in range(n_iterations):
-            self._iteration(h_args, update_H, update_W)
-            if not self._report('Iteration', iteration, progress_callback):
+            record = every is not None and iteration % every == 0
+            value = self._iteration(h_args, update_H, update_W, record=record)
+            n_done = iteration + 1
+            stop = record and self._record(iteration, value, tol)
+            if not self._report('Iteration', iteration, progress_callback) or stop:
                 break
+        self._end_history(n_done)
         self._logger.info('TNMF finished.')
 
     # -- mini batches (reference :350-504) ----------------------------------------------------------------------
@@ -427,7 +529,8 @@ class TransformInvariantNMF:
                         batch_size: int = 3, n_epochs: int = 1000, sag_lambda: float = 0.2, keep_W: bool = False,
                         sparsity_H: float = 0., inhibition_strength: float = 0.,
                         cross_atom_inhibition_strength: float = 0., progress_callback: ProgressCallback = None,
-                        weights=None):
+                        weights=None, objective_every: Optional[int] = None, tol: Optional[float] = None):
+        every, tol = self._convergence_args(objective_every, tol)
         G = self._weights_of(V, weights)
         self._check_samples(V, G)
         assert sparsity_H >= 0 and inhibition_strength >= 0 and cross_atom_inhibition_strength >= 0
@@ -448,10 +551,16 @@ class TransformInvariantNMF:
             MiniBatchAlgorithm.GSAG_MU: self._epoch_gsag,
         }[algorithm]
         state = None
+        self._begin_history()
+        n_done = 0
         for epoch in range(n_epochs):
+            # (the exact objective at the epoch boundary: one reconstruction per recorded epoch; the epochs run as they do)
+            stop = every is not None and epoch % every == 0 and self._record(epoch, self._energy_function(), tol)
             state = epoch_fn(state, batches, h_args, sag_lambda)
-            if not self._report('Epoch', epoch, progress_callback):
+            n_done = epoch + 1
+            if not self._report('Epoch', epoch, progress_callback) or stop:
                 break
+        self._end_history(n_done)
         self._logger.info('MiniBatch TNMF finished.')
 
     def _local_gradient_W(self):

@@ -29,6 +29,7 @@ EXPORTS = (
     'tnmf_hip_group_expand_W', 'tnmf_hip_group_fold_grad_W', 'tnmf_hip_group_apply_W',
     'tnmf_hip_atom_ops_create', 'tnmf_hip_atom_ops_destroy', 'tnmf_hip_ops_expand_W', 'tnmf_hip_ops_fold_grad_W',
     'tnmf_hip_ops_apply_W',
+    'tnmf_hip_ctx_set_objective_tap', 'tnmf_hip_sample_objective',
 )
 
 MODES = {'valid': 0, 'full': 1, 'circular': 2, 'reflect': 3}
@@ -136,6 +137,8 @@ def load() -> ctypes.CDLL:
     lib.tnmf_hip_ops_expand_W.argtypes = [vp, gp, vp, vp, vp, vp]
     lib.tnmf_hip_ops_fold_grad_W.argtypes = [vp, gp, vp, vp, vp, vp]
     lib.tnmf_hip_ops_apply_W.argtypes = [vp, gp, vp, vp, vp, vp, cd, vp]
+    lib.tnmf_hip_ctx_set_objective_tap.argtypes = [vp, vp]
+    lib.tnmf_hip_sample_objective.argtypes = [vp, gp, cd, cd, vp, vp, vp, vp, vp, vp]
     lib.tnmf_hip_pad_H.argtypes = [vp, gp, ci, vp, vp, vp]
     lib.tnmf_hip_fold_H.argtypes = [vp, gp, ci, vp, vp, vp]
     for name in EXPORTS:

@@ -667,15 +667,21 @@ class HIP_Backend(Backend):
 
     def fused_update_H(self, V, W: torch.Tensor, H: torch.Tensor, s: slice = sliceNone, sparsity: float = 0.,
                        eps: float = 1e-9, inhibition: float = 0., cross_inhibition: float = 0.,
-                       inhibition_kernels: Optional[Sequence[np.ndarray]] = None, beta: float = 2.) -> None:
+                       inhibition_kernels: Optional[Sequence[np.ndarray]] = None, beta: float = 2.,
+                       objective_out: Optional[torch.Tensor] = None) -> None:
         """One H half step, in place (reference: TransformInvariantNMF.py:246-271): 'valid' mode without lateral terms on
         the fused kernels (tnmf_hip_update_H); with lateral inhibition / cross-atom inhibition and for the other
         reconstruction modes through tnmf_hip_update_H_ex, for beta != 2 through tnmf_hip_update_H_beta, with weights
         bound through tnmf_hip_update_H_weighted -- the separable convolution, the lateral terms, the pad, the fold, the
-        (weighted) beta-divergence fields and the update all run as kernels of the library."""
+        (weighted) beta-divergence fields and the update all run as kernels of the library.
+        objective_out (new_objective_buffer()): objective_out[s] receives each sample's objective at the (W, H) passed in,
+        read off the reconstruction the step computes anyway (tnmf_hip_ctx_set_objective_tap); no synchronisation."""
         self._check_beta(beta)
         ls = self._local(s)
         Hs, Vs = H[ls], self._V_dev[ls]
+        if objective_out is not None:
+            assert objective_out.is_cuda and objective_out.dtype == torch.float64 and objective_out.is_contiguous()
+            assert tuple(objective_out.shape) == (self.n_local_samples,)
         if Hs.shape[0] == 0:
             return
         self._check_W(W)
@@ -717,7 +723,52 @@ class HIP_Backend(Backend):
                     if beta == 2.:
                         return self._lib.tnmf_hip_update_H_ex(*args, self._stream()), 'tnmf_hip_update_H_ex'
                     return self._lib.tnmf_hip_update_H_beta(*args, float(beta), self._stream()), 'tnmf_hip_update_H_beta'
-        self._call_resident_H(Hs, W, True, run, lateral)
+        if objective_out is None:
+            self._call_resident_H(Hs, W, True, run, lateral)
+            return
+        _lib.check(self._lib.tnmf_hip_ctx_set_objective_tap(self._ctx, _ptr(objective_out[ls])),
+                   'tnmf_hip_ctx_set_objective_tap')
+        try:
+            self._call_resident_H(Hs, W, True, run, lateral)
+        finally:
+            self._lib.tnmf_hip_ctx_set_objective_tap(self._ctx, None)
+
+    # -- the objective tap ------------------------------------------------------------------------------------------
+    # The H half step materialises R = reconstruct(W, H) before anything else: one pass over (V, R[, G]) there gives
+    # the objective of the state the iteration starts from, per sample (include/tnmf_hip.h, "per-sample objective and
+    # the objective tap").  Writing it is asynchronous; read_objective is the only place that waits.
+    supports_objective_tap = True
+
+    def new_objective_buffer(self) -> torch.Tensor:
+        """One float64 per local sample on the device, for ``fused_update_H(..., objective_out=)``."""
+        return torch.zeros(self.n_local_samples, dtype=torch.float64, device=self._device)
+
+    def read_objective(self, buf: torch.Tensor) -> float:
+        """The objective a tapped H half step over all local samples left in ``buf``: one copy of the per-sample values,
+        summed in sample order; with several ranks one all-reduce of the scalar (every rank decides alike)."""
+        total = 0.0
+        for x in buf.cpu().tolist():
+            total += x
+        if self._world > 1:
+            t = torch.tensor([total], dtype=torch.float64, device=self._device)
+            self._all_reduce(t)
+            return float(t.item())
+        return total
+
+    def sample_objective(self, V, W: torch.Tensor, H: torch.Tensor, beta: float = 2., eps: float = 1e-9) -> np.ndarray:
+        """[n_local_samples] float64: each local sample's share of reconstruction_energy(V, W, H, beta, eps)
+        -> tnmf_hip_sample_objective."""
+        self._check_beta(beta)
+        self._check_W(W)
+        self._foreign_H()
+        self._check_H(H, W.shape[0])
+        H = self._pad(H)
+        out = torch.zeros(H.shape[0], dtype=torch.float64, device=self._device)
+        self._call_H(H, False, lambda Hc, ld: (self._lib.tnmf_hip_sample_objective(
+            self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)), float(beta), float(eps),
+            _ptr(self._V_dev), None if self._G_dev is None else _ptr(self._G_dev), _ptr(W), _ptr(Hc), _ptr(out),
+            self._stream()), 'tnmf_hip_sample_objective'))
+        return out.cpu().numpy()
 
     # -- a whole mini-batch epoch in one call -------------------------------------------------------------------
     @property

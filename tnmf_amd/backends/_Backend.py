@@ -25,7 +25,12 @@ declares ``supports_transforms`` takes ``initialize(..., transforms=name)`` (tnm
 ``n_atoms * T`` effective atoms while W keeps ``n_atoms``, and it offers ``expand_W(W, name, W_eff=None) -> W_eff``,
 ``fold_gradient_W(negpos_eff, name) -> negpos`` and ``fused_update_W_transformed(V, W, W_eff, H, s, name, eps, beta)``;
 every other hook is called with W_eff in the place of W.  A backend that declares ``supports_atom_operators`` as well
-takes an ``AtomOperators`` (tnmf_amd/transforms.py) wherever those hooks take a group name.
+takes an ``AtomOperators`` (tnmf_amd/transforms.py) wherever those hooks take a group name.  A backend that declares
+``supports_objective_tap`` reads the objective off the reconstruction its H half step computes anyway: it offers
+``new_objective_buffer() -> buf`` (one float64 per local sample, backend-native), takes ``fused_update_H(...,
+objective_out=buf)`` -- passed only on the iterations that record; the step's slice selects the part written, with each
+sample's objective at the (W, H) passed in -- and ``read_objective(buf) -> float``, the only call that waits: the sum in
+sample order, over all ranks.  ``sample_objective(V, W, H, beta, eps)`` -> one float64 per local sample, host side.
 """
 import abc
 from typing import Optional, Sequence, Tuple, Union
@@ -54,6 +59,8 @@ class Backend(abc.ABC):
 
     # takes an AtomOperators as ``transforms`` (with ``supports_transforms``): arbitrary non-negative linear atom maps
     supports_atom_operators = False
+    # fused_update_H takes ``objective_out`` (with new_objective_buffer / read_objective): the objective tap
+    supports_objective_tap = False
 
     def __init__(self, reconstruction_mode: str = 'valid'):
         self._reconstruction_mode = reconstruction_mode

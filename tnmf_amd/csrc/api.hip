@@ -318,6 +318,23 @@ int beta_fields_of(tnmf_hip_ctx *ctx, const Geo &g, int dtype, const double *bet
     return TNMF_OK;
 }
 
+// the per-sample objective of (V, R[, G]): N samples of L elements each into out (N doubles on the device).  beta == NULL:
+// the Frobenius objective (weighted with G != NULL).  Asynchronous on s.
+int sample_objective_of(tnmf_hip_ctx *ctx, int dtype, const double *beta, double eps, const void *V, const void *G,
+                        const void *R, size_t N, size_t L, double *out, hipStream_t s) {
+    const size_t B = objective_blocks(L);
+    if (B > 1) CHECK(ensure_buffer(&ctx->ob, &ctx->ob_bytes, align_up(N * B * sizeof(double), 256), false));
+    return launch_sample_objective(dtype, beta ? *beta : 2.0, eps, V, G, R, N, L, static_cast<double *>(ctx->ob), out, s);
+}
+
+// the objective tap of the H half steps (tnmf_hip_ctx_set_objective_tap): R holds the reconstruction of the activations
+// as they were passed in; reads only, so the step computes what it computes without the tap
+inline int tap_objective(tnmf_hip_ctx *ctx, int dtype, const double *beta, double eps, const void *V, const void *G,
+                         const void *R, size_t N, size_t L, hipStream_t s) {
+    if (!ctx->obj_tap) return TNMF_OK;
+    return sample_objective_of(ctx, dtype, beta, eps, V, G, R, N, L, ctx->obj_tap, s);
+}
+
 static_assert(kBetaPartials <= kEnergyPartials, "the energy words of the scratch hold the beta partials");
 
 inline bool beta_ok(double beta) { return beta == beta && beta - beta == 0.0; }   // finite
@@ -390,6 +407,7 @@ int vol_api_update_H(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V
         CHECK(vol_scratch(ctx, v, dtype, &Rs, nullptr));
     }
     if (!r_is_valid) CHECK(vol_reconstruct(v, dtype, W, H_inout, Rs, s));
+    CHECK(tap_objective(ctx, dtype, nullptr, eps, V, nullptr, Rs, (size_t)v.N, (size_t)v.C * vol_vox(v), s));
     const double reg = eps + (sparsity > 0 ? sparsity : 0.0);   // TransformInvariantNMF.py:227-230
     return vol_corr_W(v, dtype, V, Rs, W, H_inout, nullptr, nullptr, true, reg, s);
 }
@@ -441,10 +459,12 @@ int vol_api_update_H_ex(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, 
     }
     if (mode == TNMF_MODE_VALID) {
         CHECK(vol_reconstruct(v, dtype, W, H_inout, Rs, s));
+        CHECK(tap_objective(ctx, dtype, nullptr, eps, V, nullptr, Rs, (size_t)v.N, (size_t)v.C * vol_vox(v), s));
         CHECK(vol_corr_W(v, dtype, V, Rs, W, nullptr, neg, pos, false, 0.0, s));
     } else {
         CHECK(vol_pad_fold(ctx, v, dtype, mode, false, H_inout, Hp, s));
         CHECK(vol_reconstruct(v, dtype, W, Hp, Rs, s));
+        CHECK(tap_objective(ctx, dtype, nullptr, eps, V, nullptr, Rs, (size_t)v.N, (size_t)v.C * vol_vox(v), s));
         CHECK(vol_corr_W(v, dtype, V, Rs, W, nullptr, negp, posp, false, 0.0, s));
         CHECK(vol_pad_fold(ctx, v, dtype, mode, true, negp, neg, s));
         CHECK(vol_pad_fold(ctx, v, dtype, mode, true, posp, pos, s));
@@ -595,7 +615,7 @@ int tnmf_hip_ctx_create(int device_id, tnmf_hip_ctx **out) {
 int tnmf_hip_ctx_destroy(tnmf_hip_ctx *ctx) {
     if (!ctx) return TNMF_OK;
     int rc = TNMF_OK;
-    if (ctx->ws || ctx->fft.ws || ctx->wimg || ctx->hw || ctx->qb) {
+    if (ctx->ws || ctx->fft.ws || ctx->wimg || ctx->hw || ctx->qb || ctx->ob) {
         (void)hipSetDevice(ctx->device);
         (void)hipDeviceSynchronize();
     }
@@ -603,6 +623,7 @@ int tnmf_hip_ctx_destroy(tnmf_hip_ctx *ctx) {
     split_release(ctx);
     if (ctx->hw) (void)hipFree(ctx->hw);
     if (ctx->qb) (void)hipFree(ctx->qb);
+    if (ctx->ob) (void)hipFree(ctx->ob);
     for (int i = 0; i < tnmf_hip_ctx::kOpSlots; ++i) {
         if (ctx->ops_done[i]) (void)hipEventDestroy(ctx->ops_done[i]);
         if (ctx->ops_pinned[i]) (void)hipHostFree(ctx->ops_pinned[i]);
@@ -815,6 +836,39 @@ int tnmf_hip_energy_weighted(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, doubl
     return energy_2d(ctx, geom, V, G, W, H, out_host, beta == 2.0 ? nullptr : &beta, eps, stream);
 }
 
+int tnmf_hip_ctx_set_objective_tap(tnmf_hip_ctx *ctx, double *per_sample_dev) {
+    if (!ctx) return TNMF_E_NULL;
+    ctx->obj_tap = per_sample_dev;
+    return TNMF_OK;
+}
+
+int tnmf_hip_sample_objective(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, double beta, double eps, const void *V,
+                              const void *G_or_null, const void *W, const void *H, double *per_sample_dev, void *stream) {
+    if (!ctx || !geom) return TNMF_E_NULL;
+    if (!beta_ok(beta)) return TNMF_E_UNSUPPORTED;
+    const double *bp = beta == 2.0 ? nullptr : &beta;
+    if (is_vol(geom)) {
+        if (bp || G_or_null) return TNMF_E_UNSUPPORTED;   // (volumes: the Frobenius objective, unweighted)
+        VOL_ENTER(ctx, geom);
+        if (v.N == 0) return TNMF_OK;
+        if (!V || !W || !H || !per_sample_dev) return TNMF_E_NULL;
+        void *Rs;
+        CHECK(vol_scratch(ctx, v, dtype, &Rs, nullptr));
+        CHECK(vol_reconstruct(v, dtype, W, H, Rs, s));
+        return sample_objective_of(ctx, dtype, nullptr, eps, V, nullptr, Rs, (size_t)v.N, (size_t)v.C * vol_vox(v),
+                                   per_sample_dev, s);
+    }
+    ENTER(ctx, geom);
+    if (g.N == 0) return TNMF_OK;
+    if (!V || !W || !H || !per_sample_dev) return TNMF_E_NULL;
+    const Scratch sc = plan_scratch(ctx, g, dtype);
+    CHECK(ensure_scratch(ctx, sc.total));
+    void *Rs = ws_at(ctx, sc.r_off);
+    CHECK(do_reconstruct(ctx, g, dtype, W, H, Rs, s));
+    return sample_objective_of(ctx, dtype, bp, eps, V, G_or_null, Rs, (size_t)g.N, (size_t)g.C * g.Dy * g.Dx,
+                               per_sample_dev, s);
+}
+
 int tnmf_hip_beta_fields(tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *R, void *Q,
                          void *P, size_t n_elems, void *stream) {
     if (!ctx) return TNMF_E_NULL;
@@ -922,6 +976,7 @@ static int update_H_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, c
             CHECK(launch_inhibition(ctx, dtype, g.N, g.M, g.Hy, g.Hs, H_inout, E, ky, ly, kx, lx, inhibition, xc, s));
         }
         if (!r_is_valid) CHECK(do_reconstruct(ctx, g, dtype, W, H_inout, Rs, s));
+        CHECK(tap_objective(ctx, dtype, beta, eps, V, G, Rs, (size_t)g.N, (size_t)g.C * g.Dy * g.Dx, s));
         if (beta || G) CHECK(beta_fields_of(ctx, g, dtype, beta, eps, V, G, Rs, &V, s));
         int rc = do_corr_W(ctx, g, dtype, V, Rs, W, H_inout, nullptr, nullptr, true, reg, s, E);
         if (!E || (rc != TNMF_E_UNSUPPORTED && rc != TNMF_E_STRIDE)) return rc;
@@ -953,6 +1008,7 @@ static int update_H_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, c
     fft_invalidate(ctx);   // the padded copy lives at the same address every call, with new contents
     CHECK(launch_pad_fold(ctx, g, dtype, mode, false, H_inout, Hp, s));
     CHECK(do_reconstruct(ctx, g, dtype, W, Hp, Rs, s));
+    CHECK(tap_objective(ctx, dtype, beta, eps, V, G, Rs, (size_t)g.N, (size_t)g.C * g.Dy * g.Dx, s));
     if (beta || G) CHECK(beta_fields_of(ctx, g, dtype, beta, eps, V, G, Rs, &V, s));
     CHECK(do_corr_W(ctx, g, dtype, V, Rs, W, nullptr, negp, posp, false, 0.0, s));
     if (lateral) CHECK(launch_inhibition(ctx, dtype, g.N, g.M, Sy, Sx, H_inout, E, ky, ly, kx, lx, inhibition, xc, s));

@@ -24,3 +24,19 @@ int launch_beta_fields(const tnmf_hip_ctx *ctx, int dtype, double beta, double e
 constexpr int kBetaPartials = 2048;
 int launch_beta_energy(const tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *G,
                        const void *R, size_t n, double *partials, double *out_dev, hipStream_t s);
+
+// The objective of every sample of a call, out[n] = sum over the sample's L = C * D elements of the data term -- 1/2 (V - R)^2
+// (beta == 2, G == nullptr: the element formula of launch_half_sqdiff), D_beta(V | max(R, 0) + eps) (beta != 2) or G times
+// either (G != nullptr; G <= 0 selects exactly 0: launch_beta_energy's formulas).  Their sum over n is what the energy
+// entry points return for the same (V, R[, G]).  A segmented two-stage reduction in double without atomics: a sample is
+// cut into blocks of kObjChunk elements -- a function of L alone, never of N, so a sample's value does not depend on which
+// samples share the call -- each block leaves one partial, and the partials of a sample are added in block order.
+// Asynchronous on s.
+constexpr int kObjChunk = 4096;   // elements of one sample per block
+
+inline size_t objective_blocks(size_t L) { return L ? (L + kObjChunk - 1) / kObjChunk : 1; }
+
+// V, R (and G) hold N samples of L elements of type dtype; out: N doubles on the device; partials: N * objective_blocks(L)
+// doubles on the device (not touched when a sample is one block).
+int launch_sample_objective(int dtype, double beta, double eps, const void *V, const void *G, const void *R, size_t N,
+                            size_t L, double *partials, double *out, hipStream_t s);

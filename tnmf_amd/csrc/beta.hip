@@ -1,6 +1,6 @@
 // beta.hip -- the elementwise kernels of the beta-divergence and weighted objectives (beta.h): the fields Q, P that stand
-// in for V, R in the correlations of a multiplicative update, and the (weighted) D_beta energy.  Streaming kernels: 16-byte loads and stores
-// for aligned operands, a scalar tail for lengths that are not a whole number of vectors.
+// in for V, R in the correlations of a multiplicative update, the (weighted) D_beta energy and the same objective per sample.
+// Streaming kernels: 16-byte loads and stores for aligned operands, a scalar tail for lengths that are not a whole number of vectors.
 #include <cmath>
 #include <cstdint>
 
@@ -220,6 +220,112 @@ int energy_typed(double beta, double eps, const void *V, const void *G, const vo
     return TNMF_OK;
 }
 
+// ---- the objective of every sample of a call (beta.h: launch_sample_objective): the tap of the H half steps and
+// tnmf_hip_sample_objective.  The same assignment of elements to threads with 16-byte loads and with scalar loads, so the
+// value of a sample does not depend on the path.
+
+// one element's term.  K: 0 = Itakura-Saito, 1 = Kullback-Leibler, 2 = Frobenius, 3 = any other beta.  Unweighted K == 2
+// is (V - R)^2 with the difference taken in T (k_sqdiff_partial; the 1/2 is applied to the block's sum); weighted K == 2
+// is 1/2 G (V - R)^2 in double, and G <= 0 selects exactly 0 whatever V and R hold (k_beta_energy).
+template <int K, typename T, bool kW>
+__device__ __forceinline__ double term(T v, T g, T r, double eps, double beta) {
+    if constexpr (kW) {
+        double d;
+        if constexpr (K == 2) {
+            const double e = (double)v - (double)r;
+            d = 0.5 * e * e;
+        } else {
+            d = divergence<K>((double)v, (double)r, eps, beta);
+        }
+        const double gd = (double)g;
+        return gd > 0.0 ? gd * d : 0.0;
+    } else if constexpr (K == 2) {
+        const T d = v - r;
+        return (double)d * (double)d;
+    } else {
+        return divergence<K>((double)v, (double)r, eps, beta);
+    }
+}
+
+// block (n, b) = blockIdx.x / B, blockIdx.x % B sums elements [b * kObjChunk, min(L, (b + 1) * kObjChunk)) of sample n;
+// thread t takes the vectors t, t + kBlock, ... of the block.  kVec: every vector is whole and 16-byte aligned.
+template <int K, typename T, bool kVec, bool kW>
+__global__ __launch_bounds__(kBlock) void k_sample_objective(const T *__restrict__ V, const T *__restrict__ G,
+                                                             const T *__restrict__ R, size_t L, unsigned B, double eps,
+                                                             double beta, double *__restrict__ dst) {
+    using VT = typename Vec<T>::type;
+    constexpr int kL = Vec<T>::n;
+    constexpr int kIter = kObjChunk / (kBlock * kL);
+    static_assert(kIter * kBlock * kL == kObjChunk, "a block is a whole number of passes of its threads");
+    __shared__ double sh[kBlock / 64];
+    const size_t n = blockIdx.x / B, b = blockIdx.x % B;
+    const size_t lo = b * kObjChunk;
+    const size_t len = L - lo < (size_t)kObjChunk ? L - lo : (size_t)kObjChunk;
+    const T *v = V + n * L + lo, *r = R + n * L + lo, *g = kW ? G + n * L + lo : nullptr;
+    double acc = 0.0;
+    if constexpr (kVec) {
+        VT vv[kIter], rr[kIter], gg[kIter];
+#pragma unroll
+        for (int k = 0; k < kIter; ++k) {   // every load of the block in flight before the first term
+            const size_t i = ((size_t)k * kBlock + threadIdx.x) * kL;
+            if (i < len) {
+                vv[k] = *reinterpret_cast<const VT *>(v + i);
+                rr[k] = *reinterpret_cast<const VT *>(r + i);
+                if constexpr (kW) gg[k] = *reinterpret_cast<const VT *>(g + i);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kIter; ++k) {
+            const size_t i = ((size_t)k * kBlock + threadIdx.x) * kL;
+            if (i < len) {
+#pragma unroll
+                for (int j = 0; j < kL; ++j)
+                    acc += term<K, T, kW>(reinterpret_cast<const T *>(&vv[k])[j],
+                                          kW ? reinterpret_cast<const T *>(&gg[k])[j] : T(0),
+                                          reinterpret_cast<const T *>(&rr[k])[j], eps, beta);
+            }
+        }
+    } else {
+        for (int k = 0; k < kIter; ++k) {
+            const size_t i = ((size_t)k * kBlock + threadIdx.x) * kL;
+            for (int j = 0; j < kL; ++j)
+                if (i + j < len) acc += term<K, T, kW>(v[i + j], kW ? g[i + j] : T(0), r[i + j], eps, beta);
+        }
+    }
+    const double tot = block_sum(acc, sh);
+    if (threadIdx.x == 0) dst[blockIdx.x] = (!kW && K == 2) ? 0.5 * tot : tot;
+}
+
+// out[n] = the B partials of sample n in block order; one thread per sample
+__global__ __launch_bounds__(kBlock) void k_objective_finish(const double *__restrict__ partials, size_t N, unsigned B,
+                                                             double *__restrict__ out) {
+    const size_t n = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (n >= N) return;
+    double acc = 0.0;
+    for (unsigned b = 0; b < B; ++b) acc += partials[n * B + b];
+    out[n] = acc;
+}
+
+template <int K, typename T, bool kW>
+void objective_as(bool vec, double beta, double eps, const void *V, const void *G, const void *R, size_t L, unsigned B,
+                  unsigned grid, double *dst, hipStream_t s) {
+    if (vec)
+        hipLaunchKernelGGL((k_sample_objective<K, T, true, kW>), dim3(grid), dim3(kBlock), 0, s, (const T *)V,
+                           (const T *)G, (const T *)R, L, B, eps, beta, dst);
+    else
+        hipLaunchKernelGGL((k_sample_objective<K, T, false, kW>), dim3(grid), dim3(kBlock), 0, s, (const T *)V,
+                           (const T *)G, (const T *)R, L, B, eps, beta, dst);
+}
+
+template <typename T, bool kW>
+void objective_typed(bool vec, double beta, double eps, const void *V, const void *G, const void *R, size_t L,
+                     unsigned B, unsigned grid, double *dst, hipStream_t s) {
+    if (beta == 0.0) objective_as<0, T, kW>(vec, beta, eps, V, G, R, L, B, grid, dst, s);
+    else if (beta == 1.0) objective_as<1, T, kW>(vec, beta, eps, V, G, R, L, B, grid, dst, s);
+    else if (beta == 2.0) objective_as<2, T, kW>(vec, beta, eps, V, G, R, L, B, grid, dst, s);
+    else objective_as<3, T, kW>(vec, beta, eps, V, G, R, L, B, grid, dst, s);
+}
+
 }  // namespace
 
 int launch_beta_fields(const tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *G,
@@ -238,5 +344,35 @@ int launch_beta_energy(const tnmf_hip_ctx *ctx, int dtype, double beta, double e
     if (rc != TNMF_OK) return rc;
     hipLaunchKernelGGL(k_beta_sum, dim3(1), dim3(kBlock), 0, s, partials, grid, out_dev);
     TNMF_LAUNCH_CHECK();
+    return TNMF_OK;
+}
+
+int launch_sample_objective(int dtype, double beta, double eps, const void *V, const void *G, const void *R, size_t N,
+                            size_t L, double *partials, double *out, hipStream_t s) {
+    if (N == 0) return TNMF_OK;
+    if (L == 0) {
+        TNMF_HIP_TRY(hipMemsetAsync(out, 0, N * sizeof(double), s));
+        return TNMF_OK;
+    }
+    const size_t B = objective_blocks(L);
+    if (N * B > 0x7fffffffu) return TNMF_E_GEOM;   // (one block index per (sample, block))
+    // whole, aligned vectors: 16-byte aligned bases and samples that are a whole number of vectors (kObjChunk is one)
+    const size_t es = dtype == 0 ? 4 : 8;
+    const bool vec = ((reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(G) | reinterpret_cast<uintptr_t>(R)) & 15) == 0 &&
+                     (L * es) % 16 == 0;
+    double *dst = B == 1 ? out : partials;
+    if (dtype == 0) {
+        if (G) objective_typed<float, true>(vec, beta, eps, V, G, R, L, (unsigned)B, (unsigned)(N * B), dst, s);
+        else objective_typed<float, false>(vec, beta, eps, V, G, R, L, (unsigned)B, (unsigned)(N * B), dst, s);
+    } else {
+        if (G) objective_typed<double, true>(vec, beta, eps, V, G, R, L, (unsigned)B, (unsigned)(N * B), dst, s);
+        else objective_typed<double, false>(vec, beta, eps, V, G, R, L, (unsigned)B, (unsigned)(N * B), dst, s);
+    }
+    TNMF_LAUNCH_CHECK();
+    if (B > 1) {
+        hipLaunchKernelGGL(k_objective_finish, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, partials, N,
+                           (unsigned)B, out);
+        TNMF_LAUNCH_CHECK();
+    }
     return TNMF_OK;
 }
