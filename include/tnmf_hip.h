@@ -452,6 +452,31 @@ int tnmf_hip_ops_fold_grad_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const
 int tnmf_hip_ops_apply_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const tnmf_hip_atom_ops *ops, void *W_inout,
                          void *W_eff_out, const void *negpos_eff, double eps, void *stream);
 
+/* ---- detections: thresholded, non-maximum-suppressed peaks of H (ABI 8, additive: the version stays 8) ---------------
+ * The read-out of a fit.  H is viewed as [N, P, *S]: P = geom->M planes (with transforms the M * T effective atoms) of
+ * shift shape S = D + A - 1, rows `h_row_stride` apart (pad columns are neither read nor reported), on 1, 2 or 3 shift
+ * axes.  `geom` describes H as it does everywhere; the activations of a reconstruction mode other than 'valid' have
+ * another shift shape S (see "reconstruction modes" above): for those the caller passes D = S and A = 1 on every shift
+ * axis.  C is not read.  Nothing wraps around in any mode.
+ * The entry (n, p, u) with value h is a detection iff h > threshold (strict; threshold >= 0) and no competitor suppresses
+ * it.  Its competitors are the other entries (n, q, v) of the same sample with |v_k - u_k| <= radius[k] on every shift
+ * axis k, inside the plane, and q in the run of `group` consecutive planes [g * group, (g + 1) * group) that holds p
+ * (group 1: its own plane; T: the orientations of its atom; P: every plane).  A competitor suppresses it when its value is
+ * larger, or equal with the lower flat C-order index in [N, P, *S] -- one winner per plateau and neighbourhood.  NaN
+ * compares false: never a detection, never a suppressor.  radius 0 everywhere with group 1 is a pure threshold; a radius
+ * at or beyond the extent of an axis means the whole axis.
+ * Output: count_out (one unsigned 64-bit word on the device) is zeroed on the stream, then counts EVERY detection; the
+ * detections are appended in no particular order as idx_out[slot] = flat C-order index in [N, P, *S] of the H passed (a
+ * mini-batch slice counts from its own first sample), val_out[slot] = the entry's bits in the element type, while
+ * slot < capacity.  Nothing is written at or beyond `capacity`; a count above it tells the caller the size to come back
+ * with.  Asynchronous like the other entry points: the caller reads count_out.
+ * TNMF_E_GEOM: a negative radius, group < 1 or not a divisor of geom->M, sizes <= 0, a row stride below the shift width;
+ * TNMF_E_UNSUPPORTED: a threshold that is negative or NaN; TNMF_E_NULL, TNMF_E_DTYPE as usual (idx_out / val_out may be
+ * NULL when capacity is 0) -- all before anything is written. */
+int tnmf_hip_find_peaks(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *H, double threshold, const int *radius,
+                        int group, long long *idx_out, void *val_out, size_t capacity, unsigned long long *count_out,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

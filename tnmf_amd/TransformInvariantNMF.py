@@ -3,7 +3,8 @@ Front end of the MI355X shift-invariant NMF: the multiplicative-update schedules
 
 Public surface = the reference's (tnmf/TransformInvariantNMF.py): ``TransformInvariantNMF(n_atoms, atom_shape,
 inhibition_range, backend, logger, verbose, **backend_kwargs)`` with ``fit`` / ``fit_batch`` / ``fit_minibatches`` /
-``fit_stream``, the read-outs ``W``, ``H``, ``V``, ``R``, ``R_partial(i)`` and the ``MiniBatchAlgorithm`` enum.
+``fit_stream``, the read-outs ``W``, ``H``, ``V``, ``R``, ``R_partial(i)`` and the ``MiniBatchAlgorithm`` enum; beyond it
+``detections()`` (-> ``Detections``), the events read off ``H``.
 The only backend shipped is ``'hip'`` (tnmf_amd/backends/HIP.py); any object implementing
 tnmf_amd.backends._Backend.Backend can be passed instead of a name.
 
@@ -14,6 +15,7 @@ Differences from the reference, all deliberate:
   * the per-iteration energy is evaluated only if the logger is enabled for INFO (the reference formats it eagerly,
     TransformInvariantNMF.py:346, which costs a reconstruction per iteration).
 """
+import dataclasses
 import enum
 import itertools
 import logging
@@ -95,6 +97,59 @@ def _backend_registry():
 
 
 ProgressCallback = Callable[['TransformInvariantNMF', int], bool]
+
+
+@dataclasses.dataclass(frozen=True)
+class Detections:
+    """The detections of a fitted model (``TransformInvariantNMF.detections``): K rows in the C order of the ``H`` property.
+
+    sample    [K] index of the sample in the order of ``V`` (with a process group: this rank's samples, offset by the start
+              of its shard)
+    atom      [K] atom m
+    transform [K] orientation t of the atom (0 without transforms)
+    shift     [K, k] index into the k shift axes of ``H``
+    origin    [K, k] sample coordinate of the atom's first pixel: the occurrence covers ``origin .. origin + atom_shape - 1``
+              (``shift - (atom_shape - 1)`` in 'valid' mode, ``shift`` in 'full' / 'circular' / 'reflect'); positions outside
+              the sample belong to a partly visible, wrapped or mirrored occurrence
+    strength  [K] the entries of ``H``, bit for bit
+    """
+    sample: np.ndarray
+    atom: np.ndarray
+    transform: np.ndarray
+    shift: np.ndarray
+    origin: np.ndarray
+    strength: np.ndarray
+
+    def __len__(self) -> int:
+        return len(self.sample)
+
+
+def find_peaks_numpy(H: np.ndarray, threshold: float, radius: Tuple[int, ...], group: int = 1):
+    """(idx, val) of the detections of ``H[N, P, *S]`` on the host, for backends without ``find_peaks``: the semantics of
+    tnmf_hip_find_peaks (include/tnmf_hip.h, "detections"), one window per candidate.  Not on the hip path."""
+    H = np.ascontiguousarray(H)
+    shape, k = H.shape, H.ndim - 2
+    assert k >= 1 and len(radius) == k and shape[1] % group == 0
+    t = H.dtype.type(threshold)          # the largest value of H's type not above the threshold: `h > t` is then exact
+    if float(t) > threshold:
+        t = np.nextafter(t, H.dtype.type(-np.inf))
+    flat = H.reshape(-1)
+    candidates = np.flatnonzero(flat > t)
+    keep = np.zeros(len(candidates), dtype=bool)
+    for i, (f, at) in enumerate(zip(candidates, zip(*np.unravel_index(candidates, shape)))):
+        n, p, u = at[0], at[1], at[2:]
+        g0 = p // group * group
+        lo = [max(0, int(x) - r) for x, r in zip(u, radius)]
+        box = H[(n, slice(g0, g0 + group)) + tuple(slice(a, int(x) + r + 1) for a, x, r in zip(lo, u, radius))]
+        h = flat[f]
+        if np.any(box > h):
+            continue
+        ties = np.argwhere(box == h)     # (the candidate itself is one of them)
+        ties = np.ravel_multi_index((np.full(len(ties), n), g0 + ties[:, 0]) + tuple(a + ties[:, 1 + j] for j, a in
+                                                                                   enumerate(lo)), shape)
+        keep[i] = not np.any(ties < f)
+    idx = candidates[keep].astype(np.int64)
+    return idx, flat[idx]
 
 
 class TransformInvariantNMF:
@@ -277,6 +332,78 @@ class TransformInvariantNMF:
         """The objective of the current (W, H): 1/2 ||V - R||^2, sum D_beta(V | R + eps), or the weighted sum of either --
         the data term only, without the sparsity and inhibition penalties."""
         return self._energy_function()
+
+    # -- detections -----------------------------------------------------------------------------------------------------
+    _SUPPRESS = ('atom', 'transforms', 'all')
+
+    def detections(self, threshold: float = 0., min_distance: Union[None, int, Tuple[int, ...]] = None,
+                   suppress: str = 'atom', max_per_sample: Optional[int] = None) -> Detections:
+        """Where each atom occurs: the entries of ``H`` above ``threshold`` (strictly) that no entry within
+        ``min_distance`` on every shift axis suppresses -- a larger one, or an equal one with the lower C-order index, so a
+        plateau has one winner per neighbourhood.  Neighbourhoods end at the border of the plane in every reconstruction
+        mode.  NaN is never a detection.
+
+        min_distance : ``None`` (the model's ``inhibition_range``: the neighbourhood lateral inhibition acts on), an int or
+                       one int per shift axis, >= 0
+        suppress : what competes for a location -- ``'atom'`` each effective atom with itself only, ``'transforms'`` the T
+                   orientations of one atom, ``'all'`` every atom and orientation
+        max_per_sample : keep only each sample's strongest k (ties: the lower C-order index first)
+
+        On a backend with ``find_peaks`` the search runs on the device and only the list of detections is copied; any
+        other backend's ``H`` is searched on the host."""
+        if self._H is None:
+            raise RuntimeError('detections() needs a fitted model: call fit first')
+        if (isinstance(threshold, (bool, np.bool_)) or not isinstance(threshold, numbers.Real)
+                or not math.isfinite(threshold) or threshold < 0):
+            raise ValueError(f'threshold must be a finite number >= 0, not {threshold!r}')
+        k = len(self.atom_shape)
+        if min_distance is None:
+            radius = self._inhibition_range
+        elif isinstance(min_distance, numbers.Integral) and not isinstance(min_distance, (bool, np.bool_)):
+            radius = (min_distance,) * k
+        elif isinstance(min_distance, (tuple, list)) and len(min_distance) == k:
+            radius = tuple(min_distance)
+        else:
+            raise ValueError(f'min_distance must be None, an int or {k} ints, not {min_distance!r}')
+        if any(isinstance(r, (bool, np.bool_)) or not isinstance(r, numbers.Integral) or r < 0 for r in radius):
+            raise ValueError(f'min_distance must be >= 0 on every axis, not {min_distance!r}')
+        radius = tuple(int(r) for r in radius)
+        if not isinstance(suppress, str) or suppress not in self._SUPPRESS:
+            raise ValueError(f'suppress must be one of {self._SUPPRESS}, not {suppress!r}')
+        if suppress == 'transforms' and self._transforms is None:
+            raise ValueError("suppress='transforms' needs a model with transforms")
+        if max_per_sample is not None and (isinstance(max_per_sample, (bool, np.bool_))
+                                           or not isinstance(max_per_sample, numbers.Integral) or max_per_sample < 0):
+            raise ValueError(f'max_per_sample must be None or an int >= 0, not {max_per_sample!r}')
+        shape = tuple(int(x) for x in self._H.shape)   # [local samples, M * T, *shift]
+        T = self.n_transforms
+        group = {'atom': 1, 'transforms': T, 'all': shape[1]}[suppress]
+        hook = getattr(self._backend, 'find_peaks', None)
+        if hook is not None:
+            idx, val = hook(self._H, float(threshold), radius, group)
+        else:
+            idx, val = find_peaks_numpy(self._backend.to_ndarray(self._H), float(threshold), radius, group)
+        at = np.unravel_index(np.asarray(idx, dtype=np.int64), shape)
+        sample = at[0].astype(np.int64)
+        if self._shuffle_idx is not None:
+            # (the H property shows internal sample a[i] at place i, a = argsort(shuffle): undo it, keep the C order)
+            place = np.empty(shape[0], dtype=np.int64)
+            place[np.argsort(self._shuffle_idx)] = np.arange(shape[0])
+            sample = place[sample]
+            order = np.argsort(sample, kind='stable')
+            sample, val, at = sample[order], val[order], tuple(a[order] for a in at)
+        if max_per_sample is not None:
+            # each sample's strongest first, ties in C order; the survivors stay in C order
+            by_strength = np.lexsort((np.arange(len(val)), -val.astype(np.float64), sample))
+            first = np.searchsorted(sample, sample[by_strength], side='left')   # (sample is ascending)
+            keep = np.sort(by_strength[np.arange(len(val)) - first < max_per_sample])
+            sample, val, at = sample[keep], val[keep], tuple(a[keep] for a in at)
+        sample = sample + int(getattr(self._backend, 'shard', (0, 0))[0])
+        shift = np.stack([a.astype(np.int64) for a in at[2:]], axis=1).reshape(len(val), k)
+        mode = getattr(self._backend, '_reconstruction_mode', 'valid')
+        offset = np.array([a - 1 if mode == 'valid' else 0 for a in self.atom_shape], dtype=np.int64)
+        return Detections(sample=sample, atom=(at[1] // T).astype(np.int64), transform=(at[1] % T).astype(np.int64),
+                          shift=shift, origin=shift - offset, strength=val)
 
     def sample_objective(self) -> np.ndarray:
         """[N] float64: each sample's share of ``objective()``, in the order of ``V`` (with a process group: this rank's

@@ -30,6 +30,7 @@ EXPORTS = (
     'tnmf_hip_atom_ops_create', 'tnmf_hip_atom_ops_destroy', 'tnmf_hip_ops_expand_W', 'tnmf_hip_ops_fold_grad_W',
     'tnmf_hip_ops_apply_W',
     'tnmf_hip_ctx_set_objective_tap', 'tnmf_hip_sample_objective',
+    'tnmf_hip_find_peaks',
 )
 
 MODES = {'valid': 0, 'full': 1, 'circular': 2, 'reflect': 3}
@@ -55,6 +56,7 @@ class Op(ctypes.Structure):
 
 OP_UPDATE_H, OP_GRAD_W, OP_APPLY_W = 0, 1, 2
 
+E_GEOM = -2
 E_UNSUPPORTED = -5
 E_STRIDE = -6   # TNMF_E_STRIDE: the kernel family of this call wants C-contiguous H
 
@@ -139,6 +141,7 @@ def load() -> ctypes.CDLL:
     lib.tnmf_hip_ops_apply_W.argtypes = [vp, gp, vp, vp, vp, vp, cd, vp]
     lib.tnmf_hip_ctx_set_objective_tap.argtypes = [vp, vp]
     lib.tnmf_hip_sample_objective.argtypes = [vp, gp, cd, cd, vp, vp, vp, vp, vp, vp]
+    lib.tnmf_hip_find_peaks.argtypes = [vp, gp, vp, cd, pi, ci, vp, vp, sz, vp, vp]
     lib.tnmf_hip_pad_H.argtypes = [vp, gp, ci, vp, vp, vp]
     lib.tnmf_hip_fold_H.argtypes = [vp, gp, ci, vp, vp, vp]
     for name in EXPORTS:

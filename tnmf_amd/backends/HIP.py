@@ -770,6 +770,42 @@ class HIP_Backend(Backend):
             self._stream()), 'tnmf_hip_sample_objective'))
         return out.cpu().numpy()
 
+    # -- detections -----------------------------------------------------------------------------------------------------
+    # The peaks of H are found and compacted on the device (include/tnmf_hip.h, "detections"): only the list of
+    # (index, value) pairs crosses to the host, never H.
+    supports_peaks = True
+
+    def find_peaks(self, H: torch.Tensor, threshold: float, radius: Sequence[int], group: int = 1,
+                   capacity: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """(idx, val): the flat C-order indices in H's shape [n, P, *S], ascending, and the values of the detections of H
+        -- the resident activations, a mini-batch view H[s] of them, row-padded or not -> tnmf_hip_find_peaks.  The list is
+        sized by a guess (``capacity``; default: 1/256 of H); when the kernel counts more, it runs once more with the
+        exact size.  Sorted by index on the device."""
+        k = len(self.atom_shape)
+        assert H.is_cuda and H.dtype == self._torch_dtype and H.dim() == 2 + k and len(radius) == k
+        ld = self._row_stride(H)
+        if ld is None:
+            H, ld = H.contiguous(), 0
+        n, P = int(H.shape[0]), int(H.shape[1])
+        # (the shift shape is H's own, whatever the reconstruction mode: D = S, A = 1)
+        g = _lib.make_geom(n, P, self.n_channels, tuple(H.shape[2:]), (1,) * k, self._dtype_code, ld)
+        rad = (ctypes.c_int * 3)(*[min(int(r), 2 ** 31 - 1) for r in radius])
+        count = torch.zeros(1, dtype=torch.int64, device=self._device)
+        cap = max(4096, H.numel() // 256) if capacity is None else int(capacity)
+        while True:
+            idx = torch.empty(cap, dtype=torch.int64, device=self._device)
+            val = torch.empty(cap, dtype=self._torch_dtype, device=self._device)
+            with self._timed('find_peaks'):
+                _lib.check(self._lib.tnmf_hip_find_peaks(self._ctx, ctypes.byref(g), _ptr(H), float(threshold), rad,
+                                                         int(group), _ptr(idx), _ptr(val), cap, _ptr(count),
+                                                         self._stream()), 'tnmf_hip_find_peaks')
+            total = int(count.item())
+            if total <= cap:
+                break
+            cap = total
+        idx, order = torch.sort(idx[:total])
+        return idx.cpu().numpy(), val[:total][order].cpu().numpy()
+
     # -- a whole mini-batch epoch in one call -------------------------------------------------------------------
     @property
     def supports_schedules(self) -> bool:

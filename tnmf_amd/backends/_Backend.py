@@ -31,6 +31,9 @@ takes an ``AtomOperators`` (tnmf_amd/transforms.py) wherever those hooks take a 
 objective_out=buf)`` -- passed only on the iterations that record; the step's slice selects the part written, with each
 sample's objective at the (W, H) passed in -- and ``read_objective(buf) -> float``, the only call that waits: the sum in
 sample order, over all ranks.  ``sample_objective(V, W, H, beta, eps)`` -> one float64 per local sample, host side.
+A backend that declares ``supports_peaks`` offers ``find_peaks(H, threshold, radius, group) -> (idx, val)``: the ascending
+flat C-order indices (int64, host) in H's shape [n, P, *S] and the values of the detections of its native H
+(include/tnmf_hip.h, "detections"); without it ``detections()`` searches ``to_ndarray(H)`` on the host.
 """
 import abc
 from typing import Optional, Sequence, Tuple, Union
@@ -61,6 +64,8 @@ class Backend(abc.ABC):
     supports_atom_operators = False
     # fused_update_H takes ``objective_out`` (with new_objective_buffer / read_objective): the objective tap
     supports_objective_tap = False
+    # offers ``find_peaks``: the detections are found where H lives
+    supports_peaks = False
 
     def __init__(self, reconstruction_mode: str = 'valid'):
         self._reconstruction_mode = reconstruction_mode

@@ -11,6 +11,7 @@
 #include "fft.h"
 #include "generic.h"
 #include "mfma.h"
+#include "peaks.h"
 #include "split.h"
 #include "volume.h"
 
@@ -1311,6 +1312,35 @@ int tnmf_hip_apply_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, void *W_inout
     char *np = static_cast<char *>(negpos);
     const size_t wbytes = (size_t)g.M * g.C * g.Ay * g.Ax * esize(dtype);
     return launch_apply_normalize_W(g, dtype, W_inout, np, np + wbytes, eps, true, s);
+}
+
+int tnmf_hip_find_peaks(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *H, double threshold, const int *radius,
+                        int group, long long *idx_out, void *val_out, size_t capacity, unsigned long long *count_out,
+                        void *stream) {
+    if (!ctx || !geom || !radius) return TNMF_E_NULL;
+    if (geom->dtype != 0 && geom->dtype != 1) return TNMF_E_DTYPE;
+    if (geom->ndim < 1 || geom->ndim > 3 || geom->N < 0 || geom->M <= 0) return TNMF_E_GEOM;
+    int S[3] = {1, 1, 1}, r[3] = {0, 0, 0};   // leading axes of extent 1: one scheme for 1, 2 and 3 shift axes
+    for (int i = 0; i < geom->ndim; ++i) {
+        const int k = 3 - geom->ndim + i;
+        if (geom->D[i] <= 0 || geom->A[i] <= 0 || radius[i] < 0) return TNMF_E_GEOM;
+        S[k] = geom->D[i] + geom->A[i] - 1;
+        r[k] = std::min(radius[i], S[k] - 1);   // (a radius at or beyond the extent: the whole axis)
+    }
+    if (group < 1 || geom->M % group != 0) return TNMF_E_GEOM;
+    if (geom->h_row_stride > 0 && geom->h_row_stride < S[2]) return TNMF_E_GEOM;
+    if (!(threshold >= 0) || (long long)S[0] * S[1] > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
+    if (!count_out || (geom->N > 0 && !H) || (capacity > 0 && (!idx_out || !val_out))) return TNMF_E_NULL;
+    PeakGeo g;
+    g.planes = (long long)geom->N * geom->M;
+    g.P = geom->M;
+    g.Sz = S[0], g.Sy = S[1], g.Sx = S[2];
+    g.Hs = geom->h_row_stride > 0 ? geom->h_row_stride : S[2];
+    g.rz = r[0], g.ry = r[1], g.rx = r[2];
+    g.group = group;
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return peaks_find(ctx, g, geom->dtype, H, threshold, idx_out, val_out, capacity, count_out,
+                      static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"
