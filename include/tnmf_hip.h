@@ -477,6 +477,63 @@ int tnmf_hip_find_peaks(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void
                         int group, long long *idx_out, void *val_out, size_t capacity, unsigned long long *count_out,
                         void *stream);
 
+/* ---- events: render and refit a list of detections (ABI 8, additive: the version stays 8) -----------------------------
+ * The H side with the activations held as a list.  An EVENT is (n, p, u, h): local sample n, plane p of the effective
+ * dictionary W_eff[P, C, *A] (P = geom->M; with transforms p = atom * T + transform), shift index u in the activations of
+ * the reconstruction mode (shift shape S, "reconstruction modes" above), strength h, finite and >= 0.  geom describes the
+ * samples as everywhere (N, C, D, A, dtype; h_row_stride is not read): 1 or 2 shift axes, float32 or float64.
+ * Every mode is a 'valid' reconstruction of padded activations, so an entry at padded position q adds h * W_eff[p, c, j]
+ * to R[n, c, q - (A - 1) + j], 0 <= j < A, wherever that lies inside the sample.  An event stands for its IMAGES in the
+ * padded frame [D + A - 1]; per shift axis, with a the atom extent and S the shift extent:
+ *   valid      q = u
+ *   full       q = u + a - 1
+ *   circular   q = u + a - 1, and also q = u - (S - (a - 1)) when u >= S - (a - 1)
+ *   reflect    q = u + a - 1, and also q = (a - 1) - u when 1 <= u <= a - 1
+ * (the padding table read backwards).  The images of an event are the Cartesian product over the axes: at most 2^ndim.
+ *
+ * tnmf_hip_events_render: R[N, C, *D] = the sum over all images of strength[event] * W_eff[plane], placed as above.  It
+ * is a gather without atomics -- the same list gives the same bits run after run, duplicates add up -- and writes every
+ * element of R exactly once, zeros included: R needs no initialisation and is never read.  THE IMAGE LIST is the caller's
+ * to build, once per support (only the strengths change between the steps of a refit):
+ *   - cells of TNMF_EVENTS_CELL_1D padded positions (ndim == 1), TNMF_EVENTS_CELL_2D x TNMF_EVENTS_CELL_2D (ndim == 2)
+ *     tile the padded frame, nc[i] = ceil((D[i] + A[i] - 1) / cell) per axis; the cell of an image at q is q / cell per
+ *     axis, its key (n * nc[0] + cell_0) * nc[1] + cell_1 (ndim == 1: n * nc[0] + cell_0);
+ *   - images: n_images rows of four ints (plane, q_0, q_1, event) (ndim == 1: (plane, 0, q_0, event)), `event` the index
+ *     into `strength` [n_events], sorted by ascending key; the order inside a cell is free and fixes the order of the
+ *     additions;
+ *   - cell_start: N * nc[0] * nc[1] + 1 ints, cell_start[key] = the first row of that key (the rows of a key end where
+ *     the next begins), cell_start[last] = n_images -- a searchsorted of 0 .. number of keys in the sorted keys.
+ *   The list lives on the device, so its CONTENTS cannot be refused by an asynchronous call: a row whose plane or event is
+ *   out of range is skipped and cell_start is clamped to [0, n_images] -- nothing is read or written out of bounds -- and
+ *   a row filed under the wrong key is simply not seen by the tiles it belongs to.  Workspace: none.
+ *
+ * tnmf_hip_events_update: one multiplicative update of the strengths against V, given R = the render of the same
+ * strengths: with neg_e = sum over the images of event e, the channels c and the atom entries j of V[n, c, x] *
+ * W_eff[p, c, j] over the in-sample pixels x, and pos_e the same sum with R,
+ *   strength[e] <- strength[e] * neg_e / (pos_e + eps + sparsity)
+ * -- the dense Frobenius H half step without inhibition (tnmf_hip_update_H_ex) on activations that are zero off the
+ * support, read at the support; a strength of 0 stays 0.  It needs the events distinct in (n, p, u).  events: n_events
+ * rows of four ints (n, p, u_0, u_1) (ndim == 1: (n, p, 0, u_0)) in the order of `strength`; the images are derived from
+ * them by the table above.  The sums are taken in double in a fixed order (deterministic) and the quotient is rounded
+ * once to the element type.  It reads R and writes the n_events strengths, nothing else; a row whose sample, plane or
+ * shift is out of range is skipped.
+ *
+ * Both are asynchronous.  Refused before anything is written: TNMF_E_NULL (ctx, geom, an operand the sizes make
+ * necessary; `images` / `strength` may be NULL when n_images == 0, and everything of the update when n_events == 0),
+ * TNMF_E_DTYPE, TNMF_E_UNSUPPORTED for volumes (ndim == 3), for more than 2^31 - 1 images or events and for an eps or
+ * sparsity that is negative or NaN, TNMF_E_GEOM for any other ndim, sizes <= 0, negative counts, an unknown mode and the
+ * per-axis limits of the mode ("reconstruction modes" above). */
+#define TNMF_EVENTS_CELL_1D 256
+#define TNMF_EVENTS_CELL_2D 16
+
+int tnmf_hip_events_render(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *W_eff, const int *images,
+                           long long n_images, const int *cell_start, const void *strength, long long n_events, void *R,
+                           void *stream);
+
+int tnmf_hip_events_update(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,
+                           void *strength_inout, long long n_events, const void *V, const void *R, double eps,
+                           double sparsity, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,8 @@ Front end of the MI355X shift-invariant NMF: the multiplicative-update schedules
 Public surface = the reference's (tnmf/TransformInvariantNMF.py): ``TransformInvariantNMF(n_atoms, atom_shape,
 inhibition_range, backend, logger, verbose, **backend_kwargs)`` with ``fit`` / ``fit_batch`` / ``fit_minibatches`` /
 ``fit_stream``, the read-outs ``W``, ``H``, ``V``, ``R``, ``R_partial(i)`` and the ``MiniBatchAlgorithm`` enum; beyond it
-``detections()`` (-> ``Detections``), the events read off ``H``.
+``detections()`` (-> ``Detections``), the events read off ``H``, and ``reconstruct_detections`` / ``refit_detections``,
+what such a list explains and its strengths refitted on the fixed support.
 The only backend shipped is ``'hip'`` (tnmf_amd/backends/HIP.py); any object implementing
 tnmf_amd.backends._Backend.Backend can be passed instead of a name.
 
@@ -150,6 +151,66 @@ def find_peaks_numpy(H: np.ndarray, threshold: float, radius: Tuple[int, ...], g
         keep[i] = not np.any(ties < f)
     idx = candidates[keep].astype(np.int64)
     return idx, flat[idx]
+
+
+def event_images(shift: np.ndarray, atom_shape: Tuple[int, ...], shift_shape: Tuple[int, ...], mode: str):
+    """(event [I], q [I, k]): the images of the events with shifts ``shift[K, k]`` in the padded activation frame
+    ``[D + A - 1]`` of a reconstruction mode -- the table of include/tnmf_hip.h, "events": per axis one position, and a
+    second one for a 'circular' shift in the wrap zone or a 'reflect' shift in the mirror zone; over the axes their
+    Cartesian product."""
+    shift = np.asarray(shift, dtype=np.int64).reshape(-1, len(atom_shape))
+    event, q = np.arange(len(shift), dtype=np.int64), np.empty((len(shift), 0), dtype=np.int64)
+    for i, (a, s) in enumerate(zip(atom_shape, shift_shape)):
+        u = shift[event, i]
+        first = u if mode == 'valid' else u + (a - 1)
+        if mode == 'circular':
+            more, second = np.flatnonzero(u >= s - (a - 1)), u - (s - (a - 1))
+        elif mode == 'reflect':
+            more, second = np.flatnonzero((u >= 1) & (u <= a - 1)), (a - 1) - u
+        else:
+            more, second = np.zeros(0, dtype=np.int64), u
+        q = np.concatenate([np.column_stack([q, first]), np.column_stack([q[more], second[more]])])
+        event = np.concatenate([event, event[more]])
+    return event, q
+
+
+def events_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], n_samples: int, mode: str, sample, plane, shift, strength,
+                 V: Optional[np.ndarray] = None, n_iterations: int = 0, sparsity: float = 0., eps: float = 1e-9):
+    """Events on the host, for backends without ``render_events`` / ``refit_events``: the semantics of
+    tnmf_hip_events_render / tnmf_hip_events_update (include/tnmf_hip.h, "events"), one loop over the images.  Without ``V``:
+    R ``[n_samples, C, *D]``, the render of the events (sample, plane of ``W[P, C, *A]``, shift, strength).  With ``V``
+    (the samples, ``[n_samples, C, *D]``): the strengths after ``n_iterations`` multiplicative updates on the fixed
+    support.  Not on the hip path."""
+    A, D = tuple(W.shape[2:]), tuple(sample_shape)
+    shift_shape = tuple(d + a - 1 if mode == 'valid' else d - a + 1 if mode == 'full' else d for d, a in zip(D, A))
+    h = np.array(strength, dtype=W.dtype).reshape(-1)
+    event, q = event_images(shift, A, shift_shape, mode)
+    placed = []   # per image: (event, where in the sample, the atom clipped to it)
+    for e, at in zip(event, q):
+        origin = [int(x) - (a - 1) for x, a in zip(at, A)]
+        lo = [max(o, 0) for o in origin]
+        hi = [min(o + a, d) for o, a, d in zip(origin, A, D)]
+        if all(b > a for a, b in zip(lo, hi)):
+            where = (int(sample[e]), slice(None)) + tuple(slice(a, b) for a, b in zip(lo, hi))
+            atom = W[(int(plane[e]), slice(None)) + tuple(slice(a - o, b - o) for a, b, o in zip(lo, hi, origin))]
+            placed.append((int(e), where, atom))
+
+    def render():
+        R = np.zeros((n_samples, W.shape[1]) + D, dtype=W.dtype)
+        for e, where, atom in placed:
+            R[where] += h[e] * atom
+        return R
+    if V is None:
+        return render()
+    reg = eps + (sparsity if sparsity > 0 else 0.)
+    for _ in range(n_iterations):
+        R = render()
+        neg, pos = np.zeros(len(h), dtype=W.dtype), np.zeros(len(h), dtype=W.dtype)
+        for e, where, atom in placed:
+            neg[e] += np.sum(atom * V[where])
+            pos[e] += np.sum(atom * R[where])
+        h = h * neg / (pos + reg)
+    return h
 
 
 class TransformInvariantNMF:
@@ -404,6 +465,94 @@ class TransformInvariantNMF:
         offset = np.array([a - 1 if mode == 'valid' else 0 for a in self.atom_shape], dtype=np.int64)
         return Detections(sample=sample, atom=(at[1] // T).astype(np.int64), transform=(at[1] % T).astype(np.int64),
                           shift=shift, origin=shift - offset, strength=val)
+
+    # -- detections rendered and refitted -------------------------------------------------------------------------------
+    def _events_of(self, det, distinct: bool):
+        """The events of ``det`` in the backend's terms -- (internal local sample, plane of the effective dictionary, shift,
+        strength in the model's element type) -- after the checks: the inverse of what ``detections()`` applies to the
+        sample (shard offset, shuffle) and to the plane (atom * T + transform)."""
+        if self._H is None:
+            raise RuntimeError('the detections of a model need a fitted model: call fit first')
+        k = len(self.atom_shape)
+        if k == 3:
+            raise NotImplementedError('detections are rendered and refitted on 1 or 2 shift axes, not volumes')
+        shape = tuple(int(x) for x in self._H.shape)   # [local samples, M * T, *shift]
+        T = self.n_transforms
+        cols = [np.asarray(getattr(det, name)) for name in ('sample', 'atom', 'transform', 'shift', 'strength')]
+        K = len(cols[0])
+        for name, c in zip(('sample', 'atom', 'transform', 'shift'), cols):
+            if c.dtype.kind not in 'iu':
+                raise ValueError(f'detections: {name} must hold integers, not {c.dtype}')
+        sample, atom, transform = (c.astype(np.int64).reshape(-1) for c in cols[:3])
+        if cols[3].size != K * k or len(atom) != K or len(transform) != K or cols[4].size != K:
+            raise ValueError('detections: one row per detection in sample, atom, transform, shift and strength')
+        shift = cols[3].astype(np.int64).reshape(K, k)
+        if cols[4].dtype.kind not in 'iuf':
+            raise ValueError(f'detections: strength must hold real numbers, not {cols[4].dtype}')
+        with np.errstate(over='ignore'):
+            strength = cols[4].reshape(-1).astype(self._V.dtype)
+        n0 = int(getattr(self._backend, 'shard', (0, 0))[0])
+        local = sample - n0
+        if np.any((local < 0) | (local >= shape[0])):
+            raise ValueError(f'detections: samples outside the samples [{n0}, {n0 + shape[0]}) of this model (rank)')
+        if np.any((atom < 0) | (atom >= self.n_atoms)) or np.any((transform < 0) | (transform >= T)):
+            raise ValueError(f'detections: atoms outside [0, {self.n_atoms}) or transforms outside [0, {T})')
+        if np.any((shift < 0) | (shift >= np.asarray(shape[2:], dtype=np.int64))):
+            raise ValueError(f'detections: shifts outside the shift shape {shape[2:]}')
+        if not np.all(np.isfinite(strength)) or np.any(strength < 0):
+            raise ValueError('detections: strengths must be finite and >= 0')
+        if distinct and K and len(np.unique(np.column_stack([sample, atom, transform, shift]), axis=0)) != K:
+            raise ValueError('detections: a refit needs distinct (sample, atom, transform, shift)')
+        if self._shuffle_idx is not None:
+            local = np.argsort(self._shuffle_idx)[local]   # (the H property shows internal sample a[i] at place i)
+        return local, atom * T + transform, shift, strength
+
+    def _local_V(self) -> np.ndarray:
+        """This rank's samples on the host, in the backend's order."""
+        n0, n = int(getattr(self._backend, 'shard', (0, 0))[0]), int(self._H.shape[0])
+        return self._V if len(self._V) == n else self._V[n0:n0 + n]
+
+    def reconstruct_detections(self, det) -> np.ndarray:
+        """What the detections ``det`` (a ``Detections``, or any object with its sample, atom, transform, shift and
+        strength) explain: the reconstruction of the activations that hold the strengths at the detections and zero
+        elsewhere, in the order and shape of ``R``.  Duplicate rows add up.  On a backend with ``render_events`` the list is
+        rendered on the device, without a dense H; any other backend's is rendered on the host."""
+        sample, plane, shift, strength = self._events_of(det, distinct=False)
+        hook = getattr(self._backend, 'render_events', None)
+        if hook is not None:
+            return self._backend.to_ndarray(hook(self._W_dict, sample, plane, shift, strength))
+        return events_numpy(self._backend.to_ndarray(self._W_dict), self._V.shape[2:], int(self._H.shape[0]),
+                            getattr(self._backend, '_reconstruction_mode', 'valid'), sample, plane, shift, strength)
+
+    def refit_detections(self, det, n_iterations: int = 50, sparsity_H: float = 0.) -> Detections:
+        """The detections with their strengths refitted: ``n_iterations`` multiplicative updates of the strengths alone, on
+        the fixed support ``det`` and the fixed dictionary, against the model's own V -- the H half step without
+        inhibition on activations that are zero off the support.  It removes the shrinkage the strengths carry from a fit
+        under ``sparsity_H`` or inhibition (and from the sub-threshold activations ``detections()`` dropped).  The rows must
+        be distinct; a strength of 0 stays 0.  The plain Frobenius objective only."""
+        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
+            raise NotImplementedError('refit_detections covers the plain Frobenius objective (beta_loss 2, no weights)')
+        if (isinstance(n_iterations, (bool, np.bool_)) or not isinstance(n_iterations, numbers.Integral)
+                or n_iterations < 0):
+            raise ValueError(f'n_iterations must be an int >= 0, not {n_iterations!r}')
+        if (isinstance(sparsity_H, (bool, np.bool_)) or not isinstance(sparsity_H, numbers.Real)
+                or not math.isfinite(sparsity_H) or sparsity_H < 0):
+            raise ValueError(f'sparsity_H must be a finite number >= 0, not {sparsity_H!r}')
+        sample, plane, shift, strength = self._events_of(det, distinct=True)
+        hook = getattr(self._backend, 'refit_events', None)
+        if hook is not None:
+            new = self._backend.to_ndarray(hook(self._V, self._W_dict, sample, plane, shift, strength, int(n_iterations),
+                                                sparsity=float(sparsity_H), eps=self.eps))
+        else:
+            new = events_numpy(self._backend.to_ndarray(self._W_dict), self._V.shape[2:], int(self._H.shape[0]),
+                               getattr(self._backend, '_reconstruction_mode', 'valid'), sample, plane, shift, strength,
+                               V=self._local_V(), n_iterations=int(n_iterations), sparsity=float(sparsity_H),
+                               eps=self.eps)
+        mode = getattr(self._backend, '_reconstruction_mode', 'valid')
+        offset = np.array([a - 1 if mode == 'valid' else 0 for a in self.atom_shape], dtype=np.int64)
+        as_rows = lambda x: np.asarray(x).astype(np.int64).reshape(len(new))   # noqa: E731
+        return Detections(sample=as_rows(det.sample), atom=as_rows(det.atom), transform=as_rows(det.transform),
+                          shift=shift, origin=shift - offset, strength=new)
 
     def sample_objective(self) -> np.ndarray:
         """[N] float64: each sample's share of ``objective()``, in the order of ``V`` (with a process group: this rank's

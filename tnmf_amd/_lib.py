@@ -31,12 +31,16 @@ EXPORTS = (
     'tnmf_hip_ops_apply_W',
     'tnmf_hip_ctx_set_objective_tap', 'tnmf_hip_sample_objective',
     'tnmf_hip_find_peaks',
+    'tnmf_hip_events_render', 'tnmf_hip_events_update',
 )
 
 MODES = {'valid': 0, 'full': 1, 'circular': 2, 'reflect': 3}
 
 # transform groups (TNMF_GROUP_*): name -> id; tnmf_amd/transforms.py defines them
 GROUPS = {'flip': 0, 'mirrors': 1, 'rot90': 2, 'dihedral': 3}
+
+# the cell (= output tile) of tnmf_hip_events_render per number of shift axes: TNMF_EVENTS_CELL_*
+EVENT_CELLS = {1: (256,), 2: (16, 16)}
 
 PATHS = {'auto': 0, 'generic': 1, 'mfma': 2, 'fft': 3, 'hybrid': 4, 'split': 5}
 
@@ -142,6 +146,9 @@ def load() -> ctypes.CDLL:
     lib.tnmf_hip_ctx_set_objective_tap.argtypes = [vp, vp]
     lib.tnmf_hip_sample_objective.argtypes = [vp, gp, cd, cd, vp, vp, vp, vp, vp, vp]
     lib.tnmf_hip_find_peaks.argtypes = [vp, gp, vp, cd, pi, ci, vp, vp, sz, vp, vp]
+    ll = ctypes.c_longlong
+    lib.tnmf_hip_events_render.argtypes = [vp, gp, vp, vp, ll, vp, vp, ll, vp, vp]
+    lib.tnmf_hip_events_update.argtypes = [vp, gp, ci, vp, vp, vp, ll, vp, vp, cd, cd, vp]
     lib.tnmf_hip_pad_H.argtypes = [vp, gp, ci, vp, vp, vp]
     lib.tnmf_hip_fold_H.argtypes = [vp, gp, ci, vp, vp, vp]
     for name in EXPORTS:

@@ -12,6 +12,7 @@ backend reproduces) and tnmf/backends/_Backend.py (the interface).
 from typing import Optional, Sequence, Tuple
 
 import ctypes
+import itertools
 import weakref
 
 import numpy as np
@@ -805,6 +806,147 @@ class HIP_Backend(Backend):
             cap = total
         idx, order = torch.sort(idx[:total])
         return idx.cpu().numpy(), val[:total][order].cpu().numpy()
+
+    # -- events: the detections rendered and refitted --------------------------------------------------------------------
+    # The H side on a list of events (include/tnmf_hip.h, "events"): no buffer of H's size exists on this path.  The
+    # support is fixed over a refit, so the sorted image list and the cell offsets are built once (event_list); only the
+    # strengths change between the steps.
+    supports_events = True
+
+    def _check_events(self, n_planes: int, sample, plane, shift, strength):
+        """-> (sample [K], plane [K], shift [K, k], strength [K]) on the device, checked against this rank's samples, the
+        planes of the dictionary and the shift shape of the mode: ValueError for anything out of range, for a strength that
+        is negative or not finite; NotImplementedError for volumes."""
+        k = len(self.atom_shape)
+        if k == 3:
+            raise NotImplementedError('events: 1 or 2 shift axes only')
+
+        def dev(x, dtype):
+            t = x.to(self._device) if isinstance(x, torch.Tensor) else torch.tensor(np.asarray(x), device=self._device)
+            if dtype is torch.int64 and (t.dtype.is_floating_point or t.dtype == torch.bool):
+                raise ValueError('events: sample, plane and shift must be integers')
+            return t.to(dtype)
+        sample, plane = dev(sample, torch.int64).reshape(-1), dev(plane, torch.int64).reshape(-1)
+        K = sample.numel()
+        shift = dev(shift, torch.int64).reshape(K, k)
+        strength = dev(strength, self._torch_dtype).reshape(-1).contiguous()
+        if plane.numel() != K or strength.numel() != K:
+            raise ValueError('events: sample, plane, shift and strength must have one row per event')
+        if K:
+            S = torch.tensor(self._transform_shape, dtype=torch.int64, device=self._device)
+            bad = torch.stack([((sample < 0) | (sample >= self.n_local_samples)).any(),
+                               ((plane < 0) | (plane >= n_planes)).any(), ((shift < 0) | (shift >= S)).any(),
+                               (~torch.isfinite(strength) | (strength < 0)).any()]).tolist()
+            for flag, what in zip(bad, (f'samples outside [0, {self.n_local_samples})', f'planes outside [0, {n_planes})',
+                                        f'shifts outside the shift shape {self._transform_shape}',
+                                        'strengths that are negative or not finite')):
+                if flag:
+                    raise ValueError(f'events: {what}')
+        return sample, plane, shift, strength
+
+    def event_list(self, sample: torch.Tensor, plane: torch.Tensor, shift: torch.Tensor):
+        """The lists tnmf_hip_events_render / _update take, built on the device for checked events (_check_events):
+        (images [I, 4] int32 sorted by (sample, cell), cell_start [cells + 1] int32, events [K, 4] int32).  The images of
+        an event per shift axis are the header's table; a stable sort keeps, inside a cell, the order image combination,
+        then event."""
+        k = len(self.atom_shape)
+        K = sample.numel()
+        mode = self._reconstruction_mode
+        with self._timed('event_list'):
+            per_axis = []
+            for i, (a, s) in enumerate(zip(self.atom_shape, self._transform_shape)):
+                u = shift[:, i]
+                if mode == 'valid':
+                    per_axis.append([(u, None)])
+                elif mode == 'circular':
+                    per_axis.append([(u + (a - 1), None), (u - (s - (a - 1)), u >= s - (a - 1))])
+                elif mode == 'reflect':
+                    per_axis.append([(u + (a - 1), None), ((a - 1) - u, (u >= 1) & (u <= a - 1))])
+                else:
+                    per_axis.append([(u + (a - 1), None)])
+            every = torch.arange(K, dtype=torch.int64, device=self._device)
+            es, qs = [], []
+            for combo in itertools.product(*per_axis):
+                q = torch.stack([c[0] for c in combo], dim=1)
+                masks = [c[1] for c in combo if c[1] is not None]
+                if not masks:
+                    es.append(every)
+                    qs.append(q)
+                    continue
+                sel = torch.nonzero(masks[0] if len(masks) == 1 else masks[0] & masks[1]).reshape(-1)
+                es.append(sel)
+                qs.append(q[sel])
+            e, q = torch.cat(es), torch.cat(qs)
+            cells = _lib.EVENT_CELLS[k]
+            nc = [-(-(d + a - 1) // c) for d, a, c in zip(self._sample_shape, self.atom_shape, cells)]
+            n_keys = self.n_local_samples * int(np.prod(nc))
+            if e.numel() >= 2 ** 31 or n_keys >= 2 ** 31 - 1:
+                raise NotImplementedError('events: more than 2^31 - 1 images or cells')
+            key = sample[e]
+            for i in range(k):
+                key = key * nc[i] + torch.div(q[:, i], cells[i], rounding_mode='floor')
+            key, order = torch.sort(key, stable=True)
+            e, q = e[order], q[order]
+            zero = torch.zeros_like(e)
+            images = torch.stack([plane[e], q[:, 0] if k == 2 else zero, q[:, -1], e], dim=1).to(torch.int32).contiguous()
+            cell_start = torch.searchsorted(key, torch.arange(n_keys + 1, dtype=torch.int64, device=self._device)
+                                            ).to(torch.int32).contiguous()
+            zero = torch.zeros_like(sample)
+            events = torch.stack([sample, plane, shift[:, 0] if k == 2 else zero, shift[:, -1]],
+                                 dim=1).to(torch.int32).contiguous()
+        return images, cell_start, events
+
+    def render_event_list(self, W: torch.Tensor, images: torch.Tensor, cell_start: torch.Tensor, strength: torch.Tensor,
+                          R: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """R[n_local, C, *D] of the image list (event_list) and the strengths -> tnmf_hip_events_render (into R when
+        given: every element is written)."""
+        self._check_W(W)
+        assert strength.is_cuda and strength.is_contiguous() and strength.dtype == self._torch_dtype
+        shape = (self.n_local_samples, self.n_channels) + self._sample_shape
+        if R is None:
+            R = torch.empty(shape, dtype=self._torch_dtype, device=self._device)
+        assert R.is_contiguous() and tuple(R.shape) == shape and R.dtype == self._torch_dtype
+        with self._timed('events_render'):
+            _lib.check(self._lib.tnmf_hip_events_render(
+                self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0])), _ptr(W), _ptr(images),
+                images.shape[0], _ptr(cell_start), _ptr(strength), strength.numel(), _ptr(R), self._stream()),
+                'tnmf_hip_events_render')
+        return R
+
+    def update_event_list(self, W: torch.Tensor, events: torch.Tensor, strength: torch.Tensor, R: torch.Tensor,
+                          sparsity: float = 0., eps: float = 1e-9) -> None:
+        """One multiplicative update of the strengths in place, R being their render -> tnmf_hip_events_update."""
+        self._check_W(W)
+        assert strength.is_contiguous() and strength.dtype == self._torch_dtype and events.shape[0] == strength.numel()
+        with self._timed('events_update'):
+            _lib.check(self._lib.tnmf_hip_events_update(
+                self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0])), self._mode, _ptr(W), _ptr(events),
+                _ptr(strength), strength.numel(), _ptr(self._V_dev), _ptr(R), float(eps), float(sparsity),
+                self._stream()), 'tnmf_hip_events_update')
+
+    def render_events(self, W: torch.Tensor, sample, plane, shift, strength) -> torch.Tensor:
+        """R[n_local, C, *D]: what the events (local sample, plane of W, shift in H of this mode, strength) reconstruct --
+        the reconstruction of the activations that hold the strengths at the events and zero elsewhere, without those
+        activations.  Duplicate events add up."""
+        sample, plane, shift, strength = self._check_events(W.shape[0], sample, plane, shift, strength)
+        images, cell_start, _ = self.event_list(sample, plane, shift)
+        return self.render_event_list(W, images, cell_start, strength)
+
+    def refit_events(self, V, W: torch.Tensor, sample, plane, shift, strength, n_iterations: int, sparsity: float = 0.,
+                     eps: float = 1e-9) -> torch.Tensor:
+        """[K] strengths after ``n_iterations`` multiplicative updates on the fixed support, W fixed, against the resident
+        samples (`V` is the array given to initialize(), as for the other hooks): per step one render and one update.
+        The plain Frobenius objective; the events must be distinct in (sample, plane, shift)."""
+        if self._G_dev is not None:
+            raise NotImplementedError('refit_events is unweighted')
+        sample, plane, shift, strength = self._check_events(W.shape[0], sample, plane, shift, strength)
+        images, cell_start, events = self.event_list(sample, plane, shift)
+        strength = strength.clone()
+        R = torch.empty_like(self._V_dev)
+        for _ in range(int(n_iterations)):
+            self.render_event_list(W, images, cell_start, strength, R)
+            self.update_event_list(W, events, strength, R, sparsity, eps)
+        return strength
 
     # -- a whole mini-batch epoch in one call -------------------------------------------------------------------
     @property

@@ -34,6 +34,11 @@ sample order, over all ranks.  ``sample_objective(V, W, H, beta, eps)`` -> one f
 A backend that declares ``supports_peaks`` offers ``find_peaks(H, threshold, radius, group) -> (idx, val)``: the ascending
 flat C-order indices (int64, host) in H's shape [n, P, *S] and the values of the detections of its native H
 (include/tnmf_hip.h, "detections"); without it ``detections()`` searches ``to_ndarray(H)`` on the host.
+A backend that declares ``supports_events`` works on lists of events (local sample, plane of the effective dictionary,
+shift in its H, strength; include/tnmf_hip.h, "events"): ``render_events(W, sample, plane, shift, strength) -> R``
+(backend-native ``[n_local, C, *D]``) and ``refit_events(V, W, sample, plane, shift, strength, n_iterations, sparsity=0.,
+eps=1e-9) -> strength`` (backend-native ``[K]``); without them ``reconstruct_detections`` / ``refit_detections`` run
+``events_numpy`` on the host.
 """
 import abc
 from typing import Optional, Sequence, Tuple, Union
@@ -66,6 +71,8 @@ class Backend(abc.ABC):
     supports_objective_tap = False
     # offers ``find_peaks``: the detections are found where H lives
     supports_peaks = False
+    # offers ``render_events`` / ``refit_events``: detections are rendered and refitted without a dense H
+    supports_events = False
 
     def __init__(self, reconstruction_mode: str = 'valid'):
         self._reconstruction_mode = reconstruction_mode

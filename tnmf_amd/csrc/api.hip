@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "beta.h"
+#include "events.h"
 #include "fft.h"
 #include "generic.h"
 #include "mfma.h"
@@ -1341,6 +1342,63 @@ int tnmf_hip_find_peaks(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
     return peaks_find(ctx, g, geom->dtype, H, threshold, idx_out, val_out, capacity, count_out,
                       static_cast<hipStream_t>(stream));
+}
+
+// the geometry of the two events entry points, checked: ndim 1 or 2 (3: TNMF_E_UNSUPPORTED), every size positive
+static int events_geo(const tnmf_hip_geom *geom, EventGeo *g) {
+    if (geom->dtype != 0 && geom->dtype != 1) return TNMF_E_DTYPE;
+    if (geom->ndim == 3) return TNMF_E_UNSUPPORTED;
+    if (geom->ndim != 1 && geom->ndim != 2) return TNMF_E_GEOM;
+    if (geom->N < 0 || geom->M <= 0 || geom->C <= 0) return TNMF_E_GEOM;
+    for (int i = 0; i < geom->ndim; ++i)
+        if (geom->D[i] <= 0 || geom->A[i] <= 0) return TNMF_E_GEOM;
+    const bool two = geom->ndim == 2;
+    g->N = geom->N, g->P = geom->M, g->C = geom->C;
+    g->Dy = two ? geom->D[0] : 1, g->Dx = geom->D[two ? 1 : 0];
+    g->Ay = two ? geom->A[0] : 1, g->Ax = geom->A[two ? 1 : 0];
+    if ((long long)g->Dy + g->Ay > 0x7fffffffLL || (long long)g->Dx + g->Ax > 0x7fffffffLL ||
+        (long long)g->C * g->Ay * g->Ax > 0x7fffffffLL)
+        return TNMF_E_UNSUPPORTED;
+    events_tile(geom->ndim, &g->ty, &g->tx);
+    g->ncy = cdiv(g->Dy + g->Ay - 1, g->ty), g->ncx = cdiv(g->Dx + g->Ax - 1, g->tx);
+    return TNMF_OK;
+}
+
+int tnmf_hip_events_render(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *W_eff, const int *images,
+                           long long n_images, const int *cell_start, const void *strength, long long n_events, void *R,
+                           void *stream) {
+    if (!ctx || !geom) return TNMF_E_NULL;
+    EventGeo g;
+    const int rc = events_geo(geom, &g);
+    if (rc != TNMF_OK) return rc;
+    if (n_images < 0 || n_events < 0) return TNMF_E_GEOM;
+    if (n_images > 0x7fffffffLL || n_events > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
+    if (g.N > 0 && (!W_eff || !cell_start || !R || (n_images > 0 && (!images || !strength)))) return TNMF_E_NULL;
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return events_render(ctx, g, geom->dtype, W_eff, images, n_images, cell_start, strength, n_events, R,
+                         static_cast<hipStream_t>(stream));
+}
+
+int tnmf_hip_events_update(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,
+                           void *strength_inout, long long n_events, const void *V, const void *R, double eps,
+                           double sparsity, void *stream) {
+    if (!ctx || !geom) return TNMF_E_NULL;
+    EventGeo g;
+    const int rc = events_geo(geom, &g);
+    if (rc != TNMF_OK) return rc;
+    if (mode < TNMF_MODE_VALID || mode > TNMF_MODE_REFLECT || n_events < 0) return TNMF_E_GEOM;
+    int S[2];
+    const int D[2] = {g.Dy, g.Dx}, A[2] = {g.Ay, g.Ax};
+    for (int i = 0; i < 2; ++i) {   // the limits of "reconstruction modes" above, per axis
+        S[i] = mode == TNMF_MODE_VALID ? D[i] + A[i] - 1 : mode == TNMF_MODE_FULL ? D[i] - A[i] + 1 : D[i];
+        if (S[i] < 1 || (mode == TNMF_MODE_CIRCULAR && A[i] - 1 > S[i]) || (mode == TNMF_MODE_REFLECT && A[i] - 1 >= S[i]))
+            return TNMF_E_GEOM;
+    }
+    if (!(eps >= 0) || !(sparsity >= 0)) return TNMF_E_UNSUPPORTED;
+    if (n_events > 0 && g.N > 0 && (!W_eff || !events || !strength_inout || !V || !R)) return TNMF_E_NULL;
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return events_update(ctx, g, geom->dtype, mode, S[0], S[1], W_eff, events, strength_inout, n_events, V, R,
+                         eps + (sparsity > 0 ? sparsity : 0.), static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

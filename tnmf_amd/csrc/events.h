@@ -1,0 +1,36 @@
+// Events: the sparse H side -- render a list of events into R, refit their strengths (events.hip;
+// tnmf_hip_events_render / tnmf_hip_events_update).
+#pragma once
+
+#include "common.h"
+
+// One index scheme for one and two shift axes (signals run as Dy = Ay = 1).  An image sits at a position (qy, qx) of the
+// padded activation frame [Dy + Ay - 1, Dx + Ax - 1]; cells of ty x tx positions tile that frame, ncy x ncx per sample.
+struct EventGeo {
+    int N, P, C;      // samples, planes of W_eff, channels
+    int Dy, Dx;       // sample shape
+    int Ay, Ax;       // atom shape
+    int ty, tx;       // cell = output tile (ty * tx == kEventThreads)
+    int ncy, ncx;     // cells per sample and axis
+};
+
+constexpr int kEventThreads = 256;
+
+// the cell / tile shape the render works with: 16 x 16 for two shift axes, 1 x 256 for one
+inline void events_tile(int ndim, int *ty, int *tx) {
+    *ty = ndim == 2 ? TNMF_EVENTS_CELL_2D : 1;
+    *tx = ndim == 2 ? TNMF_EVENTS_CELL_2D : TNMF_EVENTS_CELL_1D;
+}
+static_assert(TNMF_EVENTS_CELL_2D * TNMF_EVENTS_CELL_2D == kEventThreads && TNMF_EVENTS_CELL_1D == kEventThreads,
+              "one thread per pixel of a tile");
+
+// R[N,C,Dy,Dx] = the sum over the images of strength[event] * W_eff[plane] placed at their position; every pixel is
+// written exactly once.  images: n_images x (plane, qy, qx, event), sorted by (sample, cell); cell_start: N * ncy * ncx + 1.
+int events_render(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, const void *W, const int *images, long long n_images,
+                  const int *cell_start, const void *strength, long long n_events, void *R, hipStream_t s);
+
+// strength[e] *= neg_e / (pos_e + reg): V and R gathered under every image of event e = (sample, plane, uy, ux) of the
+// reconstruction mode `mode` with shift shape (Sy, Sx).
+int events_update(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const void *W,
+                  const int *events, void *strength, long long n_events, const void *V, const void *R, double reg,
+                  hipStream_t s);
