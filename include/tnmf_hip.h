@@ -477,7 +477,7 @@ int tnmf_hip_find_peaks(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void
                         int group, long long *idx_out, void *val_out, size_t capacity, unsigned long long *count_out,
                         void *stream);
 
-/* ---- events: render and refit a list of detections (ABI 8, additive: the version stays 8) -----------------------------
+/* ---- events: render, refit and learn from a list of detections (ABI 8, additive: the version stays 8) -----------------------------
  * The H side with the activations held as a list.  An EVENT is (n, p, u, h): local sample n, plane p of the effective
  * dictionary W_eff[P, C, *A] (P = geom->M; with transforms p = atom * T + transform), shift index u in the activations of
  * the reconstruction mode (shift shape S, "reconstruction modes" above), strength h, finite and >= 0.  geom describes the
@@ -533,6 +533,41 @@ int tnmf_hip_events_render(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const v
 int tnmf_hip_events_update(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,
                            void *strength_inout, long long n_events, const void *V, const void *R, double eps,
                            double sparsity, void *stream);
+
+/* tnmf_hip_events_grad_W: the W gradient of a list of events -- with the images q of event e = (n, p, u, h_e) per the table
+ * above, for every plane p, channel c and atom entry j (0 <= j < A per axis)
+ *   neg[p, c, j] = sum over the events e of plane p, over their images q, of  h_e * V[n_e, c, q - (A - 1) + j]
+ *   pos[p, c, j] = the same sum with R, the render of the same strengths and the same W_eff
+ * -- pixels outside the sample are skipped, duplicate rows add up: the dense Frobenius W gradient (tnmf_hip_grad_W_fused)
+ * of activations that are zero off the support, so a multiplicative W step on the list is tnmf_hip_apply_W (or a fold of a
+ * transform group first) on this buffer.  negpos_eff: [2, P, C, *A] in the element type, neg first; every element is
+ * written, zeros for a plane without events: it needs no initialisation and is never read.  W_eff itself is not an
+ * operand (R carries it).  No float atomics: the same list gives the same bits run after run, on any device.
+ * THE PLANE LIST is the caller's to build, once per support:
+ *   - events: the n_events rows of four ints (n, p, u_0, u_1) of tnmf_hip_events_update, in the order of `strength`;
+ *   - by_plane: n_events ints, the indices of the rows sorted by ascending plane with a STABLE sort (rows of one plane keep
+ *     their order: it is the order of the additions);
+ *   - plane_start: P + 1 ints, plane_start[p] = the first entry of by_plane of plane p, plane_start[P] = n_events -- a
+ *     searchsorted of 0 .. P in the sorted planes;
+ *   - each plane's run is cut into SEGMENTS of TNMF_EVENTS_SEGMENT entries (the last one shorter), numbered through the
+ *     planes in plane order; a segment is summed in list order in double into one slab of 2 * C * prod(A) doubles, and the
+ *     slabs of a plane are added in segment order in double and rounded once to the element type.  The segment length is a
+ *     constant of this contract, not of the device.
+ *   - workspace: (n_events / TNMF_EVENTS_SEGMENT + P) * 2 * C * prod(A) doubles (integer division; an upper bound of the
+ *     number of segments), uninitialised, the caller's; no other memory is used, and none of H's size.
+ *   As for the image list the CONTENTS cannot be refused: an entry of by_plane outside [0, n_events), a row whose sample or
+ *   shift is out of range or whose plane is not the one it is filed under is skipped, plane_start is clamped to
+ *   [0, n_events] and a run that ends before it begins is empty -- nothing is read or written out of bounds.
+ * Asynchronous.  Refused before anything is written: TNMF_E_NULL (ctx, geom, negpos_eff, and with n_events > 0 and N > 0
+ * every other operand), TNMF_E_DTYPE, TNMF_E_UNSUPPORTED for volumes and for more than 2^31 - 1 events, TNMF_E_GEOM as
+ * for tnmf_hip_events_update. */
+#ifndef TNMF_EVENTS_SEGMENT
+#define TNMF_EVENTS_SEGMENT 64
+#endif
+
+int tnmf_hip_events_grad_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const int *events, const int *by_plane,
+                           const int *plane_start, const void *strength, long long n_events, const void *V, const void *R,
+                           void *workspace, void *negpos_eff, void *stream);
 
 #ifdef __cplusplus
 }

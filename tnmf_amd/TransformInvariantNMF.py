@@ -213,6 +213,64 @@ def events_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], n_samples: int, m
     return h
 
 
+def events_fit_numpy(W: np.ndarray, transforms, sample_shape: Tuple[int, ...], n_samples: int, mode: str, sample, plane,
+                     shift, strength, V: np.ndarray, n_iterations: int, update_H: bool = True, update_W: bool = True,
+                     sparsity: float = 0., eps: float = 1e-9, normalize: Optional[Callable] = None):
+    """Alternating updates of the strengths and of the dictionary on a fixed support, on the host, for backends without
+    ``fit_events``: the strengths' step of ``events_numpy`` and the W gradient of tnmf_hip_events_grad_W (include/tnmf_hip.h,
+    "events"), one loop over the images, folded onto ``W[M, C, *A]`` when ``transforms`` is given (the planes then index
+    the expanded dictionary), MU, and ``normalize(W)`` in place over the atom axes.  An atom whose summed neg is exactly zero
+    keeps its entries.  Returns (W, strengths); the arguments are left as they are.  Not on the hip path."""
+    W = np.array(W)
+    A, D = tuple(W.shape[2:]), tuple(sample_shape)
+    shift_shape = tuple(d + a - 1 if mode == 'valid' else d - a + 1 if mode == 'full' else d for d, a in zip(D, A))
+    h = np.array(strength, dtype=W.dtype).reshape(-1)
+    event, q = event_images(shift, A, shift_shape, mode)
+    placed = []   # per image: (event, where in the sample, which entries of the atom lie there)
+    for e, at in zip(event, q):
+        origin = [int(x) - (a - 1) for x, a in zip(at, A)]
+        lo = [max(o, 0) for o in origin]
+        hi = [min(o + a, d) for o, a, d in zip(origin, A, D)]
+        if all(b > a for a, b in zip(lo, hi)):
+            where = (int(sample[e]), slice(None)) + tuple(slice(a, b) for a, b in zip(lo, hi))
+            entries = (int(plane[e]), slice(None)) + tuple(slice(a - o, b - o) for a, b, o in zip(lo, hi, origin))
+            placed.append((int(e), where, entries))
+    if normalize is None:
+        def normalize(arr):
+            arr /= arr.sum(axis=tuple(range(2, arr.ndim)), keepdims=True)
+
+    def render(W_eff):
+        R = np.zeros((n_samples, W.shape[1]) + D, dtype=W.dtype)
+        for e, where, entries in placed:
+            R[where] += h[e] * W_eff[entries]
+        return R
+    reg = eps + (sparsity if sparsity > 0 else 0.)
+    for _ in range(n_iterations):
+        W_eff = W if transforms is None else _transforms.expand(W, transforms)
+        if update_H:
+            R = render(W_eff)
+            neg, pos = np.zeros(len(h), dtype=W.dtype), np.zeros(len(h), dtype=W.dtype)
+            for e, where, entries in placed:
+                neg[e] += np.sum(W_eff[entries] * V[where])
+                pos[e] += np.sum(W_eff[entries] * R[where])
+            h = h * neg / (pos + reg)
+        if update_W:
+            R = render(W_eff)
+            neg, pos = np.zeros_like(W_eff), np.zeros_like(W_eff)
+            for e, where, entries in placed:
+                neg[entries] += h[e] * V[where]
+                pos[entries] += h[e] * R[where]
+            if transforms is not None:
+                neg, pos = _transforms.fold(neg, transforms), _transforms.fold(pos, transforms)
+            keep = ~neg.reshape(len(W), -1).any(axis=1)      # atoms without evidence
+            new = W * neg / (pos + eps)
+            with np.errstate(invalid='ignore', divide='ignore'):
+                normalize(new)
+            new[keep] = W[keep]
+            W = new
+    return W, h
+
+
 class TransformInvariantNMF:
     r"""
     Shift-invariant non-negative matrix factorisation ``V ~ sum_m H[:, m] (*) W[m]`` by multiplicative updates.
@@ -549,6 +607,53 @@ class TransformInvariantNMF:
                                V=self._local_V(), n_iterations=int(n_iterations), sparsity=float(sparsity_H),
                                eps=self.eps)
         mode = getattr(self._backend, '_reconstruction_mode', 'valid')
+        offset = np.array([a - 1 if mode == 'valid' else 0 for a in self.atom_shape], dtype=np.int64)
+        as_rows = lambda x: np.asarray(x).astype(np.int64).reshape(len(new))   # noqa: E731
+        return Detections(sample=as_rows(det.sample), atom=as_rows(det.atom), transform=as_rows(det.transform),
+                          shift=shift, origin=shift - offset, strength=new)
+
+    def fit_detections(self, det, n_iterations: int = 50, sparsity_H: float = 0., update_H: bool = True,
+                       update_W: bool = True) -> Detections:
+        """Learn from the detections alone: ``n_iterations`` alternating multiplicative updates of the strengths
+        (``update_H``: the step of ``refit_detections``) and of the dictionary (``update_W``: the W half step of a fit on
+        activations that are zero off the support ``det``), against the model's own V -- templates refined from the events,
+        without the sub-threshold activations ``detections()`` dropped.  Updates the model's ``W`` (and
+        ``transformed_atoms``) in place and returns the rows with their refitted strengths.  An atom without evidence --
+        no detections, only zero strengths, or only zero data under them -- keeps its entries.  The dense ``H`` is left
+        as it is: ``R`` and ``objective()`` then describe the NEW W with the OLD dense H; what the detections explain is
+        ``reconstruct_detections`` of the returned rows.  ``update_W=False`` is ``refit_detections``.  The rows must be
+        distinct; the plain Frobenius objective only.  With a process group the call is collective: every rank calls with
+        the detections of its own samples (possibly none) and the same ``n_iterations``."""
+        for name, flag in (('update_H', update_H), ('update_W', update_W)):
+            if not isinstance(flag, (bool, np.bool_)):
+                raise ValueError(f'{name} must be a bool, not {flag!r}')
+        if not update_H and not update_W:
+            raise ValueError('fit_detections: update_H and update_W are both off')
+        if not update_W:
+            return self.refit_detections(det, n_iterations, sparsity_H)
+        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
+            raise NotImplementedError('fit_detections covers the plain Frobenius objective (beta_loss 2, no weights)')
+        if (isinstance(n_iterations, (bool, np.bool_)) or not isinstance(n_iterations, numbers.Integral)
+                or n_iterations < 0):
+            raise ValueError(f'n_iterations must be an int >= 0, not {n_iterations!r}')
+        if (isinstance(sparsity_H, (bool, np.bool_)) or not isinstance(sparsity_H, numbers.Real)
+                or not math.isfinite(sparsity_H) or sparsity_H < 0):
+            raise ValueError(f'sparsity_H must be a finite number >= 0, not {sparsity_H!r}')
+        sample, plane, shift, strength = self._events_of(det, distinct=True)
+        mode = getattr(self._backend, '_reconstruction_mode', 'valid')
+        hook = getattr(self._backend, 'fit_events', None)
+        if hook is not None:
+            new = self._backend.to_ndarray(hook(self._V, self._W, self._W_eff, self._transforms, sample, plane, shift,
+                                                strength, int(n_iterations), update_H=bool(update_H), update_W=True,
+                                                sparsity=float(sparsity_H), eps=self.eps))
+        else:
+            W, new = events_fit_numpy(
+                self._backend.to_ndarray(self._W), self._transforms, self._V.shape[2:], int(self._H.shape[0]), mode, sample,
+                plane, shift, strength, self._local_V(), int(n_iterations), update_H=bool(update_H), update_W=True,
+                sparsity=float(sparsity_H), eps=self.eps,
+                normalize=lambda arr: self._backend.normalize(arr, axis=self._axes_W_normalization))
+            self._W[...] = W
+            self._expand_W()
         offset = np.array([a - 1 if mode == 'valid' else 0 for a in self.atom_shape], dtype=np.int64)
         as_rows = lambda x: np.asarray(x).astype(np.int64).reshape(len(new))   # noqa: E731
         return Detections(sample=as_rows(det.sample), atom=as_rows(det.atom), transform=as_rows(det.transform),

@@ -31,7 +31,7 @@ EXPORTS = (
     'tnmf_hip_ops_apply_W',
     'tnmf_hip_ctx_set_objective_tap', 'tnmf_hip_sample_objective',
     'tnmf_hip_find_peaks',
-    'tnmf_hip_events_render', 'tnmf_hip_events_update',
+    'tnmf_hip_events_render', 'tnmf_hip_events_update', 'tnmf_hip_events_grad_W',
 )
 
 MODES = {'valid': 0, 'full': 1, 'circular': 2, 'reflect': 3}
@@ -41,6 +41,8 @@ GROUPS = {'flip': 0, 'mirrors': 1, 'rot90': 2, 'dihedral': 3}
 
 # the cell (= output tile) of tnmf_hip_events_render per number of shift axes: TNMF_EVENTS_CELL_*
 EVENT_CELLS = {1: (256,), 2: (16, 16)}
+# the events of a plane that tnmf_hip_events_grad_W sums into one slab: TNMF_EVENTS_SEGMENT
+EVENT_SEGMENT = 64
 
 PATHS = {'auto': 0, 'generic': 1, 'mfma': 2, 'fft': 3, 'hybrid': 4, 'split': 5}
 
@@ -149,6 +151,7 @@ def load() -> ctypes.CDLL:
     ll = ctypes.c_longlong
     lib.tnmf_hip_events_render.argtypes = [vp, gp, vp, vp, ll, vp, vp, ll, vp, vp]
     lib.tnmf_hip_events_update.argtypes = [vp, gp, ci, vp, vp, vp, ll, vp, vp, cd, cd, vp]
+    lib.tnmf_hip_events_grad_W.argtypes = [vp, gp, ci, vp, vp, vp, vp, ll, vp, vp, vp, vp, vp]
     lib.tnmf_hip_pad_H.argtypes = [vp, gp, ci, vp, vp, vp]
     lib.tnmf_hip_fold_H.argtypes = [vp, gp, ci, vp, vp, vp]
     for name in EXPORTS:

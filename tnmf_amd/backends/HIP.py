@@ -948,6 +948,84 @@ class HIP_Backend(Backend):
             self.update_event_list(W, events, strength, R, sparsity, eps)
         return strength
 
+    # -- events: the dictionary learnt from the detections ------------------------------------------------------------------
+    def event_plane_list(self, plane: torch.Tensor, n_planes: int):
+        """The plane list tnmf_hip_events_grad_W takes, built on the device for checked events: (by_plane [K] int32, the
+        rows in a stable order of ascending plane; plane_start [n_planes + 1] int32; workspace, the float64 slabs of the
+        segments)."""
+        with self._timed('event_plane_list'):
+            K = plane.numel()
+            sorted_plane, by_plane = torch.sort(plane, stable=True)
+            plane_start = torch.searchsorted(sorted_plane, torch.arange(n_planes + 1, dtype=torch.int64,
+                                                                        device=self._device)).to(torch.int32).contiguous()
+            taps = self.n_channels * int(np.prod(self.atom_shape))
+            workspace = torch.empty((K // _lib.EVENT_SEGMENT + n_planes) * 2 * taps, dtype=torch.float64,
+                                    device=self._device)
+        return by_plane.to(torch.int32).contiguous(), plane_start, workspace
+
+    def gradient_W_event_list(self, W: torch.Tensor, events: torch.Tensor, lists, strength: torch.Tensor,
+                              R: torch.Tensor) -> torch.Tensor:
+        """This rank's [neg | pos] of the W gradient of the events, [2, P, C, *A] for the dictionary ``W[P, C, *A]`` the
+        planes index, R being the render of the same strengths; NOT yet summed over ranks -> tnmf_hip_events_grad_W."""
+        self._check_W(W)
+        by_plane, plane_start, workspace = lists
+        assert strength.is_contiguous() and strength.dtype == self._torch_dtype and events.shape[0] == strength.numel()
+        assert by_plane.numel() == strength.numel() and plane_start.numel() == W.shape[0] + 1
+        assert R.is_contiguous() and R.dtype == self._torch_dtype and tuple(R.shape) == tuple(self._V_dev.shape)
+        negpos = torch.empty((2,) + tuple(W.shape), dtype=W.dtype, device=W.device)
+        with self._timed('events_grad_W'):
+            _lib.check(self._lib.tnmf_hip_events_grad_W(
+                self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0])), self._mode, _ptr(events),
+                _ptr(by_plane), _ptr(plane_start), _ptr(strength), strength.numel(), _ptr(self._V_dev), _ptr(R),
+                _ptr(workspace), _ptr(negpos), self._stream()), 'tnmf_hip_events_grad_W')
+        return negpos
+
+    def update_W_event_list(self, W: torch.Tensor, W_eff: Optional[torch.Tensor], transforms, negpos_eff: torch.Tensor,
+                            eps: float = 1e-9) -> None:
+        """The tail of the dense W half step on the gradient of the events, in place on W (and W_eff): fold, all-reduce,
+        MU + normalise, expand.  An atom without evidence -- its summed neg, folded and all-reduced, is exactly zero in
+        every entry: no events, only zero strengths, or only zero data under them -- keeps its entries, where the dense
+        step would make it 0 / 0; the rule is a select on the device from the all-reduced buffer, the same on every rank."""
+        negpos = negpos_eff if transforms is None else self.fold_gradient_W(negpos_eff, transforms)
+        self._all_reduce(negpos)
+        keep = ~negpos[0].reshape(W.shape[0], -1).any(dim=1)
+        kept = W.clone()
+        if transforms is None:
+            self.apply_W(W, negpos, eps)
+        elif self._world == 1:
+            self.apply_W_transformed(W, W_eff, negpos_eff, transforms, eps)   # (the same bits as apply_W + expand_W)
+        else:
+            self.apply_W(W, negpos, eps)
+        W.copy_(torch.where(keep.reshape((-1,) + (1,) * (W.dim() - 1)), kept, W))
+        if transforms is not None:
+            self.expand_W(W, transforms, W_eff)
+
+    def fit_events(self, V, W: torch.Tensor, W_eff: Optional[torch.Tensor], transforms, sample, plane, shift, strength,
+                   n_iterations: int, update_H: bool = True, update_W: bool = True, sparsity: float = 0.,
+                   eps: float = 1e-9) -> torch.Tensor:
+        """[K] strengths after ``n_iterations`` alternating multiplicative updates on the fixed support: of the strengths
+        (update_H: the step of refit_events) and of the dictionary (update_W: the dense W half step on activations that are
+        zero off the support), W and W_eff updated in place (W_eff is None without transforms).  The plain Frobenius
+        objective.  With a process group the calls are collective: every rank calls with its own events (possibly none) and
+        the same ``n_iterations``."""
+        if self._G_dev is not None:
+            raise NotImplementedError('fit_events is unweighted')
+        D = W if transforms is None else W_eff
+        sample, plane, shift, strength = self._check_events(D.shape[0], sample, plane, shift, strength)
+        images, cell_start, events = self.event_list(sample, plane, shift)
+        lists = self.event_plane_list(plane, D.shape[0]) if update_W else None
+        strength = strength.clone()
+        R = torch.empty_like(self._V_dev)
+        for _ in range(int(n_iterations)):
+            if update_H:
+                self.render_event_list(D, images, cell_start, strength, R)
+                self.update_event_list(D, events, strength, R, sparsity, eps)
+            if update_W:
+                self.render_event_list(D, images, cell_start, strength, R)
+                negpos_eff = self.gradient_W_event_list(D, events, lists, strength, R)
+                self.update_W_event_list(W, W_eff, transforms, negpos_eff, eps)
+        return strength
+
     # -- a whole mini-batch epoch in one call -------------------------------------------------------------------
     @property
     def supports_schedules(self) -> bool:

@@ -1344,7 +1344,7 @@ int tnmf_hip_find_peaks(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void
                       static_cast<hipStream_t>(stream));
 }
 
-// the geometry of the two events entry points, checked: ndim 1 or 2 (3: TNMF_E_UNSUPPORTED), every size positive
+// the geometry of the events entry points, checked: ndim 1 or 2 (3: TNMF_E_UNSUPPORTED), every size positive
 static int events_geo(const tnmf_hip_geom *geom, EventGeo *g) {
     if (geom->dtype != 0 && geom->dtype != 1) return TNMF_E_DTYPE;
     if (geom->ndim == 3) return TNMF_E_UNSUPPORTED;
@@ -1361,6 +1361,18 @@ static int events_geo(const tnmf_hip_geom *geom, EventGeo *g) {
         return TNMF_E_UNSUPPORTED;
     events_tile(geom->ndim, &g->ty, &g->tx);
     g->ncy = cdiv(g->Dy + g->Ay - 1, g->ty), g->ncx = cdiv(g->Dx + g->Ax - 1, g->tx);
+    return TNMF_OK;
+}
+
+// the shift shape of a reconstruction mode, checked against the limits of "reconstruction modes" above, per axis
+static int events_shift_shape(const EventGeo &g, int mode, int S[2]) {
+    if (mode < TNMF_MODE_VALID || mode > TNMF_MODE_REFLECT) return TNMF_E_GEOM;
+    const int D[2] = {g.Dy, g.Dx}, A[2] = {g.Ay, g.Ax};
+    for (int i = 0; i < 2; ++i) {
+        S[i] = mode == TNMF_MODE_VALID ? D[i] + A[i] - 1 : mode == TNMF_MODE_FULL ? D[i] - A[i] + 1 : D[i];
+        if (S[i] < 1 || (mode == TNMF_MODE_CIRCULAR && A[i] - 1 > S[i]) || (mode == TNMF_MODE_REFLECT && A[i] - 1 >= S[i]))
+            return TNMF_E_GEOM;
+    }
     return TNMF_OK;
 }
 
@@ -1388,17 +1400,31 @@ int tnmf_hip_events_update(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mod
     if (rc != TNMF_OK) return rc;
     if (mode < TNMF_MODE_VALID || mode > TNMF_MODE_REFLECT || n_events < 0) return TNMF_E_GEOM;
     int S[2];
-    const int D[2] = {g.Dy, g.Dx}, A[2] = {g.Ay, g.Ax};
-    for (int i = 0; i < 2; ++i) {   // the limits of "reconstruction modes" above, per axis
-        S[i] = mode == TNMF_MODE_VALID ? D[i] + A[i] - 1 : mode == TNMF_MODE_FULL ? D[i] - A[i] + 1 : D[i];
-        if (S[i] < 1 || (mode == TNMF_MODE_CIRCULAR && A[i] - 1 > S[i]) || (mode == TNMF_MODE_REFLECT && A[i] - 1 >= S[i]))
-            return TNMF_E_GEOM;
-    }
+    if (events_shift_shape(g, mode, S) != TNMF_OK) return TNMF_E_GEOM;
     if (!(eps >= 0) || !(sparsity >= 0)) return TNMF_E_UNSUPPORTED;
     if (n_events > 0 && g.N > 0 && (!W_eff || !events || !strength_inout || !V || !R)) return TNMF_E_NULL;
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
     return events_update(ctx, g, geom->dtype, mode, S[0], S[1], W_eff, events, strength_inout, n_events, V, R,
                          eps + (sparsity > 0 ? sparsity : 0.), static_cast<hipStream_t>(stream));
+}
+
+int tnmf_hip_events_grad_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const int *events, const int *by_plane,
+                           const int *plane_start, const void *strength, long long n_events, const void *V, const void *R,
+                           void *workspace, void *negpos_eff, void *stream) {
+    if (!ctx || !geom) return TNMF_E_NULL;
+    EventGeo g;
+    const int rc = events_geo(geom, &g);
+    if (rc != TNMF_OK) return rc;
+    if (n_events < 0) return TNMF_E_GEOM;
+    int S[2];
+    if (events_shift_shape(g, mode, S) != TNMF_OK) return TNMF_E_GEOM;
+    if (n_events > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
+    if (!negpos_eff) return TNMF_E_NULL;
+    if (n_events > 0 && g.N > 0 && (!events || !by_plane || !plane_start || !strength || !V || !R || !workspace))
+        return TNMF_E_NULL;
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return events_grad_W(ctx, g, geom->dtype, mode, S[0], S[1], events, by_plane, plane_start, strength, n_events, V, R,
+                         workspace, negpos_eff, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// Events: the sparse H side -- render a list of events into R, refit their strengths (events.hip;
-// tnmf_hip_events_render / tnmf_hip_events_update).
+// Events: the sparse H side -- render a list of events into R, refit their strengths, take their W gradient (events.hip;
+// tnmf_hip_events_render / tnmf_hip_events_update / tnmf_hip_events_grad_W).
 #pragma once
 
 #include "common.h"
@@ -34,3 +34,11 @@ int events_render(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, const void *W
 int events_update(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const void *W,
                   const int *events, void *strength, long long n_events, const void *V, const void *R, double reg,
                   hipStream_t s);
+
+// negpos[2, P, C, Ay, Ax] = the W gradient of the events against V (neg) and R (pos): the events sorted by plane
+// (by_plane: n_events indices into `events`, plane_start: P + 1), summed in double per segment of TNMF_EVENTS_SEGMENT events
+// into `workspace` (events_grad_W_slabs() slabs of 2 * C * Ay * Ax doubles), then per plane in segment order.
+long long events_grad_W_slabs(long long n_events, int P);
+int events_grad_W(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const int *events,
+                  const int *by_plane, const int *plane_start, const void *strength, long long n_events, const void *V,
+                  const void *R, void *workspace, void *negpos, hipStream_t s);

@@ -18,6 +18,17 @@
 // stride over the C * Ay * Ax atom entries, gather V and R under each image, clipped per pixel, into double partial sums,
 // reduce them with a butterfly of fixed order and lane 0 applies the multiplicative update to the strength in place.  It
 // writes the K strengths and nothing else.
+//
+// k_events_grad_W / k_events_grad_W_sum: the W gradient of the list, many events onto few destinations (P * C * Ay * Ax
+// entries), without float atomics: a store pass and an ordered per-destination sum.  The caller sorts the events once per
+// support by plane (a permutation and plane_start); each plane's run is cut into segments of TNMF_EVENTS_SEGMENT events, a
+// constant of the list contract, so the order of the additions does not depend on the device.  One workgroup per segment
+// stages the rows and strengths of its events in LDS, images derived (axis_images); a thread owns a tap t = c * Ay * Ax + j
+// and walks the events in list order, loading V and R under each image through one address (consecutive jx are contiguous
+// in x) into double partial sums.  With at most 128 taps floor(256 / taps) sub-lanes share a tap, sub-lane s taking the
+// events s, s + L, ... of the segment, and are added through LDS in sub-lane order; with more than 256 taps the threads
+// loop over the taps.  The segment's [2, taps] slab of doubles is stored once; the second kernel adds the slabs of a plane
+// in segment order and rounds once to the element type, zeros for a plane without events: negpos is never read.
 #include <algorithm>
 
 #include "events.h"
@@ -148,6 +159,140 @@ __global__ __launch_bounds__(kEventThreads) void k_events_update(EventGeo g, int
     }
 }
 
+// The segments are numbered through the planes in plane order: plane p owns ceil(count_p / TNMF_EVENTS_SEGMENT) consecutive
+// slabs.  -> the run of plane p in by_plane, [*first, *first + *count), from plane_start clamped to [0, K]; a run that ends
+// before it begins is empty.
+__device__ __forceinline__ void plane_run(const int *__restrict__ plane_start, int p, int K, int *first, int *count) {
+    if (K <= 0) {   // (no events: plane_start is not read)
+        *first = *count = 0;
+        return;
+    }
+    const int a = min(max(plane_start[p], 0), K), b = min(max(plane_start[p + 1], 0), K);
+    *first = a;
+    *count = max(b - a, 0);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kEventThreads) void k_events_grad_W(EventGeo g, int mode, int Sy, int Sx,
+                                                                  const int4 *__restrict__ ev,
+                                                                  const int *__restrict__ by_plane,
+                                                                  const int *__restrict__ plane_start,
+                                                                  const T *__restrict__ h, int K,
+                                                                  const T *__restrict__ V, const T *__restrict__ R,
+                                                                  double *__restrict__ slabs) {
+    __shared__ int4 s_q[TNMF_EVENTS_SEGMENT];      // (qy0, qy1, qx0, qx1): the padded positions of the images per axis
+    __shared__ int s_n[TNMF_EVENTS_SEGMENT];       // the sample; -1 for a row to skip
+    __shared__ int s_cnt[TNMF_EVENTS_SEGMENT];     // images per axis: ny | nx << 2
+    __shared__ double s_h[TNMF_EVENTS_SEGMENT];
+    __shared__ double s_part[2][kEventThreads];    // the partial sums of the sub-lanes
+    // which plane, which of its segments (the same walk in every thread: scalar loads of a few cached ints)
+    const int slab = blockIdx.x;
+    int plane = -1, first = 0, count = 0;
+    long long acc = 0;   // (64 bits: overlapping runs of a plane_start outside the contract may add up beyond K)
+    for (int p = 0; p < g.P; ++p) {
+        int a, c;
+        plane_run(plane_start, p, K, &a, &c);
+        const int ns = (c + TNMF_EVENTS_SEGMENT - 1) / TNMF_EVENTS_SEGMENT;
+        if (slab < acc + ns) {
+            plane = p;
+            first = a + (int)(slab - acc) * TNMF_EVENTS_SEGMENT;
+            count = min(TNMF_EVENTS_SEGMENT, a + c - first);
+            break;
+        }
+        acc += ns;
+    }
+    if (plane < 0) return;   // (workgroup-uniform: a slab beyond the last segment)
+    for (int i = threadIdx.x; i < count; i += kEventThreads) {
+        const int e = by_plane[first + i];
+        int n = -1, cnt = 0;
+        int4 q = make_int4(0, 0, 0, 0);
+        double hv = 0.;
+        if ((unsigned)e < (unsigned)K) {
+            const int4 v = ev[e];   // sample, plane, uy, ux
+            if ((unsigned)v.x < (unsigned)g.N && v.y == plane && (unsigned)v.z < (unsigned)Sy &&
+                (unsigned)v.w < (unsigned)Sx) {
+                int qy[2] = {0, 0}, qx[2] = {0, 0};
+                const int ny = axis_images(mode, v.z, g.Ay, Sy, qy), nx = axis_images(mode, v.w, g.Ax, Sx, qx);
+                n = v.x, cnt = ny | nx << 2, q = make_int4(qy[0], qy[1], qx[0], qx[1]);
+                hv = (double)h[e];
+            }
+        }
+        s_n[i] = n, s_cnt[i] = cnt, s_q[i] = q, s_h[i] = hv;
+    }
+    __syncthreads();
+    const int AA = g.Ay * g.Ax, taps = g.C * AA;
+    const int L = max(1, kEventThreads / taps);   // sub-lanes per tap
+    const size_t plane_size = (size_t)g.Dy * g.Dx;
+    double *out = slabs + (size_t)slab * 2 * taps;
+    for (int t0 = 0; t0 < taps; t0 += kEventThreads) {
+        const int sub = L > 1 ? (int)threadIdx.x / taps : 0;
+        const int t = L > 1 ? (int)threadIdx.x - sub * taps : t0 + (int)threadIdx.x;
+        const bool active = t < taps && sub < L;
+        double neg = 0., pos = 0.;
+        if (active) {
+            const int c = t / AA, r = t - c * AA;
+            const int jy = r / g.Ax, jx = r - jy * g.Ax;
+            for (int i = sub; i < count; i += L) {
+                const int n = s_n[i];
+                if (n < 0) continue;
+                const int4 q = s_q[i];
+                const int cnt = s_cnt[i], ny = cnt & 3, nx = cnt >> 2;
+                const double hv = s_h[i];
+                const size_t base = ((size_t)n * g.C + c) * plane_size;
+                double a = 0., b = 0.;
+                for (int iy = 0; iy < ny; ++iy) {
+                    const int y = (iy ? q.y : q.x) - (g.Ay - 1) + jy;
+                    for (int ix = 0; ix < nx; ++ix) {
+                        const int x = (ix ? q.w : q.z) - (g.Ax - 1) + jx;
+                        if ((unsigned)y < (unsigned)g.Dy && (unsigned)x < (unsigned)g.Dx) {
+                            const size_t at = base + (size_t)y * g.Dx + x;
+                            a += (double)V[at];
+                            b += (double)R[at];
+                        }
+                    }
+                }
+                neg += hv * a;
+                pos += hv * b;
+            }
+        }
+        if (L > 1) {   // (taps < 256: one pass, t0 == 0)
+            s_part[0][threadIdx.x] = neg, s_part[1][threadIdx.x] = pos;
+            __syncthreads();
+            if (active && sub == 0) {
+                for (int s = 1; s < L; ++s) neg += s_part[0][s * taps + t], pos += s_part[1][s * taps + t];
+            }
+        }
+        if (active && sub == 0) out[t] = neg, out[taps + t] = pos;
+    }
+}
+
+// negpos[2, P, taps] = per plane the sum of its slabs in segment order, rounded once; one thread per (plane, tap)
+template <typename T>
+__global__ __launch_bounds__(kEventThreads) void k_events_grad_W_sum(int P, int taps, const int *__restrict__ plane_start,
+                                                                      int K, long long n_slabs,
+                                                                      const double *__restrict__ slabs,
+                                                                      T *__restrict__ negpos) {
+    const int chunks = (taps + kEventThreads - 1) / kEventThreads;
+    const int p = blockIdx.x / chunks, t = (blockIdx.x - p * chunks) * kEventThreads + threadIdx.x;
+    if (t >= taps) return;
+    long long s0 = 0;
+    int a, c;
+    for (int pp = 0; pp < p; ++pp) {
+        plane_run(plane_start, pp, K, &a, &c);
+        s0 += (c + TNMF_EVENTS_SEGMENT - 1) / TNMF_EVENTS_SEGMENT;
+    }
+    plane_run(plane_start, p, K, &a, &c);
+    const long long s1 = std::min<long long>(s0 + (c + TNMF_EVENTS_SEGMENT - 1) / TNMF_EVENTS_SEGMENT, n_slabs);
+    double neg = 0., pos = 0.;
+    for (long long s = s0; s < s1; ++s) {
+        const double *slab = slabs + (size_t)s * 2 * taps;
+        neg += slab[t];
+        pos += slab[taps + t];
+    }
+    negpos[(size_t)p * taps + t] = (T)neg;
+    negpos[((size_t)P + p) * taps + t] = (T)pos;
+}
+
 unsigned grid_for(const tnmf_hip_ctx *ctx, long long blocks) {
     return (unsigned)std::max<long long>(1, std::min<long long>(blocks, (long long)ctx->num_cu * 64));
 }
@@ -186,6 +331,37 @@ int events_update(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int
         hipLaunchKernelGGL(k_events_update<double>, dim3(grid), dim3(kEventThreads), 0, s, g, mode, Sy, Sx,
                            (const double *)W, (const int4 *)events, (double *)strength, n_events, (const double *)V,
                            (const double *)R, reg);
+    TNMF_LAUNCH_CHECK();
+    return TNMF_OK;
+}
+
+long long events_grad_W_slabs(long long n_events, int P) { return n_events / TNMF_EVENTS_SEGMENT + P; }
+
+int events_grad_W(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const int *events,
+                  const int *by_plane, const int *plane_start, const void *strength, long long n_events, const void *V,
+                  const void *R, void *workspace, void *negpos, hipStream_t s) {
+    const int taps = g.C * g.Ay * g.Ax;
+    const long long n_slabs = events_grad_W_slabs(n_events, g.P);
+    if (n_events > 0 && g.N > 0) {
+        if (dtype == 0)
+            hipLaunchKernelGGL(k_events_grad_W<float>, dim3((unsigned)n_slabs), dim3(kEventThreads), 0, s, g, mode, Sy, Sx,
+                               (const int4 *)events, by_plane, plane_start, (const float *)strength, (int)n_events,
+                               (const float *)V, (const float *)R, (double *)workspace);
+        else
+            hipLaunchKernelGGL(k_events_grad_W<double>, dim3((unsigned)n_slabs), dim3(kEventThreads), 0, s, g, mode, Sy,
+                               Sx, (const int4 *)events, by_plane, plane_start, (const double *)strength, (int)n_events,
+                               (const double *)V, (const double *)R, (double *)workspace);
+        TNMF_LAUNCH_CHECK();
+    }
+    // (without events or samples no slab exists: K = 0 makes every run empty, whatever plane_start holds)
+    const int K = g.N > 0 ? (int)n_events : 0;
+    const dim3 grid((unsigned)((long long)cdiv(taps, kEventThreads) * g.P));
+    if (dtype == 0)
+        hipLaunchKernelGGL(k_events_grad_W_sum<float>, grid, dim3(kEventThreads), 0, s, g.P, taps, plane_start, K, n_slabs,
+                           (const double *)workspace, (float *)negpos);
+    else
+        hipLaunchKernelGGL(k_events_grad_W_sum<double>, grid, dim3(kEventThreads), 0, s, g.P, taps, plane_start, K,
+                           n_slabs, (const double *)workspace, (double *)negpos);
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
