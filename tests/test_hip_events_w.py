@@ -73,6 +73,17 @@ def test_the_own_cases_reach_what_they_are_for():
     assert C * int(np.prod(A)) > 256
     (_, C, _, _, A, _) = wcase('few-taps')[0]
     assert C * int(np.prod(A)) < 64
+    # ... and the verdict of the host mirror of the kernels (tests/events_dispatch.py) on the same three
+    import events_dispatch as ed
+    reached = {name: ed.reached(*wcase(name)[:4]) for name in OWN}
+    assert {'full-segment', 'partial-segment', 'plane-of-several-segments', 'slab-beyond-the-last-segment',
+            'L-2..63'} <= reached['segments']['grad_W']
+    assert {'plane-without-slabs', 'one-slab', 'several-slabs'} <= reached['segments']['grad_W_sum']
+    assert {'tap-loop-strides', 'L==1', 'idle-threads'} <= reached['more-taps-than-threads']['grad_W']
+    assert 'G1:three-tap-passes' not in reached['more-taps-than-threads']['grad_W']
+    assert {'several-chunks', 'threads-beyond-the-taps'} <= reached['more-taps-than-threads']['grad_W_sum']
+    assert {'L-2..63', 'idle-threads', 'two-images'} <= reached['few-taps']['grad_W']
+    assert ed.sub_lanes(7) == 36 and 'U1:idle-lanes' in reached['few-taps']['update']
 
 
 @functools.lru_cache(maxsize=None)
