@@ -249,7 +249,10 @@ int tnmf_hip_grad_W_fused(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const vo
  * A RUN of consecutive TNMF_OP_UPDATE_H operations on pairwise disjoint sample ranges is executed as the H half step of
  * their union (ranges sorted and joined where they touch): such steps commute -- the H update of a sample reads that sample
  * and W only, and W does not change inside the run -- so GSG-MU / GSAG-MU (:474-479, :493-504: H for every shuffled batch, W
- * from the last batch) cost one H half step over all samples per epoch, not one launch chain per batch. */
+ * from the last batch) cost one H half step over all samples per epoch, not one launch chain per batch.
+ * The whole list is checked before anything runs, on one, two and three shift axes alike: an unknown kind is
+ * TNMF_E_UNSUPPORTED, a range outside [0, N] or with n1 < n0 TNMF_E_GEOM (TNMF_OP_APPLY_W names no samples: its n0, n1 are
+ * not read), and a refused list leaves W, H and acc as they were. */
 enum { TNMF_OP_UPDATE_H = 0, TNMF_OP_GRAD_W = 1, TNMF_OP_APPLY_W = 2 };
 typedef struct {
     int kind;    /* TNMF_OP_* */

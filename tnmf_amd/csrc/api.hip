@@ -487,6 +487,11 @@ int vol_api_run_schedule(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const voi
     const size_t wn = (size_t)v.M * v.C * vol_avox(v);
     int nmax = 0;
     for (int i = 0; i < n_ops; ++i) {
+        // (kinds and ranges of the whole list before anything runs, as on one and two shift axes: a refused list leaves
+        // W, H and acc as they were; the W update names no samples)
+        if (ops[i].kind != TNMF_OP_UPDATE_H && ops[i].kind != TNMF_OP_GRAD_W && ops[i].kind != TNMF_OP_APPLY_W)
+            return TNMF_E_UNSUPPORTED;
+        if (ops[i].kind == TNMF_OP_APPLY_W) continue;
         if (ops[i].n0 < 0 || ops[i].n1 < ops[i].n0 || ops[i].n1 > v.N) return TNMF_E_GEOM;
         if (ops[i].n1 - ops[i].n0 > nmax) nmax = ops[i].n1 - ops[i].n0;
     }
