@@ -537,6 +537,30 @@ int tnmf_hip_events_update(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mod
                            void *strength_inout, long long n_events, const void *V, const void *R, double eps,
                            double sparsity, void *stream);
 
+/* tnmf_hip_events_gain: what each event of a list explains -- the Frobenius energy E = 1/2 ||V - R||^2 of the list without
+ * event e minus that of the list, R being the render of the whole list.  With phi_e[c, x] = the sum over the images of e of
+ * W_eff[p, c, .] placed at the image, restricted to the pixels inside sample n, and d = V - R,
+ *   gain[e] = h_e * a_e + 1/2 * h_e^2 * b_e,   a_e = <phi_e, d>,   b_e = ||phi_e||^2
+ * exactly (E is quadratic in h_e): positive where the event lowers the objective, and 1/2 h_e^2 b_e >= 0 at a fixed point
+ * of the refit, where a_e = 0.  The images of one event may overlap inside the sample ('reflect' with 1 <= u <= a - 1: the
+ * offsets u and -u), so b_e is not the sum of the images' norms: with t over the taps of image i whose pixel px(i, t) lies in
+ * the sample,  a_e = sum_i sum_t w_t * d(px(i, t)),  b_e = sum_i sum_t w_t * phi_e(px(i, t)),  phi_e(px) summed over the at
+ * most four images that cover px (the tap itself for an event of one image).
+ *   mag[e] = sum_i sum_t  h_e * |w_t * d(px)| + 1/2 * h_e^2 * |w_t * phi_e(px)|
+ * is the sum of the magnitudes of the terms of gain[e]: the scale of its rounding error (may be NULL: not written).
+ * events: the n_events rows of four ints of tnmf_hip_events_update, in the order of `strength` (read, not written);
+ * duplicates are allowed, every row is scored against the R it is given.  gain, mag: n_events DOUBLES, whatever the element
+ * type; d = (double)V - (double)R and every sum are taken in double in a fixed order, no atomics: the same list gives the
+ * same bits run after run.  Every element of both is written -- they need no initialisation -- 0 for a row whose sample,
+ * plane or shift is out of range (no sample data is read for it).  It reads W_eff, events, strength, V and R and writes
+ * gain and mag, nothing else.  Workspace: none.  Asynchronous.  With n_events == 0 or N == 0 it does nothing.
+ * Refused before anything is written, as tnmf_hip_events_update is: TNMF_E_NULL (ctx, geom, and with n_events > 0 and
+ * N > 0 every operand but mag), TNMF_E_DTYPE, TNMF_E_UNSUPPORTED for volumes and for more than 2^31 - 1 events,
+ * TNMF_E_GEOM for any other ndim, sizes <= 0, a negative count, an unknown mode and the per-axis limits of the mode. */
+int tnmf_hip_events_gain(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,
+                         const void *strength, long long n_events, const void *V, const void *R, double *gain,
+                         double *mag /* may be NULL */, void *stream);
+
 /* tnmf_hip_events_grad_W: the W gradient of a list of events -- with the images q of event e = (n, p, u, h_e) per the table
  * above, for every plane p, channel c and atom entry j (0 <= j < A per axis)
  *   neg[p, c, j] = sum over the events e of plane p, over their images q, of  h_e * V[n_e, c, q - (A - 1) + j]

@@ -5,7 +5,8 @@ Public surface = the reference's (tnmf/TransformInvariantNMF.py): ``TransformInv
 inhibition_range, backend, logger, verbose, **backend_kwargs)`` with ``fit`` / ``fit_batch`` / ``fit_minibatches`` /
 ``fit_stream``, the read-outs ``W``, ``H``, ``V``, ``R``, ``R_partial(i)`` and the ``MiniBatchAlgorithm`` enum; beyond it
 ``detections()`` (-> ``Detections``), the events read off ``H``, and ``reconstruct_detections`` / ``refit_detections``,
-what such a list explains and its strengths refitted on the fixed support.
+what such a list explains and its strengths refitted on the fixed support, and ``detection_gains`` / ``prune_detections``,
+what each row explains and the list without the rows the data does not need.
 The only backend shipped is ``'hip'`` (tnmf_amd/backends/HIP.py); any object implementing
 tnmf_amd.backends._Backend.Backend can be passed instead of a name.
 
@@ -211,6 +212,47 @@ def events_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], n_samples: int, m
             pos[e] += np.sum(atom * R[where])
         h = h * neg / (pos + reg)
     return h
+
+
+def events_gain_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], n_samples: int, mode: str, sample, plane, shift, strength,
+                      V: np.ndarray) -> np.ndarray:
+    """[K] float64: what each event explains, on the host, for backends without ``event_gains`` -- the semantics of
+    tnmf_hip_events_gain (include/tnmf_hip.h, "events"): the energy 1/2 ||V - R||^2 of the list without the event minus that
+    of the list, ``h a + h^2 b / 2`` with ``a = <phi, V - R>``, ``b = ||phi||^2`` and phi the event's images summed into a
+    dense sample (so images that overlap are added before they are squared).  Not on the hip path."""
+    A, D = tuple(W.shape[2:]), tuple(sample_shape)
+    shift_shape = tuple(d + a - 1 if mode == 'valid' else d - a + 1 if mode == 'full' else d for d, a in zip(D, A))
+    W, V = np.asarray(W, dtype=np.float64), np.asarray(V, dtype=np.float64)
+    h = np.array(strength, dtype=np.float64).reshape(-1)
+    residual = V - events_numpy(W, D, n_samples, mode, sample, plane, shift, h)
+    event, q = event_images(shift, A, shift_shape, mode)
+    gain = np.zeros(len(h))
+    for e in range(len(h)):
+        phi = np.zeros((W.shape[1],) + D)
+        for at in q[event == e]:
+            origin = [int(x) - (a - 1) for x, a in zip(at, A)]
+            lo = [max(o, 0) for o in origin]
+            hi = [min(o + a, d) for o, a, d in zip(origin, A, D)]
+            if all(b > a for a, b in zip(lo, hi)):
+                phi[(slice(None),) + tuple(slice(a, b) for a, b in zip(lo, hi))] += W[
+                    (int(plane[e]), slice(None)) + tuple(slice(a - o, b - o) for a, b, o in zip(lo, hi, origin))]
+        gain[e] = h[e] * np.sum(phi * residual[int(sample[e])]) + 0.5 * h[e] * h[e] * np.sum(phi * phi)
+    return gain
+
+
+def event_boxes(shift: np.ndarray, atom_shape: Tuple[int, ...], sample_shape: Tuple[int, ...], shift_shape: Tuple[int, ...],
+                mode: str):
+    """(lo [K, k], hi [K, k]): per event the bounding box ``lo .. hi - 1`` of the pixels of the sample its images cover
+    (``event_images``, each image clipped to the sample); ``hi <= lo`` on an axis for an event without such a pixel."""
+    A, D = np.asarray(atom_shape, dtype=np.int64), np.asarray(sample_shape, dtype=np.int64)
+    K = len(np.asarray(shift).reshape(-1, len(atom_shape)))
+    event, q = event_images(shift, tuple(atom_shape), tuple(shift_shape), mode)
+    first, last = np.maximum(q - (A - 1), 0), np.minimum(q + 1, D)
+    inside = np.all(last > first, axis=1)
+    lo, hi = np.tile(D, (K, 1)), np.zeros((K, len(A)), dtype=np.int64)
+    np.minimum.at(lo, event[inside], first[inside])
+    np.maximum.at(hi, event[inside], last[inside])
+    return lo, hi
 
 
 def events_fit_numpy(W: np.ndarray, transforms, sample_shape: Tuple[int, ...], n_samples: int, mode: str, sample, plane,
@@ -611,6 +653,67 @@ class TransformInvariantNMF:
         as_rows = lambda x: np.asarray(x).astype(np.int64).reshape(len(new))   # noqa: E731
         return Detections(sample=as_rows(det.sample), atom=as_rows(det.atom), transform=as_rows(det.transform),
                           shift=shift, origin=shift - offset, strength=new)
+
+    def detection_gains(self, det) -> np.ndarray:
+        """[K] float64: what each detection of ``det`` explains -- the objective 1/2 ||V - R||^2 of the list without the row
+        minus that of the list, R being ``reconstruct_detections(det)``: ``h a + h^2 b / 2`` with phi the row's occurrence
+        (all its images, clipped to the sample), ``a = <phi, V - R>`` and ``b = ||phi||^2``.  Positive where the row lowers
+        the objective; after a refit to convergence ``a = 0`` and the gain is ``h^2 b / 2``.  Unlike the strength it is in
+        the units of the objective for every atom.  Duplicate rows are scored each against the whole list.  On a backend
+        with ``event_gains`` the list is rendered and scored on the device and only the K gains are copied.  The plain
+        Frobenius objective only."""
+        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
+            raise NotImplementedError('detection_gains covers the plain Frobenius objective (beta_loss 2, no weights)')
+        sample, plane, shift, strength = self._events_of(det, distinct=False)
+        hook = getattr(self._backend, 'event_gains', None)
+        if hook is not None:
+            return np.asarray(hook(self._V, self._W_dict, sample, plane, shift, strength), dtype=np.float64)
+        return events_gain_numpy(self._backend.to_ndarray(self._W_dict), self._V.shape[2:], int(self._H.shape[0]),
+                                 getattr(self._backend, '_reconstruction_mode', 'valid'), sample, plane, shift, strength,
+                                 self._local_V())
+
+    def prune_detections(self, det, min_gain: float, n_iterations: int = 50, sparsity_H: float = 0.,
+                         max_rounds: int = 100) -> Tuple[Detections, np.ndarray]:
+        """Backward elimination: the rows of ``det`` the data needs, refitted, and their gains.  Each round refits the
+        strengths (``refit_detections`` with ``n_iterations`` and ``sparsity_H``), scores the rows (``detection_gains``) and
+        takes those with a gain below ``min_gain`` as candidates.  Per sample the candidates are walked in ascending gain
+        (ties in row order) and dropped unless the bounding box of their occurrence in the sample meets that of a candidate
+        already dropped in this round: rows with disjoint footprints have independent gains, so dropping them together is
+        exact, and overlapping ones are scored again in the next round, after a refit without their neighbour.  It stops
+        when a round finds no candidate or after ``max_rounds`` rounds of dropping; ``max_rounds=0`` is a refit with its
+        gains.  The rows are chosen on the host -- the list is small; refit, render and gains run where the backend runs
+        them.  The rows must be distinct; the plain Frobenius objective only."""
+        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
+            raise NotImplementedError('prune_detections covers the plain Frobenius objective (beta_loss 2, no weights)')
+        if (isinstance(min_gain, (bool, np.bool_)) or not isinstance(min_gain, numbers.Real)
+                or not math.isfinite(min_gain)):
+            raise ValueError(f'min_gain must be a finite number, not {min_gain!r}')
+        if (isinstance(max_rounds, (bool, np.bool_)) or not isinstance(max_rounds, numbers.Integral)
+                or max_rounds < 0):
+            raise ValueError(f'max_rounds must be an int >= 0, not {max_rounds!r}')
+        mode = getattr(self._backend, '_reconstruction_mode', 'valid')
+        rounds = 0
+        while True:
+            det = self.refit_detections(det, n_iterations, sparsity_H)
+            gains = self.detection_gains(det)
+            if rounds >= max_rounds:
+                break
+            lo, hi = event_boxes(det.shift, self.atom_shape, self._V.shape[2:], tuple(int(x) for x in self._H.shape[2:]),
+                                 mode)
+            keep = np.ones(len(det), dtype=bool)
+            candidates = np.flatnonzero(gains < min_gain)
+            dropped = {}   # per sample: the boxes dropped in this round
+            for e in candidates[np.argsort(gains[candidates], kind='stable')]:
+                boxes = dropped.setdefault(int(det.sample[e]), [])
+                if any(np.all(np.maximum(lo[e], a) < np.minimum(hi[e], b)) for a, b in boxes):
+                    continue
+                boxes.append((lo[e], hi[e]))
+                keep[e] = False
+            if keep.all():
+                break
+            det = Detections(**{f.name: getattr(det, f.name)[keep] for f in dataclasses.fields(Detections)})
+            rounds += 1
+        return det, gains
 
     def fit_detections(self, det, n_iterations: int = 50, sparsity_H: float = 0., update_H: bool = True,
                        update_W: bool = True) -> Detections:

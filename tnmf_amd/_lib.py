@@ -31,7 +31,7 @@ EXPORTS = (
     'tnmf_hip_ops_apply_W',
     'tnmf_hip_ctx_set_objective_tap', 'tnmf_hip_sample_objective',
     'tnmf_hip_find_peaks',
-    'tnmf_hip_events_render', 'tnmf_hip_events_update', 'tnmf_hip_events_grad_W',
+    'tnmf_hip_events_render', 'tnmf_hip_events_update', 'tnmf_hip_events_grad_W', 'tnmf_hip_events_gain',
 )
 
 MODES = {'valid': 0, 'full': 1, 'circular': 2, 'reflect': 3}
@@ -152,6 +152,7 @@ def load() -> ctypes.CDLL:
     lib.tnmf_hip_events_render.argtypes = [vp, gp, vp, vp, ll, vp, vp, ll, vp, vp]
     lib.tnmf_hip_events_update.argtypes = [vp, gp, ci, vp, vp, vp, ll, vp, vp, cd, cd, vp]
     lib.tnmf_hip_events_grad_W.argtypes = [vp, gp, ci, vp, vp, vp, vp, ll, vp, vp, vp, vp, vp]
+    lib.tnmf_hip_events_gain.argtypes = [vp, gp, ci, vp, vp, vp, ll, vp, vp, vp, vp, vp]
     lib.tnmf_hip_pad_H.argtypes = [vp, gp, ci, vp, vp, vp]
     lib.tnmf_hip_fold_H.argtypes = [vp, gp, ci, vp, vp, vp]
     for name in EXPORTS:

@@ -948,6 +948,33 @@ class HIP_Backend(Backend):
             self.update_event_list(W, events, strength, R, sparsity, eps)
         return strength
 
+    def gain_event_list(self, W: torch.Tensor, events: torch.Tensor, strength: torch.Tensor, R: torch.Tensor,
+                        with_magnitude: bool = False):
+        """[K] float64 on the device: what each event explains, R being the render of the strengths ->
+        tnmf_hip_events_gain; with ``with_magnitude`` (gain, mag), mag the sum of the magnitudes of each gain's terms."""
+        self._check_W(W)
+        assert strength.is_contiguous() and strength.dtype == self._torch_dtype and events.shape[0] == strength.numel()
+        K = strength.numel()
+        gain = torch.empty(K, dtype=torch.float64, device=self._device)
+        mag = torch.empty(K, dtype=torch.float64, device=self._device) if with_magnitude else None
+        with self._timed('events_gain'):
+            _lib.check(self._lib.tnmf_hip_events_gain(
+                self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0])), self._mode, _ptr(W), _ptr(events),
+                _ptr(strength), K, _ptr(self._V_dev), _ptr(R), _ptr(gain), _ptr(mag), self._stream()),
+                'tnmf_hip_events_gain')
+        return (gain, mag) if with_magnitude else gain
+
+    def event_gains(self, V, W: torch.Tensor, sample, plane, shift, strength) -> np.ndarray:
+        """[K] float64 on the host: per event the Frobenius energy of the list without it minus that of the list, against
+        the resident samples (`V` is the array given to initialize(), as for the other hooks): one render of the list and
+        one gather per event; only the K doubles are copied.  Duplicate events are scored each against the whole list."""
+        if self._G_dev is not None:
+            raise NotImplementedError('event_gains is unweighted')
+        sample, plane, shift, strength = self._check_events(W.shape[0], sample, plane, shift, strength)
+        images, cell_start, events = self.event_list(sample, plane, shift)
+        R = self.render_event_list(W, images, cell_start, strength)
+        return self.gain_event_list(W, events, strength, R).cpu().numpy()
+
     # -- events: the dictionary learnt from the detections ------------------------------------------------------------------
     def event_plane_list(self, plane: torch.Tensor, n_planes: int):
         """The plane list tnmf_hip_events_grad_W takes, built on the device for checked events: (by_plane [K] int32, the

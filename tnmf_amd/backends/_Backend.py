@@ -38,7 +38,8 @@ A backend that declares ``supports_events`` works on lists of events (local samp
 shift in its H, strength; include/tnmf_hip.h, "events"): ``render_events(W, sample, plane, shift, strength) -> R``
 (backend-native ``[n_local, C, *D]``) and ``refit_events(V, W, sample, plane, shift, strength, n_iterations, sparsity=0.,
 eps=1e-9) -> strength`` (backend-native ``[K]``); without them ``reconstruct_detections`` / ``refit_detections`` run
-``events_numpy`` on the host.
+``events_numpy`` on the host.  It may also offer ``event_gains(V, W, sample, plane, shift, strength) -> ndarray[K]`` (float64,
+host): what each event explains; without it ``detection_gains`` runs ``events_gain_numpy`` on the host.
 """
 import abc
 from typing import Optional, Sequence, Tuple, Union

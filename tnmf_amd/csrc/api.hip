@@ -1413,6 +1413,23 @@ int tnmf_hip_events_update(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mod
                          eps + (sparsity > 0 ? sparsity : 0.), static_cast<hipStream_t>(stream));
 }
 
+int tnmf_hip_events_gain(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,
+                         const void *strength, long long n_events, const void *V, const void *R, double *gain, double *mag,
+                         void *stream) {
+    if (!ctx || !geom) return TNMF_E_NULL;
+    EventGeo g;
+    const int rc = events_geo(geom, &g);
+    if (rc != TNMF_OK) return rc;
+    if (mode < TNMF_MODE_VALID || mode > TNMF_MODE_REFLECT || n_events < 0) return TNMF_E_GEOM;
+    int S[2];
+    if (events_shift_shape(g, mode, S) != TNMF_OK) return TNMF_E_GEOM;
+    if (n_events > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
+    if (n_events > 0 && g.N > 0 && (!W_eff || !events || !strength || !V || !R || !gain)) return TNMF_E_NULL;
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return events_gain(ctx, g, geom->dtype, mode, S[0], S[1], W_eff, events, strength, n_events, V, R, gain, mag,
+                       static_cast<hipStream_t>(stream));
+}
+
 int tnmf_hip_events_grad_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const int *events, const int *by_plane,
                            const int *plane_start, const void *strength, long long n_events, const void *V, const void *R,
                            void *workspace, void *negpos_eff, void *stream) {

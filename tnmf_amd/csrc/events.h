@@ -1,5 +1,5 @@
-// Events: the sparse H side -- render a list of events into R, refit their strengths, take their W gradient (events.hip;
-// tnmf_hip_events_render / tnmf_hip_events_update / tnmf_hip_events_grad_W).
+// Events: the sparse H side -- render a list of events into R, refit their strengths, score them, take their W gradient
+// (events.hip; tnmf_hip_events_render / tnmf_hip_events_update / tnmf_hip_events_gain / tnmf_hip_events_grad_W).
 #pragma once
 
 #include "common.h"
@@ -34,6 +34,13 @@ int events_render(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, const void *W
 int events_update(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const void *W,
                   const int *events, void *strength, long long n_events, const void *V, const void *R, double reg,
                   hipStream_t s);
+
+// gain[e] = E(list without e) - E(list) of the Frobenius energy, = h_e <phi_e, V - R> + h_e^2 |phi_e|^2 / 2 with phi_e the sum
+// of the images of event e clipped to the sample, R the render of the list; mag[e] (may be NULL) = the sum of the magnitudes
+// of the terms.  Doubles whatever the element type; every element is written, 0 for a row out of range.
+int events_gain(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const void *W, const int *events,
+                const void *strength, long long n_events, const void *V, const void *R, double *gain, double *mag,
+                hipStream_t s);
 
 // negpos[2, P, C, Ay, Ax] = the W gradient of the events against V (neg) and R (pos): the events sorted by plane
 // (by_plane: n_events indices into `events`, plane_start: P + 1), summed in double per segment of TNMF_EVENTS_SEGMENT events

@@ -19,6 +19,12 @@
 // reduce them with a butterfly of fixed order and lane 0 applies the multiplicative update to the strength in place.  It
 // writes the K strengths and nothing else.
 //
+// k_events_gain: the same gather, one wave per event, for what the event explains: gain_e = E(list without e) - E(list)
+// = h a + h^2 b / 2 with a = <phi_e, V - R>, b = |phi_e|^2, phi_e the sum of the event's images clipped to the sample.  The
+// images of one event can overlap, so phi_e at a pixel is summed over the images (skipped for the single-image event,
+// where it is the tap itself).  All in double; the sum of the terms' magnitudes goes out beside the gain as the scale of
+// its rounding error.  It writes the K gains (and magnitudes), zeros for a row outside the contract, and nothing else.
+//
 // k_events_grad_W / k_events_grad_W_sum: the W gradient of the list, many events onto few destinations (P * C * Ay * Ax
 // entries), without float atomics: a store pass and an ordered per-destination sum.  The caller sorts the events once per
 // support by plane (a permutation and plane_start); each plane's run is cut into segments of TNMF_EVENTS_SEGMENT events, a
@@ -156,6 +162,74 @@ __global__ __launch_bounds__(kEventThreads) void k_events_update(EventGeo g, int
             pos += __shfl_xor(pos, off, 64);
         }
         if (lane == 0) h[e] = (T)((double)h[e] * neg / (pos + reg));
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kEventThreads) void k_events_gain(EventGeo g, int mode, int Sy, int Sx,
+                                                                const T *__restrict__ W, const int4 *__restrict__ ev,
+                                                                const T *__restrict__ h, long long n_events,
+                                                                const T *__restrict__ V, const T *__restrict__ R,
+                                                                double *__restrict__ gain, double *__restrict__ mag) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int AA = g.Ay * g.Ax, taps = g.C * AA;
+    for (long long e = (long long)blockIdx.x * kWaves + wave; e < n_events; e += (long long)gridDim.x * kWaves) {
+        const int4 v = ev[e];   // sample, plane, uy, ux
+        if ((unsigned)v.x >= (unsigned)g.N || (unsigned)v.y >= (unsigned)g.P || (unsigned)v.z >= (unsigned)Sy ||
+            (unsigned)v.w >= (unsigned)Sx) {   // (wave-uniform: outside the contract, no sample data is read)
+            if (lane == 0) {
+                gain[e] = 0.;
+                if (mag) mag[e] = 0.;
+            }
+            continue;
+        }
+        int qy[2], qx[2];
+        const int ny = axis_images(mode, v.z, g.Ay, Sy, qy), nx = axis_images(mode, v.w, g.Ax, Sx, qx);
+        const bool single = ny * nx == 1;   // (wave-uniform) phi at a pixel is the tap itself
+        const T *w = W + (size_t)v.y * taps;
+        const size_t sample = (size_t)v.x * g.C * g.Dy * g.Dx;
+        const double hv = (double)h[e], hh = 0.5 * hv * hv;
+        double a = 0., b = 0., m = 0.;
+        for (int iy = 0; iy < ny; ++iy) {
+            for (int ix = 0; ix < nx; ++ix) {
+                const int oy = qy[iy] - (g.Ay - 1), ox = qx[ix] - (g.Ax - 1);
+                for (int t = lane; t < taps; t += 64) {
+                    const int c = t / AA, r = t - c * AA;
+                    const int jy = r / g.Ax, jx = r - jy * g.Ax;
+                    const int y = oy + jy, x = ox + jx;
+                    if ((unsigned)y < (unsigned)g.Dy && (unsigned)x < (unsigned)g.Dx) {
+                        const size_t at = sample + ((size_t)c * g.Dy + y) * g.Dx + x;
+                        const double wv = (double)w[t];
+                        double phi = wv;
+                        if (!single) {   // every image that covers this pixel, in image order
+                            phi = 0.;
+                            for (int ky = 0; ky < ny; ++ky) {
+                                const int ly = y - (qy[ky] - (g.Ay - 1));
+                                if ((unsigned)ly >= (unsigned)g.Ay) continue;
+                                for (int kx = 0; kx < nx; ++kx) {
+                                    const int lx = x - (qx[kx] - (g.Ax - 1));
+                                    if ((unsigned)lx < (unsigned)g.Ax) phi += (double)w[c * AA + ly * g.Ax + lx];
+                                }
+                            }
+                        }
+                        const double wd = wv * ((double)V[at] - (double)R[at]), wp = wv * phi;
+                        a += wd;
+                        b += wp;
+                        m += hv * fabs(wd) + hh * fabs(wp);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {   // the butterfly of the update: a fixed order of additions
+            a += __shfl_xor(a, off, 64);
+            b += __shfl_xor(b, off, 64);
+            m += __shfl_xor(m, off, 64);
+        }
+        if (lane == 0) {
+            gain[e] = hv * a + hh * b;
+            if (mag) mag[e] = m;
+        }
     }
 }
 
@@ -331,6 +405,23 @@ int events_update(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int
         hipLaunchKernelGGL(k_events_update<double>, dim3(grid), dim3(kEventThreads), 0, s, g, mode, Sy, Sx,
                            (const double *)W, (const int4 *)events, (double *)strength, n_events, (const double *)V,
                            (const double *)R, reg);
+    TNMF_LAUNCH_CHECK();
+    return TNMF_OK;
+}
+
+int events_gain(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const void *W, const int *events,
+                const void *strength, long long n_events, const void *V, const void *R, double *gain, double *mag,
+                hipStream_t s) {
+    if (n_events <= 0 || g.N <= 0) return TNMF_OK;
+    const unsigned grid = grid_for(ctx, (n_events + kWaves - 1) / kWaves);
+    if (dtype == 0)
+        hipLaunchKernelGGL(k_events_gain<float>, dim3(grid), dim3(kEventThreads), 0, s, g, mode, Sy, Sx, (const float *)W,
+                           (const int4 *)events, (const float *)strength, n_events, (const float *)V, (const float *)R,
+                           gain, mag);
+    else
+        hipLaunchKernelGGL(k_events_gain<double>, dim3(grid), dim3(kEventThreads), 0, s, g, mode, Sy, Sx,
+                           (const double *)W, (const int4 *)events, (const double *)strength, n_events,
+                           (const double *)V, (const double *)R, gain, mag);
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
