@@ -596,6 +596,63 @@ int tnmf_hip_events_grad_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mod
                            const int *plane_start, const void *strength, long long n_events, const void *V, const void *R,
                            void *workspace, void *negpos_eff, void *stream);
 
+/* ---- pursuit: forward selection of events (ABI 8, additive: the version stays 8) ------------------------------------------
+ * The forward half of greedy selection, tnmf_hip_events_gain being the backward one: a round of convolutional matching
+ * pursuit scores EVERY possible event (n, p, u) against the residual d = V - R of the list so far.  With phi_{p,u} the
+ * occurrence of plane p at shift u exactly as tnmf_hip_events_gain defines it -- all images, clipped to the sample, images
+ * that overlap added before they are squared -- a = <phi, d> and b = ||phi||^2, adding the event at its best strength
+ * h = a / b lowers E = 1/2 ||V - R||^2 by g = a^2 / (2 b), for a > 0.  The dense map a[N, P, *S] is the H gradient's
+ * numerator of the residual (tnmf_hip_grad_H with d in the place of the samples, folded for the mode by tnmf_hip_fold_H): it
+ * is not an entry point of its own.  1 or 2 shift axes, float32 and float64, every mode.  All three calls are asynchronous,
+ * use no workspace and no float atomics -- the same operands give the same bits run after run -- and write every element of
+ * their outputs, which need no initialisation.
+ *
+ * tnmf_hip_events_norms: b[P, *S] (DOUBLES, C-contiguous, S the shift shape of `mode`) = ||phi_{p,u}||^2, summed in double in
+ * a fixed order; 0 where the occurrence has no pixel inside the sample.  A shift whose single image lies wholly inside the
+ * sample has the norm of the plane, sum w^2, taken once per plane; every other shift -- clipped, wrapped or mirrored -- goes
+ * through the image walk.  geom as for the events (h_row_stride is not read).
+ * Refused before anything is written: TNMF_E_NULL (ctx, geom, W_eff, b), TNMF_E_DTYPE, TNMF_E_UNSUPPORTED for volumes, for
+ * more than 65535 planes and for a shift shape beyond 2^31 - 1 entries, TNMF_E_GEOM for any other ndim, sizes <= 0, an
+ * unknown mode and the per-axis limits of the mode.
+ *
+ * tnmf_hip_pursuit_score: the gain map of a round.  a and gain_out are [N, P, *S] in the element type, viewed as
+ * tnmf_hip_find_peaks views H: P = geom->M planes of shift shape S = D + A - 1 (for a mode other than 'valid' the caller
+ * passes D = S and A = 1 on every axis), rows `h_row_stride` apart -- pad columns are neither read nor written.  b is the
+ * table of tnmf_hip_events_norms, [P, *S] doubles, C-contiguous.  C is not read.
+ *   gain_out = (element type)((double)a * (double)a / (2 * b))   where a > 0 and b > 0 (one rounding of the double quotient),
+ *   gain_out = 0   elsewhere -- NaN compares false, so a NaN in a gives 0.
+ * Then, on the same stream, the entries at the n_taken flat C-order indices of `taken` (in [N, P, *S], as tnmf_hip_find_peaks
+ * reports them: the rows of the list so far) are set to 0, which keeps the rows of the list distinct; an index out of range
+ * is skipped.  gain_out may be a itself.  A streaming pass: 16-byte accesses where a, gain_out and the row stride allow.
+ * Refused before anything is written: TNMF_E_NULL (ctx, geom, and with N > 0 a, b, gain_out, and taken when n_taken > 0),
+ * TNMF_E_DTYPE, TNMF_E_UNSUPPORTED for volumes and for more than 2^31 - 1 rows per sample, TNMF_E_GEOM for any other ndim,
+ * sizes <= 0, a negative n_taken and a row stride below the shift width.
+ *
+ * tnmf_hip_pursuit_pick: the exact score of the candidates a round keeps -- the map only ranks; in float32 its entries carry
+ * the rounding of the correlation, which the strengths and the energy bookkeeping must not.  idx: n_picked flat C-order
+ * indices in [N, P, *S], S the shift shape of `mode`; R: the render of the list so far (tnmf_hip_events_render).  Per index,
+ * with the sums of tnmf_hip_events_gain taken in double in its fixed order (d = (double)V - (double)R),
+ *   events_out[i] = the four ints (n, p, u_0, u_1) of tnmf_hip_events_update (ndim == 1: (n, p, 0, u_0)),
+ *   a = sum_i sum_t w_t * d(px(i, t)),   b = sum_i sum_t w_t * phi(px(i, t)),
+ *   strength_out[i] = max(a, 0) / b rounded once to the element type (0 where b is 0),
+ *   gain_out[i] = a > 0 ? a^2 / (2 b) : 0,   mag_out[i] = sum_i sum_t |w_t * d(px(i, t))|   (DOUBLES; mag_out may be NULL)
+ * -- mag is the scale of the rounding error of a.  An index out of range gives a row of -1 and 0 for strength, gain and mag
+ * (no sample data is read for it).  geom as for the events (h_row_stride is not read).  With n_picked == 0 it does nothing.
+ * Refused before anything is written: TNMF_E_NULL (ctx, geom, and with n_picked > 0 idx and every output but mag_out, and with
+ * N > 0 W_eff, V and R as well), TNMF_E_DTYPE, TNMF_E_UNSUPPORTED for volumes, for more than 2^31 - 1 indices and for a
+ * shift shape beyond 2^31 - 1 entries, TNMF_E_GEOM for any other ndim, sizes <= 0, a negative count, an unknown mode and the
+ * per-axis limits of the mode. */
+int tnmf_hip_events_norms(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff,
+                          double *b /* [P, *S] */, void *stream);
+
+int tnmf_hip_pursuit_score(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *a, const double *b, void *gain_out,
+                           const long long *taken, long long n_taken, void *stream);
+
+int tnmf_hip_pursuit_pick(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const long long *idx,
+                          long long n_picked, const void *V, const void *R, int *events_out /* int4 rows */,
+                          void *strength_out, double *gain_out /* double */, double *mag_out /* double, may be NULL */,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

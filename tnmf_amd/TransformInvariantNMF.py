@@ -6,7 +6,8 @@ inhibition_range, backend, logger, verbose, **backend_kwargs)`` with ``fit`` / `
 ``fit_stream``, the read-outs ``W``, ``H``, ``V``, ``R``, ``R_partial(i)`` and the ``MiniBatchAlgorithm`` enum; beyond it
 ``detections()`` (-> ``Detections``), the events read off ``H``, and ``reconstruct_detections`` / ``refit_detections``,
 what such a list explains and its strengths refitted on the fixed support, and ``detection_gains`` / ``prune_detections``,
-what each row explains and the list without the rows the data does not need.
+what each row explains and the list without the rows the data does not need, and ``pursue_detections``, the list found by
+forward selection, without a dense fit of H.
 The only backend shipped is ``'hip'`` (tnmf_amd/backends/HIP.py); any object implementing
 tnmf_amd.backends._Backend.Backend can be passed instead of a name.
 
@@ -255,6 +256,152 @@ def event_boxes(shift: np.ndarray, atom_shape: Tuple[int, ...], sample_shape: Tu
     return lo, hi
 
 
+def _occurrence(W: np.ndarray, sample_shape: Tuple[int, ...], shift_shape: Tuple[int, ...], mode: str, plane: int,
+                shift) -> np.ndarray:
+    """phi [C, *D] in float64: plane ``plane`` of ``W`` at ``shift`` -- all its images (``event_images``), clipped to the
+    sample, images that overlap added."""
+    A, D = tuple(W.shape[2:]), tuple(sample_shape)
+    phi = np.zeros((W.shape[1],) + D)
+    for at in event_images(np.asarray(shift).reshape(1, -1), A, shift_shape, mode)[1]:
+        origin = [int(x) - (a - 1) for x, a in zip(at, A)]
+        lo = [max(o, 0) for o in origin]
+        hi = [min(o + a, d) for o, a, d in zip(origin, A, D)]
+        if all(b > a for a, b in zip(lo, hi)):
+            phi[(slice(None),) + tuple(slice(a, b) for a, b in zip(lo, hi))] += W[
+                (int(plane), slice(None)) + tuple(slice(a - o, b - o) for a, b, o in zip(lo, hi, origin))]
+    return phi
+
+
+def events_norms_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], mode: str) -> np.ndarray:
+    """b [P, *S] float64: ``||phi_{p,u}||^2`` of every plane and shift, on the host, for backends without ``event_norms`` --
+    the semantics of tnmf_hip_events_norms (include/tnmf_hip.h, "pursuit"): the plane's sum of squares where the single
+    image of the shift lies wholly inside the sample, the occurrence summed into a dense sample everywhere else; 0 where
+    it has no pixel there.  Not on the hip path."""
+    W = np.asarray(W, dtype=np.float64)
+    A, D = tuple(W.shape[2:]), tuple(sample_shape)
+    S = tuple(d + a - 1 if mode == 'valid' else d - a + 1 if mode == 'full' else d for d, a in zip(D, A))
+    b = np.empty((W.shape[0],) + S)
+    shifts = np.stack(np.unravel_index(np.arange(int(np.prod(S))), S), axis=1)
+    event, q = event_images(shifts, A, S, mode)
+    whole = np.bincount(event, minlength=len(shifts)) == 1
+    first = q[:len(shifts)]   # (event_images lists the first image of every event, in event order, before the others)
+    whole &= np.all((first - (np.asarray(A) - 1) >= 0) & (first + 1 <= np.asarray(D)), axis=1)
+    for p in range(W.shape[0]):
+        flat = b[p].reshape(-1)
+        flat[whole] = np.sum(W[p] * W[p])
+        for e in np.flatnonzero(~whole):
+            phi = _occurrence(W, D, S, mode, p, shifts[e])
+            flat[e] = np.sum(phi * phi)
+    return b
+
+
+def pursuit_loop(shape: Tuple[int, ...], atom_shape: Tuple[int, ...], sample_shape: Tuple[int, ...], mode: str,
+                 min_gain: float, max_events: Optional[int], max_rounds: int, refit_iterations: int, sample, plane, shift,
+                 strength, candidates: Callable, score: Callable, refit: Callable):
+    """The rounds of ``TransformInvariantNMF.pursue_detections`` on the host, shared by every backend: the list (local
+    sample, plane, shift, strength) grows by each round's winners.  ``shape`` is ``[N, P, *S]``.  The arithmetic is the
+    caller's: ``candidates(sample, plane, shift, strength)`` -> (flat indices, gains) of the peaks of the gain map of the
+    residual of that list; ``score(sample, plane, shift, strength, idx)`` -> (strengths ``a / b`` in the element type,
+    exact gains in float64) of the entries ``idx`` against the same residual; ``refit(sample, plane, shift, strength, n)``
+    -> the strengths after n steps.  Returns (sample, plane, shift, strength, history [rounds, 3])."""
+    k = len(atom_shape)
+    S = tuple(int(x) for x in shape[2:])
+    history = []
+    for _ in range(max_rounds):
+        if max_events is not None and len(sample) >= max_events:
+            break
+        idx, val = candidates(sample, plane, shift, strength)
+        idx, val = np.asarray(idx, dtype=np.int64), np.asarray(val, dtype=np.float64)
+        at = np.unravel_index(idx, shape)
+        found = np.stack([a.astype(np.int64) for a in at[2:]], axis=1).reshape(len(idx), k)
+        lo, hi = event_boxes(found, atom_shape, sample_shape, S, mode)
+        # peaks are >= A apart on some axis, which does not see the wrapped and mirrored images: per sample the candidates in
+        # descending gain, ties in ascending index, kept unless their box meets one already kept in this round
+        kept, boxes = [], {}   # boxes: per sample the candidates kept in this round
+        for e in np.lexsort((idx, -val)):
+            mine = boxes.setdefault(int(at[0][e]), [])
+            if mine and np.any(np.all(np.maximum(lo[e], lo[mine]) < np.minimum(hi[e], hi[mine]), axis=1)):
+                continue
+            mine.append(e)
+            kept.append(e)
+        kept = np.sort(np.asarray(kept, dtype=np.int64))
+        h, gain = score(sample, plane, shift, strength, idx[kept])
+        h, gain = np.asarray(h), np.asarray(gain, dtype=np.float64)
+        above = gain > min_gain        # (the map only ranks: the exact gain decides)
+        kept, h, gain = kept[above], h[above], gain[above]
+        if max_events is not None and len(kept) > max_events - len(sample):
+            top = np.sort(np.lexsort((idx[kept], -gain))[:max_events - len(sample)])
+            kept, h, gain = kept[top], h[top], gain[top]
+        history.append((len(idx), len(kept), float(np.sum(gain))))
+        if not len(kept):
+            break
+        sample = np.concatenate([sample, at[0][kept].astype(np.int64)])
+        plane = np.concatenate([plane, at[1][kept].astype(np.int64)])
+        shift = np.concatenate([shift.reshape(-1, k), found[kept]])
+        strength = np.concatenate([strength, h.astype(strength.dtype)])
+        if refit_iterations:
+            strength = np.asarray(refit(sample, plane, shift, strength, refit_iterations)).astype(strength.dtype)
+    return sample, plane, shift, strength, np.array(history, dtype=np.float64).reshape(len(history), 3)
+
+
+def pursuit_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], n_samples: int, mode: str, sample, plane, shift, strength,
+                  V: np.ndarray, min_gain: float, max_events: Optional[int] = None, max_rounds: int = 100,
+                  refit_iterations: int = 10, eps: float = 1e-9):
+    """Forward selection on the host, for backends without ``pursue_events`` -- the semantics of the hip backend's hook and
+    of the entry points under "pursuit" in include/tnmf_hip.h, in float64: per round the residual ``d = V - R`` of the list,
+    the map ``a = <phi, d>`` as one correlation of d with every plane in the padded frame, folded onto the shifts by the
+    image table, ``g = a^2 / (2 b)``, its peaks, and the exact ``a`` and ``b`` of the kept ones from the occurrence summed
+    into a dense sample.  Returns (sample, plane, shift, strength, history).  Not on the hip path."""
+    A, D = tuple(W.shape[2:]), tuple(sample_shape)
+    k = len(A)
+    S = tuple(d + a - 1 if mode == 'valid' else d - a + 1 if mode == 'full' else d for d, a in zip(D, A))
+    W64, V64 = np.asarray(W, dtype=np.float64), np.asarray(V, dtype=np.float64)
+    shape = (n_samples, W.shape[0]) + S
+    b = events_norms_numpy(W64, D, mode)
+
+    def residual(sample, plane, shift, strength):
+        return V64 - events_numpy(W64, D, n_samples, mode, sample, plane, shift, np.asarray(strength, dtype=np.float64))
+
+    def candidates(sample, plane, shift, strength):
+        d = residual(sample, plane, shift, strength)
+        pad = np.pad(d, [(0, 0), (0, 0)] + [(a - 1, a - 1) for a in A])
+        Q = tuple(dd + a - 1 for dd, a in zip(D, A))
+        G = np.zeros((n_samples, W.shape[0]) + Q)   # the correlation at every position of the padded frame
+        for j in itertools.product(*[range(a) for a in A]):
+            window = pad[(slice(None), slice(None)) + tuple(slice(jj, jj + q) for jj, q in zip(j, Q))]
+            G += np.einsum('pc,nc...->np...', W64[(slice(None), slice(None)) + j], window)
+        for i, (a, s) in enumerate(zip(A, S)):      # the fold of the mode, axis by axis
+            u = np.arange(s)
+            out = np.take(G, u if mode == 'valid' else u + (a - 1), axis=2 + i)
+            if mode in ('circular', 'reflect'):
+                more = np.flatnonzero(u >= s - (a - 1)) if mode == 'circular' else np.flatnonzero((u >= 1) & (u <= a - 1))
+                second = more - (s - (a - 1)) if mode == 'circular' else (a - 1) - more
+                where = (slice(None),) * (2 + i) + (more,)
+                out[where] += np.take(G, second, axis=2 + i)
+            G = out
+        with np.errstate(divide='ignore', invalid='ignore'):
+            g = np.where((G > 0) & (b > 0), G * G / (2. * b), 0.)
+        g[(sample, plane) + tuple(np.asarray(shift).reshape(-1, k).T)] = 0.
+        return find_peaks_numpy(g, min_gain, tuple(a - 1 for a in A), W.shape[0])
+
+    def score(sample, plane, shift, strength, idx):
+        d = residual(sample, plane, shift, strength)
+        h, gain = np.zeros(len(idx), dtype=W.dtype), np.zeros(len(idx))
+        for i, at in enumerate(zip(*np.unravel_index(idx, shape))):
+            phi = _occurrence(W64, D, S, mode, at[1], at[2:])
+            a_, b_ = float(np.sum(phi * d[at[0]])), float(np.sum(phi * phi))
+            if a_ > 0 and b_ > 0:
+                h[i], gain[i] = a_ / b_, a_ * a_ / (2. * b_)
+        return h, gain
+
+    def refit(sample, plane, shift, strength, n):
+        return events_numpy(W, D, n_samples, mode, sample, plane, shift, strength, V=V, n_iterations=n, eps=eps)
+    return pursuit_loop(shape, A, D, mode, min_gain, max_events, max_rounds, refit_iterations,
+                        np.asarray(sample, dtype=np.int64), np.asarray(plane, dtype=np.int64),
+                        np.asarray(shift, dtype=np.int64).reshape(-1, k), np.asarray(strength, dtype=W.dtype), candidates,
+                        score, refit)
+
+
 def events_fit_numpy(W: np.ndarray, transforms, sample_shape: Tuple[int, ...], n_samples: int, mode: str, sample, plane,
                      shift, strength, V: np.ndarray, n_iterations: int, update_H: bool = True, update_W: bool = True,
                      sparsity: float = 0., eps: float = 1e-9, normalize: Optional[Callable] = None):
@@ -418,6 +565,7 @@ class TransformInvariantNMF:
         self.n_iter_ = 0
         self.converged_ = False
         self._objective_buf = None   # the tap's per-sample buffer of the current fit
+        self.pursuit_history_ = np.empty((0, 3))   # of the last pursue_detections
 
     # -- read-outs (reference :188-215) ---------------------------------------------------------------------
     @property
@@ -714,6 +862,78 @@ class TransformInvariantNMF:
             det = Detections(**{f.name: getattr(det, f.name)[keep] for f in dataclasses.fields(Detections)})
             rounds += 1
         return det, gains
+
+    def pursue_detections(self, min_gain: float, max_events: Optional[int] = None, max_rounds: int = 100,
+                          refit_iterations: int = 10, n_iterations: int = 50, sparsity_H: float = 0.,
+                          start=None) -> Tuple[Detections, np.ndarray]:
+        """Forward selection: the detections the data asks for, found without a dense fit of H -- convolutional matching
+        pursuit in its batched, locally greedy form -- and their gains, the pair ``prune_detections`` returns.  It works on
+        the model's own V and its current dictionary; to detect in new data with a learnt dictionary call
+        ``fit_batch(V_new, n_iterations=0, keep_W=True)`` first.  The list starts as ``start`` (a ``Detections`` with
+        distinct rows) or empty.  Each round takes the residual ``V - R`` of the list, R being its render, and scores
+        every possible row: with phi, ``a = <phi, V - R>`` and ``b = ||phi||^2`` as in ``detection_gains``, adding the row at
+        its best strength ``a / b`` lowers the objective by ``a^2 / (2 b)`` (0 where ``a <= 0``, and for the rows already in
+        the list).  The candidates are the entries of that gain map above ``min_gain`` that are the largest within
+        ``atom_shape - 1`` on every shift axis over all atoms and orientations; per sample they are walked in descending gain
+        (ties in index order) and kept unless the bounding box of their occurrence in the sample meets that of a candidate
+        already kept in this round -- which the spacing alone does not rule out for wrapped and mirrored occurrences.  Rows
+        with disjoint footprints do not interact, so adding them together is exact: the objective falls by the sum of
+        their gains.  The map only ranks; the strength and the gain of a kept row are computed again in double, and a row
+        whose exact gain is not above ``min_gain`` is dropped.  The list is then refitted for ``refit_iterations`` steps (the
+        step of ``refit_detections``; 0: not at all) and the next round begins.  It stops when a round keeps nothing, after
+        ``max_rounds`` rounds or with ``max_events`` rows (the last round then keeps its highest gains).  At the end the
+        list is refitted once more (``refit_detections`` with ``n_iterations`` and ``sparsity_H``) and scored
+        (``detection_gains``).  ``min_gain`` is in the units of the objective, the same for every atom.  Read-out:
+        ``pursuit_history_`` ([rounds, 3]: candidates found, rows added, the sum of their exact gains).  On a backend with
+        ``pursue_events`` the map, its peaks and the scores are computed on the device; only the candidates (index, gain)
+        and the kept rows are copied.
+        The model's dense ``H`` is left as it is.  The plain Frobenius objective only.  With a process group every rank
+        pursues its own samples: the call is not collective."""
+        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
+            raise NotImplementedError('pursue_detections covers the plain Frobenius objective (beta_loss 2, no weights)')
+        if (isinstance(min_gain, (bool, np.bool_)) or not isinstance(min_gain, numbers.Real)
+                or not math.isfinite(min_gain) or not min_gain > 0):
+            raise ValueError(f'min_gain must be a finite number > 0, not {min_gain!r}')
+        for name, value in (('max_rounds', max_rounds), ('refit_iterations', refit_iterations),
+                            ('n_iterations', n_iterations)) + ((('max_events', max_events),) if max_events is not None
+                                                               else ()):
+            if isinstance(value, (bool, np.bool_)) or not isinstance(value, numbers.Integral) or value < 0:
+                raise ValueError(f'{name} must be an int >= 0, not {value!r}')
+        if (isinstance(sparsity_H, (bool, np.bool_)) or not isinstance(sparsity_H, numbers.Real)
+                or not math.isfinite(sparsity_H) or sparsity_H < 0):
+            raise ValueError(f'sparsity_H must be a finite number >= 0, not {sparsity_H!r}')
+        k = len(self.atom_shape)
+        if start is None:
+            start = Detections(sample=np.zeros(0, dtype=np.int64), atom=np.zeros(0, dtype=np.int64),
+                               transform=np.zeros(0, dtype=np.int64), shift=np.zeros((0, k), dtype=np.int64),
+                               origin=np.zeros((0, k), dtype=np.int64), strength=np.zeros(0))
+        sample, plane, shift, strength = self._events_of(start, distinct=True)
+        mode = getattr(self._backend, '_reconstruction_mode', 'valid')
+        max_events = None if max_events is None else int(max_events)
+        hook = getattr(self._backend, 'pursue_events', None)
+        if hook is not None:
+            sample, plane, shift, strength, history = hook(
+                self._V, self._W_dict, sample, plane, shift, strength, float(min_gain), max_events=max_events,
+                max_rounds=int(max_rounds), refit_iterations=int(refit_iterations), eps=self.eps)
+        else:
+            sample, plane, shift, strength, history = pursuit_numpy(
+                self._backend.to_ndarray(self._W_dict), self._V.shape[2:], int(self._H.shape[0]), mode, sample, plane, shift,
+                strength, self._local_V(), float(min_gain), max_events=max_events, max_rounds=int(max_rounds),
+                refit_iterations=int(refit_iterations), eps=self.eps)
+        self.pursuit_history_ = history
+        sample = np.asarray(sample, dtype=np.int64)
+        if self._shuffle_idx is not None:   # (the inverse of _events_of: internal sample a[i] is shown at place i)
+            place = np.empty(int(self._H.shape[0]), dtype=np.int64)
+            place[np.argsort(self._shuffle_idx)] = np.arange(int(self._H.shape[0]))
+            sample = place[sample]
+        sample = sample + int(getattr(self._backend, 'shard', (0, 0))[0])
+        plane, shift = np.asarray(plane, dtype=np.int64), np.asarray(shift, dtype=np.int64).reshape(len(sample), k)
+        offset = np.array([a - 1 if mode == 'valid' else 0 for a in self.atom_shape], dtype=np.int64)
+        T = self.n_transforms
+        det = Detections(sample=sample, atom=plane // T, transform=plane % T, shift=shift, origin=shift - offset,
+                         strength=np.asarray(strength))
+        det = self.refit_detections(det, n_iterations, sparsity_H)
+        return det, self.detection_gains(det)
 
     def fit_detections(self, det, n_iterations: int = 50, sparsity_H: float = 0., update_H: bool = True,
                        update_W: bool = True) -> Detections:

@@ -975,6 +975,134 @@ class HIP_Backend(Backend):
         R = self.render_event_list(W, images, cell_start, strength)
         return self.gain_event_list(W, events, strength, R).cpu().numpy()
 
+    # -- pursuit: the list found by forward selection ---------------------------------------------------------------------
+    # A round (include/tnmf_hip.h, "pursuit") is the H gradient's numerator of the residual, the gain map, its peaks and
+    # the exact score of the kept ones; the rows are chosen on the host (TransformInvariantNMF.pursuit_loop) from the
+    # peaks alone -- the map, activation-sized, never leaves the device.
+    def event_norms(self, W: torch.Tensor) -> torch.Tensor:
+        """b[P, *S] float64 on the device: ||phi||^2 of every plane of ``W`` at every shift of this mode ->
+        tnmf_hip_events_norms."""
+        self._check_W(W)
+        if len(self.atom_shape) == 3:
+            raise NotImplementedError('events: 1 or 2 shift axes only')
+        b = torch.empty((W.shape[0],) + self._transform_shape, dtype=torch.float64, device=self._device)
+        with self._timed('events_norms'):
+            _lib.check(self._lib.tnmf_hip_events_norms(
+                self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0])), self._mode, _ptr(W), _ptr(b),
+                self._stream()), 'tnmf_hip_events_norms')
+        return b
+
+    def pursuit_buffers(self, n_planes: int):
+        """The activation-sized work arrays of a pursuit, allocated once for all its rounds: (neg, pos) of the padded shape
+        for tnmf_hip_grad_H and, in a mode that folds, the map of the mode's shift shape (else None: neg is the map)."""
+        shape = (self.n_local_samples, n_planes)
+        neg = torch.empty(shape + self._padded_shape, dtype=self._torch_dtype, device=self._device)
+        pos = torch.empty_like(neg)
+        folded = None if self._mode == 0 else torch.empty(shape + self._transform_shape, dtype=self._torch_dtype,
+                                                          device=self._device)
+        return neg, pos, folded
+
+    def _correlate_residual(self, W: torch.Tensor, d: torch.Tensor, buffers=None) -> torch.Tensor:
+        """a[n, P, *S]: the correlation of the residual ``d[n, C, *D]`` with every plane of W, folded for the mode -- the
+        numerator of tnmf_hip_grad_H with d in the place of the samples (and of R: the second output is not used), written
+        into ``buffers`` (pursuit_buffers; made here when not given).  The FFT family may keep the spectra of the samples it
+        is given by pointer; d changes every round at the same address, so whatever the library holds is dropped before the
+        call, and after it, when it describes d and not the fit."""
+        n, P = d.shape[0], W.shape[0]
+        neg, pos, folded = self.pursuit_buffers(P) if buffers is None else buffers
+        assert tuple(neg.shape) == (n, P) + self._padded_shape and neg.is_contiguous() and pos.shape == neg.shape
+        self._foreign_H()
+        try:
+            with self._timed('pursuit_correlate'):
+                _lib.check(self._lib.tnmf_hip_grad_H(self._ctx, ctypes.byref(self._geom(n, P)), _ptr(d), _ptr(d), _ptr(W),
+                                                     None, _ptr(neg), _ptr(pos), self._stream()), 'tnmf_hip_grad_H')
+        finally:
+            self._foreign_H()
+        if folded is None:
+            return neg
+        _lib.check(self._lib.tnmf_hip_fold_H(self._ctx, ctypes.byref(self._geom(n, P)), self._mode, _ptr(neg), _ptr(folded),
+                                             self._stream()), 'tnmf_hip_fold_H')
+        return folded
+
+    def pursuit_round(self, W: torch.Tensor, b: torch.Tensor, d: torch.Tensor, taken: torch.Tensor, min_gain: float,
+                      buffers=None) -> Tuple[np.ndarray, np.ndarray]:
+        """(idx, val) on the host: the candidates of a round -- the peaks above ``min_gain``, within ``atom_shape - 1`` over
+        all planes, of the gain map ``a^2 / (2 b)`` of the residual ``d`` with the entries ``taken`` (int64 flat indices, the
+        rows of the list) zeroed -> tnmf_hip_grad_H, tnmf_hip_pursuit_score (in place on the map), tnmf_hip_find_peaks."""
+        k = len(self.atom_shape)
+        a = self._correlate_residual(W, d, buffers)
+        assert a.is_contiguous() and tuple(a.shape[1:]) == tuple(b.shape) and b.dtype == torch.float64
+        assert taken.dtype == torch.int64 and taken.is_contiguous()
+        g = _lib.make_geom(int(a.shape[0]), int(a.shape[1]), self.n_channels, tuple(a.shape[2:]), (1,) * k,
+                           self._dtype_code, 0)
+        with self._timed('pursuit_score'):
+            _lib.check(self._lib.tnmf_hip_pursuit_score(self._ctx, ctypes.byref(g), _ptr(a), _ptr(b), _ptr(a), _ptr(taken),
+                                                        taken.numel(), self._stream()), 'tnmf_hip_pursuit_score')
+        return self.find_peaks(a, float(min_gain), tuple(x - 1 for x in self.atom_shape), int(a.shape[1]))
+
+    def pick_events(self, W: torch.Tensor, idx: torch.Tensor, R: torch.Tensor, with_magnitude: bool = False):
+        """(events [K, 4] int32, strength [K], gain [K] float64) on the device for the flat indices ``idx`` (int64) in
+        [n_local, P, *S]: the rows, their best strengths against the residual of the render R and what adding them gains,
+        summed in double -> tnmf_hip_pursuit_pick; with ``with_magnitude`` also mag, the scale of the rounding error."""
+        self._check_W(W)
+        assert idx.dtype == torch.int64 and idx.is_contiguous() and R.is_contiguous() and R.dtype == self._torch_dtype
+        assert tuple(R.shape) == tuple(self._V_dev.shape)
+        K = idx.numel()
+        events = torch.empty((K, 4), dtype=torch.int32, device=self._device)
+        strength = torch.empty(K, dtype=self._torch_dtype, device=self._device)
+        gain = torch.empty(K, dtype=torch.float64, device=self._device)
+        mag = torch.empty(K, dtype=torch.float64, device=self._device) if with_magnitude else None
+        with self._timed('pursuit_pick'):
+            _lib.check(self._lib.tnmf_hip_pursuit_pick(
+                self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0])), self._mode, _ptr(W), _ptr(idx), K,
+                _ptr(self._V_dev), _ptr(R), _ptr(events), _ptr(strength), _ptr(gain), _ptr(mag), self._stream()),
+                'tnmf_hip_pursuit_pick')
+        return (events, strength, gain, mag) if with_magnitude else (events, strength, gain)
+
+    def pursue_events(self, V, W: torch.Tensor, sample, plane, shift, strength, min_gain: float,
+                      max_events: Optional[int] = None, max_rounds: int = 100, refit_iterations: int = 10,
+                      eps: float = 1e-9):
+        """(sample, plane, shift, strength, history) on the host: the list (this rank's local samples) grown from the given
+        one by forward selection against the resident samples (`V` is the array given to initialize(), as for the other
+        hooks) -- per round one render of the list, the residual, pursuit_round, the host's choice among the candidates,
+        pick_events for the kept ones and refit_events for the list; only candidates and kept rows cross to the host.  The
+        resident samples and the model's activations are left as they are.  The plain Frobenius objective."""
+        from ..TransformInvariantNMF import pursuit_loop
+        if self._G_dev is not None:
+            raise NotImplementedError('pursue_events is unweighted')
+        P, k = int(W.shape[0]), len(self.atom_shape)
+        sample, plane, shift, strength = self._check_events(P, sample, plane, shift, strength)
+        b = self.event_norms(W)
+        R, d = torch.empty_like(self._V_dev), torch.empty_like(self._V_dev)
+        buffers = self.pursuit_buffers(P)   # (activation-sized: once for all the rounds)
+        shape = (self.n_local_samples, P) + self._transform_shape
+
+        def candidates(sample, plane, shift, strength):
+            s, p, u, h = self._check_events(P, sample, plane, shift, strength)
+            if s.numel():
+                images, cell_start, _ = self.event_list(s, p, u)
+                self.render_event_list(W, images, cell_start, h, R)
+            else:
+                R.zero_()
+            d.copy_(R)      # d = V - R, rounded once
+            _lib.check(self._lib.tnmf_hip_axpby(self._ctx, self._dtype_code, _ptr(d), _ptr(self._V_dev), -1., 1., d.numel(),
+                                                self._stream()), 'tnmf_hip_axpby')
+            taken = s * P + p
+            for i in range(k):
+                taken = taken * self._transform_shape[i] + u[:, i]
+            return self.pursuit_round(W, b, d, taken.contiguous(), min_gain, buffers)
+
+        def score(sample, plane, shift, strength, idx):   # (R is the render of this list: candidates() came first)
+            at = torch.as_tensor(np.ascontiguousarray(idx, dtype=np.int64)).to(self._device)
+            _, h, gain = self.pick_events(W, at, R)
+            return h.cpu().numpy(), gain.cpu().numpy()
+
+        def refit(sample, plane, shift, strength, n):
+            return self.refit_events(V, W, sample, plane, shift, strength, n, 0., eps).cpu().numpy()
+        return pursuit_loop(shape, self.atom_shape, self._sample_shape, self._reconstruction_mode, min_gain, max_events,
+                            max_rounds, refit_iterations, sample.cpu().numpy(), plane.cpu().numpy(),
+                            shift.cpu().numpy().reshape(-1, k), strength.cpu().numpy(), candidates, score, refit)
+
     # -- events: the dictionary learnt from the detections ------------------------------------------------------------------
     def event_plane_list(self, plane: torch.Tensor, n_planes: int):
         """The plane list tnmf_hip_events_grad_W takes, built on the device for checked events: (by_plane [K] int32, the

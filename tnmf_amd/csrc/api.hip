@@ -1449,4 +1449,58 @@ int tnmf_hip_events_grad_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mod
                          workspace, negpos_eff, static_cast<hipStream_t>(stream));
 }
 
+int tnmf_hip_events_norms(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, double *b,
+                          void *stream) {
+    if (!ctx || !geom) return TNMF_E_NULL;
+    EventGeo g;
+    const int rc = events_geo(geom, &g);
+    if (rc != TNMF_OK) return rc;
+    int S[2];
+    if (events_shift_shape(g, mode, S) != TNMF_OK) return TNMF_E_GEOM;
+    if ((long long)S[0] * S[1] > 0x7fffffffLL || g.P > 65535) return TNMF_E_UNSUPPORTED;
+    if (!W_eff || !b) return TNMF_E_NULL;
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return events_norms(ctx, g, geom->dtype, mode, S[0], S[1], W_eff, b, static_cast<hipStream_t>(stream));
+}
+
+int tnmf_hip_pursuit_score(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *a, const double *b, void *gain_out,
+                           const long long *taken, long long n_taken, void *stream) {
+    if (!ctx || !geom) return TNMF_E_NULL;
+    if (geom->dtype != 0 && geom->dtype != 1) return TNMF_E_DTYPE;
+    if (geom->ndim == 3) return TNMF_E_UNSUPPORTED;
+    if (geom->ndim != 1 && geom->ndim != 2) return TNMF_E_GEOM;
+    if (geom->N < 0 || geom->M <= 0 || n_taken < 0) return TNMF_E_GEOM;
+    int S[2] = {1, 1};   // a leading axis of extent 1: one scheme for 1 and 2 shift axes
+    for (int i = 0; i < geom->ndim; ++i) {
+        if (geom->D[i] <= 0 || geom->A[i] <= 0) return TNMF_E_GEOM;
+        if ((long long)geom->D[i] + geom->A[i] - 1 > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
+        S[2 - geom->ndim + i] = geom->D[i] + geom->A[i] - 1;
+    }
+    if (geom->h_row_stride > 0 && geom->h_row_stride < S[1]) return TNMF_E_GEOM;
+    if ((long long)geom->M * S[0] > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
+    if (geom->N > 0 && (!a || !b || !gain_out || (n_taken > 0 && !taken))) return TNMF_E_NULL;
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return pursuit_score(ctx, geom->dtype, (long long)geom->N * geom->M, geom->M, S[0], S[1],
+                         geom->h_row_stride > 0 ? geom->h_row_stride : S[1], a, b, gain_out, taken, n_taken,
+                         static_cast<hipStream_t>(stream));
+}
+
+int tnmf_hip_pursuit_pick(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const long long *idx,
+                          long long n_picked, const void *V, const void *R, int *events_out, void *strength_out,
+                          double *gain_out, double *mag_out, void *stream) {
+    if (!ctx || !geom) return TNMF_E_NULL;
+    EventGeo g;
+    const int rc = events_geo(geom, &g);
+    if (rc != TNMF_OK) return rc;
+    if (mode < TNMF_MODE_VALID || mode > TNMF_MODE_REFLECT || n_picked < 0) return TNMF_E_GEOM;
+    int S[2];
+    if (events_shift_shape(g, mode, S) != TNMF_OK) return TNMF_E_GEOM;
+    if (n_picked > 0x7fffffffLL || (long long)S[0] * S[1] > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
+    if (n_picked > 0 && (!idx || !events_out || !strength_out || !gain_out || (g.N > 0 && (!W_eff || !V || !R))))
+        return TNMF_E_NULL;
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return pursuit_pick(ctx, g, geom->dtype, mode, S[0], S[1], W_eff, idx, n_picked, V, R, events_out, strength_out,
+                        gain_out, mag_out, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

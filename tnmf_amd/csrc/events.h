@@ -49,3 +49,19 @@ long long events_grad_W_slabs(long long n_events, int P);
 int events_grad_W(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const int *events,
                   const int *by_plane, const int *plane_start, const void *strength, long long n_events, const void *V,
                   const void *R, void *workspace, void *negpos, hipStream_t s);
+
+// Pursuit (pursuit.hip; tnmf_hip_events_norms / tnmf_hip_pursuit_score / tnmf_hip_pursuit_pick).
+// b[P, Sy, Sx] = |phi_{p,u}|^2 in double: the norm of the occurrence of plane p at shift u, all images, clipped to the sample.
+int events_norms(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const void *W, double *b,
+                 hipStream_t s);
+
+// gain[planes, Sy, Sx] = a^2 / (2 b) where a > 0 and b > 0, else 0 (rows Hs apart; b[P, Sy, Sx] contiguous, planes a multiple
+// of P), then the n_taken flat indices of `taken` zeroed.
+int pursuit_score(tnmf_hip_ctx *ctx, int dtype, long long planes, int P, int Sy, int Sx, int Hs, const void *a,
+                  const double *b, void *gain, const long long *taken, long long n_taken, hipStream_t s);
+
+// per picked flat index of [N, P, Sy, Sx]: the row (n, p, uy, ux), a = <phi, V - R> and b = |phi|^2 in double, the strength
+// max(a, 0) / b, the gain a^2 / (2 b) and mag (may be NULL) = sum |w (V - R)|; -1 / 0 for an index out of range.
+int pursuit_pick(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const void *W,
+                 const long long *idx, long long n_picked, const void *V, const void *R, int *events, void *strength,
+                 double *gain, double *mag, hipStream_t s);
