@@ -60,6 +60,24 @@ int mixed_reconstruct(const Geo &g, const void *Tsp, const void *WT, void *OT, i
 int mixed_grad_W(const Geo &g, const void *Tsp, const void *VT, const void *RT, void *Gn, void *Gp, int KX, int KXP,
                  int ngroups, int nper, hipStream_t s);
 
+// k_mix_grad_W3, the three-multiply W gradient of large calls: 16 kx x kMixW3Atoms atoms per workgroup (one wave per
+// SIMD), taken from kMixW3MinBytes of row spectra of H on.  mixed_grad_W3_takes() decides for the launch
+// (fft_mixed.hip) and for the group count (fft.hip: mix_groups_w3) alike.  mix_w3_waves(): the workgroups of
+// k_mix_grad_W3<float, Ay> a CU holds (= waves per SIMD), as hipcc's kernel-resource-usage remarks report them
+// (ROCm 7.2: 70 / 86, 92 / 102 .. 120 / 130 .. 158 VGPRs for Ay = 1 / 2, 3 / 4 .. 7 / 8 .. 12, 12 KiB of LDS; read
+// them again when the kernel or the compiler changes); kMixW3Waves is the floor __launch_bounds__ asks for.
+// TNMF_MIX_W3_WAVES=2: A/B flavour of the library (Makefile: VARIANT) that holds the kernel to two workgroups per CU.
+#ifndef TNMF_MIX_W3_WAVES
+#define TNMF_MIX_W3_WAVES 3
+#endif
+constexpr int kMixW3Atoms = 16, kMixW3Waves = TNMF_MIX_W3_WAVES, kMixW3MaxAy = 12;
+constexpr long kMixW3MinBytes = 24L << 20;
+constexpr int mix_w3_waves(int Ay) {
+    const int w = Ay >= 8 ? 3 : (Ay >= 4 ? 4 : (Ay >= 2 ? 5 : 7));
+    return kMixW3Waves < 3 ? kMixW3Waves : w;
+}
+bool mixed_grad_W3_takes(const Geo &g, int KXP);
+
 // streaming contractions on resident full spectra of H (fft_spectral.hip): no transform inside
 int spectral_contract_R(const Geo &g, int dtype, const void *SH, const void *SW, void *SR, int Ly, int KX, int KXP,
                         hipStream_t s);

@@ -766,6 +766,28 @@ int mix_groups(const tnmf_hip_ctx *ctx, const Geo &g, const Lay &l) {
     return best;
 }
 
+// Sample groups of k_mix_grad_W3 (calls that mixed_grad_W3_takes).  There a group is a whole workgroup of four waves,
+// one per SIMD, and mix_w3_waves(Ay) of them share a CU: the grid of (blocks of 16 atoms) x (kx tiles) x groups
+// workgroups should fill the chip's mix_w3_waves(Ay) * CUs workgroup slots a whole number of times (config 3:
+// 2 * 9 * 128 = 3 x 768).  Any count is possible (no blocks of four groups); the cost is the one of mix_groups().
+int mix_groups_w3(const tnmf_hip_ctx *ctx, const Geo &g, const Lay &l) {
+    const long slots3 = (long)mix_w3_waves(g.Ay) * (ctx->num_cu > 0 ? ctx->num_cu : 256);
+    const long per_group = (long)cdiv(g.M, kMixW3Atoms) * cdiv(l.KX, 16);
+    int best = 1;
+    double best_cost = 1e30;
+    for (int cand = g.N < kMixMaxGroups ? g.N : kMixMaxGroups; cand >= 1; --cand) {
+        const int ng = cdiv(g.N, cdiv(g.N, cand));   // the groups that hold samples when cand are asked for
+        const double rounds = (double)(per_group * ng) / (double)slots3;
+        const double whole = rounds <= 1.0 ? 1.0 : (double)(long)(rounds + 0.999999);
+        const double cost3 = whole / rounds + 0.03 * ng / 32.0;
+        if (cost3 < best_cost - 1e-9) {
+            best_cost = cost3;
+            best = ng;
+        }
+    }
+    return best;
+}
+
 int fft_grad_W(tnmf_hip_ctx *ctx, const Geo &g, int dtype, const void *V, const void *R, const void *H, void *neg,
                void *pos, bool nonneg, hipStream_t s) {
     Call c;
@@ -786,12 +808,17 @@ int fft_grad_W(tnmf_hip_ctx *ctx, const Geo &g, int dtype, const void *V, const 
         const int nper = cdiv(g.N, ng);
         ng = cdiv(g.N, nper);
         const int ngpad = (int)align_up((size_t)ng, 4);   // whole blocks of 4 groups; the extra groups write zeros
-        CHECK(mixed_grad_W(g, c.T, c.VT, c.RT, at(ctx, l.Gn), at(ctx, l.Gp), l.KX, l.KXP, ngpad, nper, s));
+        int nparts = ngpad, nper_call = nper;
+        if (mixed_grad_W3_takes(g, l.KXP)) {   // large calls: k_mix_grad_W3 and its own group count (no padding)
+            nper_call = cdiv(g.N, mix_groups_w3(ctx, g, l));
+            nparts = cdiv(g.N, nper_call);
+        }
+        CHECK(mixed_grad_W(g, c.T, c.VT, c.RT, at(ctx, l.Gn), at(ctx, l.Gp), l.KX, l.KXP, nparts, nper_call, s));
         const long count = (long)g.M * g.C * g.Ay * l.KXP;
         char *out = at(ctx, l.TW);   // [2*M*C][Ay][KXP]
         hipLaunchKernelGGL(k_fft_sum_groups<float>, dim3((unsigned)((count + 63) / 64), 2), dim3(64), 0, s,
                            (const cplx<float> *)at(ctx, l.Gn), (const cplx<float> *)at(ctx, l.Gp), (cplx<float> *)out,
-                           (cplx<float> *)(out + (size_t)count * l.csz), count, ngpad, 1.0 / l.Lx);
+                           (cplx<float> *)(out + (size_t)count * l.csz), count, nparts, 1.0 / l.Lx);
         TNMF_LAUNCH_CHECK();
     } else {
         CHECK(forward_planes(g, l, dtype, R, g.N * g.C, g.Dy, g.Dx, c.Ts, c.SR, s));

@@ -37,6 +37,13 @@ __device__ __forceinline__ void cfmac(f2v &acc, f2v a, f2v b) {
     asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[0,1,1] neg_hi:[0,1,0]" : "+v"(acc) : "v"(a), "v"(b));
     asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1]" : "+v"(acc) : "v"(a), "v"(b));
 }
+// acc += x * s, both halves of x (two streams) by the same scalar: s = b.lo / s = b.hi
+__device__ __forceinline__ void pfma_lo(f2v &acc, f2v x, f2v b) {
+    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "+v"(acc) : "v"(x), "v"(b));
+}
+__device__ __forceinline__ void pfma_hi(f2v &acc, f2v x, f2v b) {
+    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "v"(x), "v"(b));
+}
 
 #define CHECK(rc_expr)                  \
     do {                                \
@@ -453,6 +460,143 @@ __global__ __launch_bounds__(kMixCols *GROUPS, 2) void k_mix_grad_W2(const cplx<
     }
 }
 
+// Large calls (mixed_grad_W3_takes): three packed FMAs per lag where k_mix_grad_W2 issues four.  With t = p + iq from
+// T, x = c + id from V^ or R^ and s = p + q (Gauss's three-multiplication form)
+//   t * conj(x) = (pc + qd) + i(qc - pd),   pc + qd = c*s - q*(c - d),   qc - pd = c*s - p*(c + d)
+// so three REAL sums per lag and stream are accumulated, A1 += c*s, A2 += (c + d)*p, A3 += (c - d)*q, and Re = A1 - A3,
+// Im = A1 - A2 are formed once, in the epilogue.  The two streams ride in the two halves of a register pair --
+// X1 = (c_V, c_R), X2 = (c_V + d_V, c_R + d_R), X3 = (c_V - d_V, c_R - d_R) -- so a lag costs three v_pk_fma_f32 for V^
+// AND R^, the scalar (s, p or q) broadcast by op_sel.  The extra adds are one per T entry (s) and two per V^/R^ row.
+//
+// Three accumulator sets leave room for ONE atom per thread, so the V^/R^ rows, which every atom needs, are loaded
+// once per workgroup: block = 16 kx x 16 atoms, all on the same sample group, walking the same samples and rows.  Per
+// chunk of CH = 16 rows every thread loads 16 bytes of V^ or R^ (16 rows x 2 streams x 128 bytes = 256 x 16), trades
+// one entry with its neighbour lane (the other stream of the same row and kx pair), forms X1, X2, X3 of one (row, kx)
+// and writes them to an LDS ring of two chunks; one barrier per chunk, the next chunk's loads in flight under the
+// current chunk's arithmetic, three broadcast ds_read_b64 per row (the four atoms of a wave read the same addresses).
+// T: one wave-uniform descriptor per sample (based at the block's first atom), a scalar row offset, one constant
+// per-lane byte offset (atom plane, kx); rows through a ring of RS = 16 statically indexed slots (row y needs
+// T[y .. y+AY-1]; RS - AY >= 4 rows are in flight), s formed when a row enters the window -- two s per register pair,
+// picked by op_sel like p and q.  One ring period = one chunk.
+// grid: 1-D, logical (atom blocks, kx tiles, groups), atom blocks fastest, XCD remap as above; partial sums
+// [group][M][AY][KXP] as k_fft_sum_groups reads them.  Groups without samples store zeros.
+// (device pass: without hipcc's pairing of DS accesses -- a ds_read2_b64 of X1 and X2 moves half the bytes per LDS clock)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TNMF_MIX_NO_DS_PAIRING __attribute__((target("no-load-store-opt")))
+#else
+#define TNMF_MIX_NO_DS_PAIRING
+#endif
+template <typename T, int AY>
+__global__ __launch_bounds__(kMixCols *kMixW3Atoms, kMixW3Waves) TNMF_MIX_NO_DS_PAIRING void k_mix_grad_W3(
+    const cplx<T> *Tsp, const cplx<T> *VT, const cplx<T> *RT, cplx<T> *Gn, cplx<T> *Gp, int N, int M, int Hy, int Dy,
+    int KX, int KXP, int nper, int gx, int gy, int gz) {
+    constexpr int NA = kMixW3Atoms, RS = 16, CH = RS, NT = kMixCols * NA;
+    static_assert(AY + 4 <= RS && sizeof(cplx<T>) == 8 && NT == 2 * CH * (kMixCols / 2), "ring depth, float spectra");
+    const int col = threadIdx.x & (kMixCols - 1), slot = threadIdx.x / kMixCols;
+    int lin = blockIdx.x;
+    {
+        const int total = gx * gy * gz, whole = total / 8 * 8;
+        if (lin < whole) lin = (lin & 7) * (whole / 8) + (lin >> 3);
+    }
+    const int bx = lin % gx, by = (lin / gx) % gy, grp = lin / (gx * gy);
+    const int kx = by * kMixCols + col, kxc = min(kx, KX - 1);
+    const int m = bx * NA + slot, mc = min(m, M - 1);   // atom slots past M repeat the last atom (not stored)
+    f2v a1[AY], a2[AY], a3[AY];
+#pragma unroll
+    for (int a = 0; a < AY; ++a) a1[a] = a2[a] = a3[a] = {0, 0};
+    typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
+    typedef float f4v __attribute__((ext_vector_type(4)));
+    const long tplane = (long)Hy * KXP, vplane = (long)Dy * KXP;
+    const int nbeg = grp * nper, nend = min(N, nbeg + nper);
+    const int lane_t = (int)(((long)(mc - bx * NA) * tplane + kxc) * 8);   // the host checks that it fits 31 bits
+    const int rowb = KXP * 8;
+    auto ld = [](const __amdgpu_buffer_rsrc_t &rs, int lane_off, int row_off) {
+        const u32x2v w = __builtin_amdgcn_raw_buffer_load_b64(rs, lane_off, row_off, 0);
+        const unsigned re = w[0], im = w[1];   // (bit_cast straight on a vector element reads element 0: hipcc 7.2)
+        return cplx<T>{__builtin_bit_cast(float, re), __builtin_bit_cast(float, im)};
+    };
+    // V^ / R^ staging: thread = (row of the chunk, pair of kx, stream); even lanes load V^, odd lanes R^
+    __shared__ __align__(16) f2v xl[2][3][CH * kMixCols];
+    const int prow = threadIdx.x / kMixCols, ppair = (threadIdx.x >> 1) & (kMixCols / 2 - 1), pstream = threadIdx.x & 1;
+    const cplx<T> *xsrc = (pstream ? RT : VT) + by * kMixCols + 2 * ppair;   // (KXP: whole 128-byte segments)
+    f4v pre;
+    auto xfetch = [&](int n, int chunk) {   // always a legal address: rows clamped, the caller clamps n
+        pre = *reinterpret_cast<const f4v *>(xsrc + (long)n * vplane + (long)min(chunk * CH + prow, Dy - 1) * KXP);
+    };
+    auto xpark = [&](int buf) {
+        // a V^ lane keeps its first entry and takes the R^ lane's first; the R^ lane keeps its second and takes V^'s
+        auto swap1 = [](float v) {   // the value of lane ^ 1 (quad_perm [1,0,3,2]; every lane is active here)
+            return __builtin_bit_cast(float,
+                                      __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false));
+        };
+        const float oc = swap1(pstream ? pre[0] : pre[2]), od = swap1(pstream ? pre[1] : pre[3]);
+        const float cv = pstream ? oc : pre[0], dv = pstream ? od : pre[1];
+        const float cr = pstream ? pre[2] : oc, dr = pstream ? pre[3] : od;
+        const int e = prow * kMixCols + 2 * ppair + pstream;
+        xl[buf][0][e] = f2v{cv, cr};
+        xl[buf][1][e] = f2v{cv + dv, cr + dr};
+        xl[buf][2][e] = f2v{cv - dv, cr - dr};
+    };
+    xfetch(min(nbeg, N - 1), 0);
+    xpark(0);
+    __syncthreads();
+    int buf = 0;
+#pragma unroll 1
+    for (int n = nbeg; n < nend; ++n) {   // (uniform over the workgroup, like every branch below)
+        const __amdgpu_buffer_rsrc_t t0 = __builtin_amdgcn_make_buffer_rsrc(
+            (void *)(Tsp + ((long)n * M + bx * NA) * tplane), 0, 0x7fffffff, 0x00020000);
+        cplx<T> t[RS];
+        f2v sp[RS / 2];   // s of ring slot j in half j & 1 of sp[j / 2]
+        // rows 0 .. RS-2 (row indices clamped: always legal addresses), s of rows 0 .. AY-2
+#pragma unroll
+        for (int i = 0; i < RS - 1; ++i) t[i] = ld(t0, lane_t, min(i, Hy - 1) * rowb);
+#pragma unroll
+        for (int i = 0; i < AY - 1; ++i) sp[i / 2][i & 1] = t[i][0] + t[i][1];
+#pragma unroll 1
+        for (int yb = 0; yb < Dy; yb += CH) {
+            // the chunk after this one: the next rows of the sample, or the first rows of the next sample
+            {
+                const bool last = yb + CH >= Dy;
+                xfetch(last ? min(n + 1, nend - 1) : n, last ? 0 : yb / CH + 1);
+            }
+            const f2v *x1 = &xl[buf][0][col], *x2 = &xl[buf][1][col], *x3 = &xl[buf][2][col];
+            // one ring period = one chunk: every ring index below is a compile-time constant
+#pragma unroll
+            for (int i = 0; i < RS; ++i) {
+                const int y = yb + i;
+                if (y >= Dy) break;
+                t[(i + RS - 1) % RS] = ld(t0, lane_t, min(y + RS - 1, Hy - 1) * rowb);   // into the slot row y - 1 left
+                {
+                    const int j = (i + AY - 1) % RS;   // row y + AY - 1 enters the window
+                    sp[j / 2][j & 1] = t[j][0] + t[j][1];
+                }
+                const f2v c = x1[i * kMixCols], cpd = x2[i * kMixCols], cmd = x3[i * kMixCols];
+#pragma unroll
+                for (int a = 0; a < AY; ++a) {
+                    const int j = (i + a) % RS;
+                    if (j & 1)
+                        pfma_hi(a1[a], c, sp[j / 2]);
+                    else
+                        pfma_lo(a1[a], c, sp[j / 2]);
+                    pfma_lo(a2[a], cpd, t[j]);
+                    pfma_hi(a3[a], cmd, t[j]);
+                }
+            }
+            xpark(buf ^ 1);   // (its last readers passed the barrier of the previous chunk)
+            __syncthreads();
+            buf ^= 1;
+        }
+    }
+    if (kx >= KX || m >= M) return;
+    const long gplane = (long)AY * KXP, gsize = (long)M * gplane;
+#pragma unroll
+    for (int a = 0; a < AY; ++a) {
+        const long o = (long)grp * gsize + (long)m * gplane + (long)a * KXP + kx;
+        Gn[o] = cplx<T>{a1[a][0] - a3[a][0], a1[a][0] - a2[a][0]};
+        Gp[o] = cplx<T>{a1[a][1] - a3[a][1], a1[a][1] - a2[a][1]};
+    }
+}
+
 // 1-D signals (one row per plane, AY == 1), up to CG channels per thread:
 //   GT[m,c,kx] = sum_n T[n,m,kx] * conj(VT[n,c,kx])   (and with RT); no lags along y, one entry per (sample, atom, kx)
 template <typename T, int CG, int GROUPS>
@@ -499,6 +643,19 @@ int launch_mix_grad_W(const void *Tsp, const void *VT, const void *RT, void *Gn,
             hipLaunchKernelGGL((k_mix_grad_W_1d<T, 4, GROUPS>), grid, dim3(kMixCols * GROUPS), 0, s, (const cplx<T> *)Tsp,
                                (const cplx<T> *)VT, (const cplx<T> *)RT, (cplx<T> *)Gn, (cplx<T> *)Gp, g.N, g.M, g.C, KX,
                                KXP, nper);
+            TNMF_LAUNCH_CHECK();
+            return TNMF_OK;
+        }
+    }
+    if constexpr (AY <= kMixW3MaxAy) {
+        // large calls: the three-multiply kernel; ngroups / nper are those of mix_groups_w3() (fft.hip), no padding
+        if (mixed_grad_W3_takes(g, KXP)) {
+            const int gx = cdiv(g.M, kMixW3Atoms), gy = cdiv(KX, kMixCols), gz = ngroups;
+            // (kMixW3Waves == 2, an A/B flavour: 48 KiB of unused dynamic LDS keep a third workgroup off the CU)
+            hipLaunchKernelGGL((k_mix_grad_W3<T, AY>), dim3((unsigned)(gx * gy * gz)), dim3(kMixCols * kMixW3Atoms),
+                               kMixW3Waves == 2 ? 48u << 10 : 0u, s,
+                               (const cplx<T> *)Tsp, (const cplx<T> *)VT, (const cplx<T> *)RT, (cplx<T> *)Gn,
+                               (cplx<T> *)Gp, g.N, g.M, g.Hy, g.Dy, KX, KXP, nper, gx, gy, gz);
             TNMF_LAUNCH_CHECK();
             return TNMF_OK;
         }
@@ -557,6 +714,18 @@ bool mixed_has_reconstruct(const Geo &g, int dtype) {
 }
 bool mixed_has_grad_W(const Geo &g, int dtype) {
     return dtype == 0 && g.Ay <= 16 && (g.C == 1 || (g.Dy == 1 && g.Ay == 1 && g.C <= 4));
+}
+
+// k_mix_grad_W3 takes the 2-D one-channel calls with atoms up to 12 rows whose row spectra of H reach 24 MiB; below
+// that the launch is a few microseconds and the grid of k_mix_grad_W2 (a wave per workgroup, four groups in it) fills
+// the chip as well.  Its per-lane byte offsets (atom slot 15, last row) must fit 31 bits.
+bool mixed_grad_W3_takes(const Geo &g, int KXP) {
+#ifdef TNMF_MIX_NO_W3   // A/B flavour of the library (Makefile: VARIANT): every call stays on the older kernels
+    return false;
+#endif
+    const long span = (long)kMixW3Atoms * g.Hy * KXP * 8;
+    const long spectra = (long)g.N * g.M * g.Hy * KXP * 8;
+    return g.C == 1 && g.Ay <= kMixW3MaxAy && !(g.Dy == 1 && g.Ay == 1) && span < (1L << 31) && spectra >= kMixW3MinBytes;
 }
 
 int mixed_reconstruct(const Geo &g, const void *Tsp, const void *WT, void *OT, int KX, int KXP, hipStream_t s) {
