@@ -18,60 +18,60 @@ import events_reference as eref
 
 NUM_CU = 256            # compute units of one MI355X (what grid_for() reads from ctx->num_cu there)
 
-THREADS = 256           # events.h:17, kEventThreads
-CHAN = 4                # events.hip:38, kChan
-WAVES = THREADS // 64   # events.hip:39, kWaves
+THREADS = 256           # events.h, kEventThreads
+CHAN = 4                # events.hip, kChan
+WAVES = THREADS // 64   # events.hip, kWaves
 SEGMENT = 64            # include/tnmf_hip.h, TNMF_EVENTS_SEGMENT
 CELL_1D, CELL_2D = 256, 16   # include/tnmf_hip.h, TNMF_EVENTS_CELL_1D / _2D
 
 BRANCHES = {
     'render': (
         'one-image', 'two-images', 'four-images',   # event_list: the images an event stands for
-        'image-clipped',                  # :83 an image whose footprint leaves the sample
-        'threads-outside',                # :56 a tile with threads outside the sample
-        'R5:whole-tiles',                 # :56 2-D, several tiles per axis, none with a thread outside the sample
-        'R5:narrower-than-a-tile',        # :56 Dx < tx: every tile row has threads outside
-        'channels-below-a-group',         # :88 C < kChan: the guard c0 + cc < C in the first pass
-        'R1:second-channel-pass',         # :60 C > kChan
-        'R1:partial-last-channel-group',  # :88 C > kChan and C % kChan != 0
-        'R2:three-cell-rows',             # :64 cy1 - tile_y >= 2 (Ay >= ty + 2)
-        'R2:three-cell-columns',          # :66 cx1 - tile_x >= 2 (Ax >= tx + 2): a run over three cells
-        'cy1-clamped', 'cx1-clamped',     # :58-59 the min() with ncy - 1 / ncx - 1 decides
-        'empty-run', 'one-chunk',         # :67 the chunk loop takes no pass / one pass
-        'R3:second-chunk',                # :67-68 a run of more than kEventThreads images: s_img / s_h are reused
-        'R3:partial-chunk-after-a-full',  # :70, :78 ... whose last chunk is partial
-        'R4:tile-loop-strides',           # :52 more tiles than workgroups
+        'image-clipped',                  # the jy / jx test: an image whose footprint leaves the sample
+        'threads-outside',                # `inside`: a tile with threads outside the sample
+        'R5:whole-tiles',                 # `inside`: 2-D, several tiles per axis, none with a thread outside the sample
+        'R5:narrower-than-a-tile',        # `inside`: Dx < tx: every tile row has threads outside
+        'channels-below-a-group',         # C < kChan: the guard c0 + cc < C in the first pass
+        'R1:second-channel-pass',         # the c0 loop: C > kChan
+        'R1:partial-last-channel-group',  # the guard c0 + cc < C: C > kChan and C % kChan != 0
+        'R2:three-cell-rows',             # the cy loop: cy1 - tile_y >= 2 (Ay >= ty + 2)
+        'R2:three-cell-columns',          # i0 .. i1: cx1 - tile_x >= 2 (Ax >= tx + 2): a run over three cells
+        'cy1-clamped', 'cx1-clamped',     # cy1 / cx1: the min() with ncy - 1 / ncx - 1 decides
+        'empty-run', 'one-chunk',         # the `base` loop over chunks takes no pass / one pass
+        'R3:second-chunk',                # the `base` loop: a run of more than kEventThreads images: s_img / s_h are reused
+        'R3:partial-chunk-after-a-full',  # `mine < i1`, `count`: ... whose last chunk is partial
+        'R4:tile-loop-strides',           # the tile loop: more tiles than workgroups
     ),
     'update': (
-        'one-image', 'two-images', 'four-images', 'image-clipped',   # :133, :144
-        'U1:one-tap',                     # :140 taps == 1: lane 0 alone gathers
-        'U1:idle-lanes',                  # :140 taps < 64: lanes without a tap take part in the butterfly
-        'lane-loop-strides',              # :140 taps > 64
-        'U2:event-loop-strides',          # :127 more events than waves
+        'one-image', 'two-images', 'four-images', 'image-clipped',   # event_walk.h: Occurrence, for_each_tap
+        'U1:one-tap',                     # for_each_tap(lane, 64), taps == 1: lane 0 alone gathers
+        'U1:idle-lanes',                  # ... taps < 64: lanes without a tap take part in the butterfly
+        'lane-loop-strides',              # ... taps > 64
+        'U2:event-loop-strides',          # the event loop: more events than waves
         'U3:widest-circular',             # api.hip events_shift_shape: A - 1 == S on an axis, every shift has two images
         'U3:widest-reflect',              # ... A - 1 == S - 1
     ),
     'grad_W': (
-        'one-image', 'two-images', 'four-images', 'image-clipped',   # :215, :247
-        'L==1', 'L-2..63', 'L>=64',       # :224 sub-lanes per tap
-        'idle-threads',                   # :230 threads with sub >= L or t >= taps
-        'G1:taps-128', 'G1:taps-256',     # :224 L == 2 / L == 1 and no idle thread
-        'tap-loop-strides',               # :227 taps > kEventThreads
-        'G1:three-tap-passes',            # :227 taps > 2 * kEventThreads
-        'G1:L-exceeds-segment',           # :235 L > TNMF_EVENTS_SEGMENT: sub-lanes that own no event
-        'full-segment', 'partial-segment',   # :199
-        'plane-of-several-segments',      # :198
-        'slab-beyond-the-last-segment',   # :204
-        'G2:empty-plane-in-front',        # :196, :202 acc crosses a plane without segments before the first populated one
+        'one-image', 'two-images', 'four-images', 'image-clipped',   # the staging (axis_images), the iy / ix loops
+        'L==1', 'L-2..63', 'L>=64',       # L: sub-lanes per tap
+        'idle-threads',                   # `active`: threads with sub >= L or t >= taps
+        'G1:taps-128', 'G1:taps-256',     # L == 2 / L == 1 and no idle thread
+        'tap-loop-strides',               # the t0 loop: taps > kEventThreads
+        'G1:three-tap-passes',            # the t0 loop: taps > 2 * kEventThreads
+        'G1:L-exceeds-segment',           # the `i = sub` loop, L > TNMF_EVENTS_SEGMENT: sub-lanes that own no event
+        'full-segment', 'partial-segment',   # `count` of the segment
+        'plane-of-several-segments',      # `first` of the segment
+        'slab-beyond-the-last-segment',   # `plane < 0`
+        'G2:empty-plane-in-front',        # the plane walk: acc crosses a plane without segments before the first populated one
         'G2:empty-plane-between',         # ... between two populated ones
-        'G3:whole-segments-then-a-plane',   # :199 count % SEGMENT == 0 with a populated plane behind
+        'G3:whole-segments-then-a-plane',   # `count`: count % SEGMENT == 0 with a populated plane behind
     ),
     'grad_W_sum': (
-        'plane-without-slabs', 'one-slab', 'several-slabs',   # :287
-        'G2:offset-crosses-an-empty-plane',   # :280-283 s0 of a populated plane behind an empty one
+        'plane-without-slabs', 'one-slab', 'several-slabs',   # the s0 .. s1 loop
+        'G2:offset-crosses-an-empty-plane',   # the pp loop: s0 of a populated plane behind an empty one
         'G3:offset-crosses-whole-segments',   # ... behind a plane of whole segments
-        'several-chunks',                 # :275 taps > kEventThreads
-        'threads-beyond-the-taps',        # :277
+        'several-chunks',                 # `chunks`: taps > kEventThreads
+        'threads-beyond-the-taps',        # `t >= taps`
     ),
 }
 
@@ -85,7 +85,7 @@ def cdiv(a, b):
 
 
 def events_tile(ndim):
-    """events.h:20-23 -> (ty, tx)."""
+    """events.h events_tile -> (ty, tx)."""
     return (CELL_2D, CELL_2D) if ndim == 2 else (1, CELL_1D)
 
 
@@ -108,12 +108,12 @@ def shift_shape(geometry):
 
 
 def grid_for(blocks, num_cu=NUM_CU):
-    """events.hip:296-298."""
+    """events.hip grid_for."""
     return max(1, min(blocks, num_cu * 64))
 
 
 def axis_images(mode, u, a, S):
-    """events.hip:103-118 on an array of shifts -> (q0, q1, two): the padded positions, and where the second exists."""
+    """event_walk.h axis_images on an array of shifts -> (q0, q1, two): the padded positions, and where the second exists."""
     u = np.asarray(u, dtype=np.int64)
     none = np.zeros(u.shape, dtype=bool)
     if mode == 'valid':
@@ -171,7 +171,7 @@ def cell_counts(geometry, sample, shift):
 
 
 def render_branches(geometry, sample, plane, shift, num_cu=NUM_CU):
-    """The branches of k_events_render (events.hip:42-100) its launch (:302-319) on this list executes."""
+    """The branches of k_events_render (events.hip) and its launch (events_render) on this list executes."""
     N, C, _, _, A, _ = geometry
     Dy, Dx, Ay, Ax = dims(geometry)
     ty, tx = events_tile(len(A))
@@ -179,17 +179,17 @@ def render_branches(geometry, sample, plane, shift, num_cu=NUM_CU):
     out, _ = _image_branches(geometry, shift)
     counts = cell_counts(geometry, sample, shift)
     start = np.concatenate([np.zeros((N, ncy, 1), dtype=np.int64), np.cumsum(counts, axis=2)], axis=2)
-    nty, ntx = cdiv(Dy, ty), cdiv(Dx, tx)                                   # :307
+    nty, ntx = cdiv(Dy, ty), cdiv(Dx, tx)                                   # events_render
     tiles = N * nty * ntx
-    if tiles > grid_for(tiles, num_cu):                                     # :52, :308
+    if tiles > grid_for(tiles, num_cu):                                     # the tile loop, grid_for
         out.add('R4:tile-loop-strides')
-    if Dy % ty or Dx % tx:                                                  # :56
+    if Dy % ty or Dx % tx:                                                  # `inside`
         out.add('threads-outside')
     elif len(A) == 2 and nty > 1 and ntx > 1:
         out.add('R5:whole-tiles')
     if Dx < tx:
         out.add('R5:narrower-than-a-tile')
-    if C < CHAN:                                                            # :60, :88
+    if C < CHAN:                                                            # the c0 loop and its guard
         out.add('channels-below-a-group')
     if C > CHAN:
         out.add('R1:second-channel-pass')
@@ -197,7 +197,7 @@ def render_branches(geometry, sample, plane, shift, num_cu=NUM_CU):
             out.add('R1:partial-last-channel-group')
     for tile_y in range(nty):
         for tile_x in range(ntx):
-            cy_free, cx_free = (tile_y * ty + ty + Ay - 2) // ty, (tile_x * tx + tx + Ax - 2) // tx   # :58-59
+            cy_free, cx_free = (tile_y * ty + ty + Ay - 2) // ty, (tile_x * tx + tx + Ax - 2) // tx   # cy1, cx1
             cy1, cx1 = min(cy_free, ncy - 1), min(cx_free, ncx - 1)
             if cy_free > ncy - 1:
                 out.add('cy1-clamped')
@@ -207,7 +207,7 @@ def render_branches(geometry, sample, plane, shift, num_cu=NUM_CU):
                 out.add('R2:three-cell-rows')
             if cx1 - tile_x >= 2:
                 out.add('R2:three-cell-columns')
-            for cy in range(tile_y, cy1 + 1):                               # :64-67: one run per cell row, per sample
+            for cy in range(tile_y, cy1 + 1):                               # the cy loop: one run per cell row, per sample
                 run = start[:, cy, cx1 + 1] - start[:, cy, tile_x]
                 if np.any(run == 0):
                     out.add('empty-run')
@@ -221,20 +221,20 @@ def render_branches(geometry, sample, plane, shift, num_cu=NUM_CU):
 
 
 def update_branches(geometry, sample, plane, shift, num_cu=NUM_CU):
-    """The branches of k_events_update (events.hip:120-160) its launch (:321-336) on this list executes."""
+    """The branches of k_events_update (events.hip) and its launch (events_update) on this list executes."""
     _, C, _, _, A, mode = geometry
     _, _, Ay, Ax = dims(geometry)
     Sy, Sx = shift_shape(geometry)
     out, _ = _image_branches(geometry, shift)
-    taps = C * Ay * Ax                                                      # :126
+    taps = C * Ay * Ax                                                      # k_events_update
     if taps == 1:
         out.add('U1:one-tap')
     if taps < 64:
         out.add('U1:idle-lanes')
     if taps > 64:
         out.add('lane-loop-strides')
-    blocks = cdiv(len(sample), WAVES)                                       # :325
-    if blocks > grid_for(blocks, num_cu):                                   # :127
+    blocks = cdiv(len(sample), WAVES)                                       # events_update
+    if blocks > grid_for(blocks, num_cu):                                   # the event loop
         out.add('U2:event-loop-strides')
     for a, s in ((Ay, Sy), (Ax, Sx)):                                       # api.hip events_shift_shape: the limits
         if mode == 'circular' and a > 1 and a - 1 == s:
@@ -245,43 +245,43 @@ def update_branches(geometry, sample, plane, shift, num_cu=NUM_CU):
 
 
 def sub_lanes(taps):
-    """events.hip:224."""
+    """k_events_grad_W, L."""
     return max(1, THREADS // taps)
 
 
 def plane_counts(geometry, plane):
-    """Events per plane: plane_start of HIP_Backend.event_plane_list as run lengths (events.hip plane_run, :165-173)."""
+    """Events per plane: plane_start of HIP_Backend.event_plane_list as run lengths (events.hip plane_run)."""
     return np.bincount(np.asarray(plane, dtype=np.int64), minlength=geometry[2])
 
 
 def events_grad_W_slabs(n_events, P):
-    """events.hip:338."""
+    """events.hip events_grad_W_slabs."""
     return n_events // SEGMENT + P
 
 
 def grad_W_branches(geometry, sample, plane, shift, num_cu=NUM_CU):
-    """The branches of k_events_grad_W (events.hip:175-267), one workgroup per slab (:347)."""
+    """The branches of k_events_grad_W (events.hip), one workgroup per slab (events_grad_W)."""
     _, C, P, _, _, _ = geometry
     _, _, Ay, Ax = dims(geometry)
     out, _ = _image_branches(geometry, shift)
     taps = C * Ay * Ax
     L = sub_lanes(taps)
     out.add('L==1' if L == 1 else 'L-2..63' if L < 64 else 'L>=64')
-    if (L > 1 and L * taps < THREADS) or (L == 1 and taps % THREADS):       # :230
+    if (L > 1 and L * taps < THREADS) or (L == 1 and taps % THREADS):       # `active`
         out.add('idle-threads')
     if taps == 128:
         out.add('G1:taps-128')
     if taps == 256:
         out.add('G1:taps-256')
-    if taps > THREADS:                                                      # :227
+    if taps > THREADS:                                                      # the t0 loop
         out.add('tap-loop-strides')
     if taps > 2 * THREADS:
         out.add('G1:three-tap-passes')
     counts = plane_counts(geometry, plane)
-    if len(sample) and L > SEGMENT:                                         # :235
+    if len(sample) and L > SEGMENT:                                         # the `i = sub` loop
         out.add('G1:L-exceeds-segment')
-    segments = [cdiv(int(c), SEGMENT) for c in counts]                      # :195
-    if sum(segments) < events_grad_W_slabs(len(sample), P):                 # :204
+    segments = [cdiv(int(c), SEGMENT) for c in counts]                      # ns of the plane walk
+    if sum(segments) < events_grad_W_slabs(len(sample), P):                 # `plane < 0`
         out.add('slab-beyond-the-last-segment')
     if any(c >= SEGMENT for c in counts):
         out.add('full-segment')
@@ -300,7 +300,7 @@ def grad_W_branches(geometry, sample, plane, shift, num_cu=NUM_CU):
 
 
 def grad_W_sum_branches(geometry, sample, plane, shift, num_cu=NUM_CU):
-    """The branches of k_events_grad_W_sum (events.hip:269-294), one thread per (plane, tap) (:358)."""
+    """The branches of k_events_grad_W_sum (events.hip), one thread per (plane, tap) (events_grad_W)."""
     _, C, P, _, _, _ = geometry
     _, _, Ay, Ax = dims(geometry)
     taps = C * Ay * Ax
@@ -313,9 +313,9 @@ def grad_W_sum_branches(geometry, sample, plane, shift, num_cu=NUM_CU):
             out.add('G2:offset-crosses-an-empty-plane')
         if ns and any(counts[q] > 0 and counts[q] % SEGMENT == 0 for q in range(p)):
             out.add('G3:offset-crosses-whole-segments')
-    if taps > THREADS:                                                      # :275
+    if taps > THREADS:                                                      # `chunks`
         out.add('several-chunks')
-    if taps % THREADS:                                                      # :277
+    if taps % THREADS:                                                      # `t >= taps`
         out.add('threads-beyond-the-taps')
     return out
 

@@ -52,10 +52,7 @@ def test_mirrored_rules_are_those_of_the_sources():
                  'const int i0 = max(cell_start[row + tile_x], 0), i1 = min(cell_start[row + cx1 + 1], n_images);',
                  'for (int base = i0; base < i1; base += kEventThreads) {',
                  'if (c0 + cc < g.C) acc[cc] += hv * w[(size_t)cc * AA];',
-                 'if (mode == TNMF_MODE_CIRCULAR && u >= S - (a - 1)) {',
-                 'if (mode == TNMF_MODE_REFLECT && u >= 1 && u <= a - 1) {',
                  'for (long long e = (long long)blockIdx.x * kWaves + wave; e < n_events; e += (long long)gridDim.x * kWaves) {',
-                 'for (int t = lane; t < taps; t += 64) {',
                  'const int ns = (c + TNMF_EVENTS_SEGMENT - 1) / TNMF_EVENTS_SEGMENT;',
                  'count = min(TNMF_EVENTS_SEGMENT, a + c - first);',
                  'const int L = max(1, kEventThreads / taps);   // sub-lanes per tap',
@@ -70,6 +67,15 @@ def test_mirrored_rules_are_those_of_the_sources():
                  'dim3((unsigned)n_slabs), dim3(kEventThreads)',
                  'const dim3 grid((unsigned)((long long)cdiv(taps, kEventThreads) * g.P));'):
         assert line in src, line
+    # the occurrence walk the wave kernels share: the image table and the lane loop, and one call per wave kernel with a
+    # lane's first tap and stride
+    walk = _read(CSRC, 'event_walk.h')
+    for line in ('if (mode == TNMF_MODE_CIRCULAR && u >= S - (a - 1)) {',
+                 'if (mode == TNMF_MODE_REFLECT && u >= 1 && u <= a - 1) {',
+                 'for (int t = first; t < taps; t += step) {'):
+        assert line in walk, line
+    assert src.count('for_each_tap(g, o, lane, 64, [&](int t, int c, int y, int x) {') == 2   # k_events_update, k_events_gain
+    assert src.count('for_each_tap(') == 2 and 'axis_images(mode, u' not in src
     api = _read(CSRC, 'api.hip')
     for line in ('g->ncy = cdiv(g->Dy + g->Ay - 1, g->ty), g->ncx = cdiv(g->Dx + g->Ax - 1, g->tx);',
                  'S[i] = mode == TNMF_MODE_VALID ? D[i] + A[i] - 1 : mode == TNMF_MODE_FULL ? D[i] - A[i] + 1 : D[i];',

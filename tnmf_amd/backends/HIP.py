@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from .. import _lib, sharding, transforms as _transforms
+from ..events_host import pursuit_loop
 from ._Backend import Backend, sliceNone
 
 _DTYPES = {np.dtype('float32'): (torch.float32, 0), np.dtype('float64'): (torch.float64, 1)}
@@ -977,7 +978,7 @@ class HIP_Backend(Backend):
 
     # -- pursuit: the list found by forward selection ---------------------------------------------------------------------
     # A round (include/tnmf_hip.h, "pursuit") is the H gradient's numerator of the residual, the gain map, its peaks and
-    # the exact score of the kept ones; the rows are chosen on the host (TransformInvariantNMF.pursuit_loop) from the
+    # the exact score of the kept ones; the rows are chosen on the host (events_host.pursuit_loop) from the
     # peaks alone -- the map, activation-sized, never leaves the device.
     def event_norms(self, W: torch.Tensor) -> torch.Tensor:
         """b[P, *S] float64 on the device: ||phi||^2 of every plane of ``W`` at every shift of this mode ->
@@ -1067,7 +1068,6 @@ class HIP_Backend(Backend):
         hooks) -- per round one render of the list, the residual, pursuit_round, the host's choice among the candidates,
         pick_events for the kept ones and refit_events for the list; only candidates and kept rows cross to the host.  The
         resident samples and the model's activations are left as they are.  The plain Frobenius objective."""
-        from ..TransformInvariantNMF import pursuit_loop
         if self._G_dev is not None:
             raise NotImplementedError('pursue_events is unweighted')
         P, k = int(W.shape[0]), len(self.atom_shape)

@@ -1381,6 +1381,14 @@ static int events_shift_shape(const EventGeo &g, int mode, int S[2]) {
     return TNMF_OK;
 }
 
+// the preamble of the events entry points that take a mode: the arguments that must be there, the geometry, the shift shape
+// (a mode out of range is events_shift_shape's TNMF_E_GEOM)
+static int events_enter(const tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, EventGeo *g, int S[2]) {
+    if (!ctx || !geom) return TNMF_E_NULL;
+    const int rc = events_geo(geom, g);
+    return rc != TNMF_OK ? rc : events_shift_shape(*g, mode, S);
+}
+
 int tnmf_hip_events_render(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *W_eff, const int *images,
                            long long n_images, const int *cell_start, const void *strength, long long n_events, void *R,
                            void *stream) {
@@ -1399,13 +1407,11 @@ int tnmf_hip_events_render(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const v
 int tnmf_hip_events_update(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,
                            void *strength_inout, long long n_events, const void *V, const void *R, double eps,
                            double sparsity, void *stream) {
-    if (!ctx || !geom) return TNMF_E_NULL;
     EventGeo g;
-    const int rc = events_geo(geom, &g);
-    if (rc != TNMF_OK) return rc;
-    if (mode < TNMF_MODE_VALID || mode > TNMF_MODE_REFLECT || n_events < 0) return TNMF_E_GEOM;
     int S[2];
-    if (events_shift_shape(g, mode, S) != TNMF_OK) return TNMF_E_GEOM;
+    const int rc = events_enter(ctx, geom, mode, &g, S);
+    if (rc != TNMF_OK) return rc;
+    if (n_events < 0) return TNMF_E_GEOM;
     if (!(eps >= 0) || !(sparsity >= 0)) return TNMF_E_UNSUPPORTED;
     if (n_events > 0 && g.N > 0 && (!W_eff || !events || !strength_inout || !V || !R)) return TNMF_E_NULL;
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
@@ -1416,13 +1422,11 @@ int tnmf_hip_events_update(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mod
 int tnmf_hip_events_gain(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,
                          const void *strength, long long n_events, const void *V, const void *R, double *gain, double *mag,
                          void *stream) {
-    if (!ctx || !geom) return TNMF_E_NULL;
     EventGeo g;
-    const int rc = events_geo(geom, &g);
-    if (rc != TNMF_OK) return rc;
-    if (mode < TNMF_MODE_VALID || mode > TNMF_MODE_REFLECT || n_events < 0) return TNMF_E_GEOM;
     int S[2];
-    if (events_shift_shape(g, mode, S) != TNMF_OK) return TNMF_E_GEOM;
+    const int rc = events_enter(ctx, geom, mode, &g, S);
+    if (rc != TNMF_OK) return rc;
+    if (n_events < 0) return TNMF_E_GEOM;
     if (n_events > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
     if (n_events > 0 && g.N > 0 && (!W_eff || !events || !strength || !V || !R || !gain)) return TNMF_E_NULL;
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
@@ -1433,13 +1437,11 @@ int tnmf_hip_events_gain(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode,
 int tnmf_hip_events_grad_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const int *events, const int *by_plane,
                            const int *plane_start, const void *strength, long long n_events, const void *V, const void *R,
                            void *workspace, void *negpos_eff, void *stream) {
-    if (!ctx || !geom) return TNMF_E_NULL;
     EventGeo g;
-    const int rc = events_geo(geom, &g);
+    int S[2];
+    const int rc = events_enter(ctx, geom, mode, &g, S);
     if (rc != TNMF_OK) return rc;
     if (n_events < 0) return TNMF_E_GEOM;
-    int S[2];
-    if (events_shift_shape(g, mode, S) != TNMF_OK) return TNMF_E_GEOM;
     if (n_events > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
     if (!negpos_eff) return TNMF_E_NULL;
     if (n_events > 0 && g.N > 0 && (!events || !by_plane || !plane_start || !strength || !V || !R || !workspace))
@@ -1451,12 +1453,10 @@ int tnmf_hip_events_grad_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mod
 
 int tnmf_hip_events_norms(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, double *b,
                           void *stream) {
-    if (!ctx || !geom) return TNMF_E_NULL;
     EventGeo g;
-    const int rc = events_geo(geom, &g);
-    if (rc != TNMF_OK) return rc;
     int S[2];
-    if (events_shift_shape(g, mode, S) != TNMF_OK) return TNMF_E_GEOM;
+    const int rc = events_enter(ctx, geom, mode, &g, S);
+    if (rc != TNMF_OK) return rc;
     if ((long long)S[0] * S[1] > 0x7fffffffLL || g.P > 65535) return TNMF_E_UNSUPPORTED;
     if (!W_eff || !b) return TNMF_E_NULL;
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
@@ -1488,13 +1488,11 @@ int tnmf_hip_pursuit_score(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const v
 int tnmf_hip_pursuit_pick(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const long long *idx,
                           long long n_picked, const void *V, const void *R, int *events_out, void *strength_out,
                           double *gain_out, double *mag_out, void *stream) {
-    if (!ctx || !geom) return TNMF_E_NULL;
     EventGeo g;
-    const int rc = events_geo(geom, &g);
-    if (rc != TNMF_OK) return rc;
-    if (mode < TNMF_MODE_VALID || mode > TNMF_MODE_REFLECT || n_picked < 0) return TNMF_E_GEOM;
     int S[2];
-    if (events_shift_shape(g, mode, S) != TNMF_OK) return TNMF_E_GEOM;
+    const int rc = events_enter(ctx, geom, mode, &g, S);
+    if (rc != TNMF_OK) return rc;
+    if (n_picked < 0) return TNMF_E_GEOM;
     if (n_picked > 0x7fffffffLL || (long long)S[0] * S[1] > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
     if (n_picked > 0 && (!idx || !events_out || !strength_out || !gain_out || (g.N > 0 && (!W_eff || !V || !R))))
         return TNMF_E_NULL;

@@ -1,0 +1,81 @@
+// The occurrence of an event on the device, shared by the kernels of events.hip and pursuit.hip: its images per axis, the
+// walk over the taps of every image clipped to the sample, the value phi of the occurrence at a pixel, and the wave's sum.
+// Device code only; everything is inlined into the kernel that calls it, the lambda of for_each_tap included.
+#pragma once
+
+#include "events.h"
+
+// the images of the shift u on one axis (atom extent a, shift extent S): their padded positions, at most two
+__device__ __forceinline__ int axis_images(int mode, int u, int a, int S, int q[2]) {
+    if (mode == TNMF_MODE_VALID) {
+        q[0] = u;
+        return 1;
+    }
+    q[0] = u + a - 1;
+    if (mode == TNMF_MODE_CIRCULAR && u >= S - (a - 1)) {
+        q[1] = u - (S - (a - 1));
+        return 2;
+    }
+    if (mode == TNMF_MODE_REFLECT && u >= 1 && u <= a - 1) {
+        q[1] = (a - 1) - u;
+        return 2;
+    }
+    return 1;
+}
+
+// the images of the shift (uy, ux) of the mode with shift shape (Sy, Sx): ny * nx of them, at (qy[iy], qx[ix])
+struct Occurrence {
+    int ny, nx, qy[2], qx[2];
+    __device__ __forceinline__ Occurrence(const EventGeo &g, int mode, int Sy, int Sx, int uy, int ux)
+        : qy{0, 0}, qx{0, 0} {   // (a second position that does not exist reads as 0, never as an unset value)
+        ny = axis_images(mode, uy, g.Ay, Sy, qy);
+        nx = axis_images(mode, ux, g.Ax, Sx, qx);
+    }
+    __device__ __forceinline__ bool single() const { return ny * nx == 1; }   // phi at a pixel is the tap itself
+};
+
+// f(t, c, y, x) for the taps t = first, first + step, ... of every image, in (iy, ix) order, whose pixel (y, x) of channel c
+// lies inside the sample.  A wave passes (lane, 64), a single thread (0, 1).
+template <typename F>
+__device__ __forceinline__ void for_each_tap(const EventGeo &g, const Occurrence &o, int first, int step, F &&f) {
+    const int AA = g.Ay * g.Ax, taps = g.C * AA;
+    const unsigned uAA = AA, uAx = g.Ax;   // (t >= 0 is divided by positive extents: unsigned, no sign handling per tap)
+    // (copies the loops may index: indexed by a loop variable inside `o`, the whole value leaves the registers for LDS;
+    // tools/probes/kernel_resources.py --no-lds checks that it has not)
+    const int qy[2] = {o.qy[0], o.qy[1]}, qx[2] = {o.qx[0], o.qx[1]};
+    for (int iy = 0; iy < o.ny; ++iy) {
+        for (int ix = 0; ix < o.nx; ++ix) {
+            const int oy = qy[iy] - (g.Ay - 1), ox = qx[ix] - (g.Ax - 1);
+            for (int t = first; t < taps; t += step) {
+                const int c = t / uAA, r = t - c * AA;
+                const int jy = r / uAx, jx = r - jy * g.Ax;
+                const int y = oy + jy, x = ox + jx;
+                if ((unsigned)y < (unsigned)g.Dy && (unsigned)x < (unsigned)g.Dx) f(t, c, y, x);
+            }
+        }
+    }
+}
+
+// phi at pixel (y, x) of the channel whose taps start at w[cAA] (cAA = c * Ay * Ax, w the plane's taps):
+// every image that covers this pixel, in image order
+template <typename T>
+__device__ __forceinline__ double phi_at(const EventGeo &g, const Occurrence &o, const T *w, int cAA, int y, int x) {
+    const int qy[2] = {o.qy[0], o.qy[1]}, qx[2] = {o.qx[0], o.qx[1]};   // (as in for_each_tap)
+    double phi = 0.;
+    for (int ky = 0; ky < o.ny; ++ky) {
+        const int ly = y - (qy[ky] - (g.Ay - 1));
+        if ((unsigned)ly >= (unsigned)g.Ay) continue;
+        for (int kx = 0; kx < o.nx; ++kx) {
+            const int lx = x - (qx[kx] - (g.Ax - 1));
+            if ((unsigned)lx < (unsigned)g.Ax) phi += (double)w[cAA + ly * g.Ax + lx];
+        }
+    }
+    return phi;
+}
+
+// the sum over the 64 lanes, in every lane: a butterfly, the same order of additions in every lane and run
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}

@@ -14,22 +14,22 @@
 // memset pass and no read of R.  Measured against the walk that loads each image through a wave-uniform address straight
 // from the list: 0.72 ms against 0.97 ms at 939 k events, 0.175 ms against 0.197 ms at 34 k.
 //
-// k_events_update: one wave per event.  The images are derived from the event itself (the table of the header); the lanes
-// stride over the C * Ay * Ax atom entries, gather V and R under each image, clipped per pixel, into double partial sums,
-// reduce them with a butterfly of fixed order and lane 0 applies the multiplicative update to the strength in place.  It
-// writes the K strengths and nothing else.
+// k_events_update: one wave per event.  The images are derived from the event itself (the table of the header, Occurrence
+// of event_walk.h); the lanes stride over the C * Ay * Ax atom entries (for_each_tap), gather V and R under each image,
+// clipped per pixel, into double partial sums, reduce them with a butterfly of fixed order (wave_sum) and lane 0 applies
+// the multiplicative update to the strength in place.  It writes the K strengths and nothing else.
 //
-// k_events_gain: the same gather, one wave per event, for what the event explains: gain_e = E(list without e) - E(list)
+// k_events_gain: the same walk, one wave per event, for what the event explains: gain_e = E(list without e) - E(list)
 // = h a + h^2 b / 2 with a = <phi_e, V - R>, b = |phi_e|^2, phi_e the sum of the event's images clipped to the sample.  The
-// images of one event can overlap, so phi_e at a pixel is summed over the images (skipped for the single-image event,
-// where it is the tap itself).  All in double; the sum of the terms' magnitudes goes out beside the gain as the scale of
-// its rounding error.  It writes the K gains (and magnitudes), zeros for a row outside the contract, and nothing else.
+// images of one event can overlap, so phi_e at a pixel is summed over the images (phi_at; skipped for the single-image
+// event, where it is the tap itself).  All in double; the sum of the terms' magnitudes goes out beside the gain as the scale
+// of its rounding error.  It writes the K gains (and magnitudes), zeros for a row outside the contract, and nothing else.
 //
 // k_events_grad_W / k_events_grad_W_sum: the W gradient of the list, many events onto few destinations (P * C * Ay * Ax
 // entries), without float atomics: a store pass and an ordered per-destination sum.  The caller sorts the events once per
 // support by plane (a permutation and plane_start); each plane's run is cut into segments of TNMF_EVENTS_SEGMENT events, a
 // constant of the list contract, so the order of the additions does not depend on the device.  One workgroup per segment
-// stages the rows and strengths of its events in LDS, images derived (axis_images); a thread owns a tap t = c * Ay * Ax + j
+// stages the rows and strengths of its events in LDS, images derived (event_walk.h); a thread owns a tap t = c * Ay * Ax + j
 // and walks the events in list order, loading V and R under each image through one address (consecutive jx are contiguous
 // in x) into double partial sums.  With at most 128 taps floor(256 / taps) sub-lanes share a tap, sub-lane s taking the
 // events s, s + L, ... of the segment, and are added through LDS in sub-lane order; with more than 256 taps the threads
@@ -37,7 +37,7 @@
 // in segment order and rounds once to the element type, zeros for a plane without events: negpos is never read.
 #include <algorithm>
 
-#include "events.h"
+#include "event_walk.h"
 
 namespace {
 
@@ -105,62 +105,29 @@ __global__ __launch_bounds__(kEventThreads) void k_events_render(EventGeo g, int
     }
 }
 
-// the images of the shift u on one axis (atom extent a, shift extent S): their padded positions, at most two
-__device__ __forceinline__ int axis_images(int mode, int u, int a, int S, int q[2]) {
-    if (mode == TNMF_MODE_VALID) {
-        q[0] = u;
-        return 1;
-    }
-    q[0] = u + a - 1;
-    if (mode == TNMF_MODE_CIRCULAR && u >= S - (a - 1)) {
-        q[1] = u - (S - (a - 1));
-        return 2;
-    }
-    if (mode == TNMF_MODE_REFLECT && u >= 1 && u <= a - 1) {
-        q[1] = (a - 1) - u;
-        return 2;
-    }
-    return 1;
-}
-
 template <typename T>
 __global__ __launch_bounds__(kEventThreads) void k_events_update(EventGeo g, int mode, int Sy, int Sx,
                                                                   const T *__restrict__ W, const int4 *__restrict__ ev,
                                                                   T *h, long long n_events, const T *__restrict__ V,
                                                                   const T *__restrict__ R, double reg) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int AA = g.Ay * g.Ax, taps = g.C * AA;
+    const int taps = g.C * g.Ay * g.Ax;
     for (long long e = (long long)blockIdx.x * kWaves + wave; e < n_events; e += (long long)gridDim.x * kWaves) {
         const int4 v = ev[e];   // sample, plane, uy, ux
         if ((unsigned)v.x >= (unsigned)g.N || (unsigned)v.y >= (unsigned)g.P || (unsigned)v.z >= (unsigned)Sy ||
             (unsigned)v.w >= (unsigned)Sx)
             continue;   // (wave-uniform: outside the contract, neither read nor written)
-        int qy[2], qx[2];
-        const int ny = axis_images(mode, v.z, g.Ay, Sy, qy), nx = axis_images(mode, v.w, g.Ax, Sx, qx);
+        const Occurrence o(g, mode, Sy, Sx, v.z, v.w);
         const T *w = W + (size_t)v.y * taps;
         const size_t sample = (size_t)v.x * g.C * g.Dy * g.Dx;
         double neg = 0., pos = 0.;
-        for (int iy = 0; iy < ny; ++iy) {
-            for (int ix = 0; ix < nx; ++ix) {
-                const int oy = qy[iy] - (g.Ay - 1), ox = qx[ix] - (g.Ax - 1);
-                for (int t = lane; t < taps; t += 64) {
-                    const int c = t / AA, r = t - c * AA;
-                    const int jy = r / g.Ax, jx = r - jy * g.Ax;
-                    const int y = oy + jy, x = ox + jx;
-                    if ((unsigned)y < (unsigned)g.Dy && (unsigned)x < (unsigned)g.Dx) {
-                        const size_t at = sample + ((size_t)c * g.Dy + y) * g.Dx + x;
-                        const double wv = (double)w[t];
-                        neg += wv * (double)V[at];
-                        pos += wv * (double)R[at];
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {   // a butterfly: the same order of additions in every lane and run
-            neg += __shfl_xor(neg, off, 64);
-            pos += __shfl_xor(pos, off, 64);
-        }
+        for_each_tap(g, o, lane, 64, [&](int t, int c, int y, int x) {
+            const size_t at = sample + ((size_t)c * g.Dy + y) * g.Dx + x;
+            const double wv = (double)w[t];
+            neg += wv * (double)V[at];
+            pos += wv * (double)R[at];
+        });
+        neg = wave_sum(neg), pos = wave_sum(pos);
         if (lane == 0) h[e] = (T)((double)h[e] * neg / (pos + reg));
     }
 }
@@ -183,51 +150,24 @@ __global__ __launch_bounds__(kEventThreads) void k_events_gain(EventGeo g, int m
             }
             continue;
         }
-        int qy[2], qx[2];
-        const int ny = axis_images(mode, v.z, g.Ay, Sy, qy), nx = axis_images(mode, v.w, g.Ax, Sx, qx);
-        const bool single = ny * nx == 1;   // (wave-uniform) phi at a pixel is the tap itself
+        const Occurrence o(g, mode, Sy, Sx, v.z, v.w);
+        const bool single = o.single();   // (wave-uniform)
         const T *w = W + (size_t)v.y * taps;
         const size_t sample = (size_t)v.x * g.C * g.Dy * g.Dx;
         const double hv = (double)h[e], hh = 0.5 * hv * hv;
         double a = 0., b = 0., m = 0.;
-        for (int iy = 0; iy < ny; ++iy) {
-            for (int ix = 0; ix < nx; ++ix) {
-                const int oy = qy[iy] - (g.Ay - 1), ox = qx[ix] - (g.Ax - 1);
-                for (int t = lane; t < taps; t += 64) {
-                    const int c = t / AA, r = t - c * AA;
-                    const int jy = r / g.Ax, jx = r - jy * g.Ax;
-                    const int y = oy + jy, x = ox + jx;
-                    if ((unsigned)y < (unsigned)g.Dy && (unsigned)x < (unsigned)g.Dx) {
-                        const size_t at = sample + ((size_t)c * g.Dy + y) * g.Dx + x;
-                        const double wv = (double)w[t];
-                        double phi = wv;
-                        if (!single) {   // every image that covers this pixel, in image order
-                            phi = 0.;
-                            for (int ky = 0; ky < ny; ++ky) {
-                                const int ly = y - (qy[ky] - (g.Ay - 1));
-                                if ((unsigned)ly >= (unsigned)g.Ay) continue;
-                                for (int kx = 0; kx < nx; ++kx) {
-                                    const int lx = x - (qx[kx] - (g.Ax - 1));
-                                    if ((unsigned)lx < (unsigned)g.Ax) phi += (double)w[c * AA + ly * g.Ax + lx];
-                                }
-                            }
-                        }
-                        const double wd = wv * ((double)V[at] - (double)R[at]), wp = wv * phi;
-                        a += wd;
-                        b += wp;
-                        m += hv * fabs(wd) + hh * fabs(wp);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {   // the butterfly of the update: a fixed order of additions
-            a += __shfl_xor(a, off, 64);
-            b += __shfl_xor(b, off, 64);
-            m += __shfl_xor(m, off, 64);
-        }
+        for_each_tap(g, o, lane, 64, [&](int t, int c, int y, int x) {
+            const size_t at = sample + ((size_t)c * g.Dy + y) * g.Dx + x;
+            const double wv = (double)w[t];
+            const double phi = single ? wv : phi_at(g, o, w, c * AA, y, x);
+            const double wd = wv * ((double)V[at] - (double)R[at]), wp = wv * phi;
+            a += wd;
+            b += wp;
+            m += fma(hh, fabs(wp), hv * fabs(wd));   // (hv |wd| + hh |wp|, the contraction spelled out as for the gain below)
+        });
+        a = wave_sum(a), b = wave_sum(b), m = wave_sum(m);
         if (lane == 0) {
-            gain[e] = hv * a + hh * b;
+            gain[e] = fma(hh, b, hv * a);   // (hv * a + hh * b with the contraction spelled out: the compiler may pick either)
             if (mag) mag[e] = m;
         }
     }

@@ -1,12 +1,14 @@
 // pursuit.hip -- forward selection of events (include/tnmf_hip.h, "pursuit"): the table of norms, the gain map of a round
 // and the exact score of the candidates a round keeps.  The correlation that feeds the map is the H gradient's; the render
-// and the refit of the list are those of events.hip.
+// and the refit of the list are those of events.hip, the occurrence of a shift and the walk over its taps those of
+// event_walk.h.
 //
 // k_events_norms: b[p, u] = |phi_{p,u}|^2 for every plane and shift, in double.  grid.y is the plane; every workgroup first
 // sums the squares of its plane's taps (256 partial sums in tap order, then a tree of fixed shape through LDS), which IS the
 // norm of every shift whose single image lies wholly inside the sample.  Any other shift -- clipped by the border, wrapped
-// or mirrored -- goes through the image walk of k_events_gain in one thread: the taps in (image, channel, row, column)
-// order, phi at a pixel summed over the images that cover it.  A plane has O(perimeter * atom) such shifts.
+// or mirrored -- goes through the walk of k_events_gain in one thread (for_each_tap from tap 0 in steps of 1): the taps in
+// (image, channel, row, column) order, phi at a pixel summed over the images that cover it (phi_at).  A plane has
+// O(perimeter * atom) such shifts.
 //
 // k_pursuit_score: g = a^2 / (2 b) where a > 0 and b > 0, else 0 -- a streaming pass over the map, rows `Hs` apart.  A
 // thread owns 16 bytes of a row (four floats, two doubles) and walks the map with a grid stride; it derives (row, column)
@@ -17,36 +19,16 @@
 // neither read nor written.  b is read through the cache: P planes of doubles against N * P planes of the map.  k_pursuit_taken then
 // zeroes the entries already in the list, on the same stream.
 //
-// k_pursuit_pick: one wave per picked flat index, the gather of k_events_gain against the residual V - R: a = <phi, V - R>,
-// b = |phi|^2 and the magnitude sum |w (V - R)|, in double with the same butterfly; lane 0 writes the event's row, the
-// strength max(a, 0) / b that minimises the energy along phi, rounded once, and the gain a^2 / (2 b) of adding it.
+// k_pursuit_pick: one wave per picked flat index, the walk of k_events_gain against the residual V - R: a = <phi, V - R>,
+// b = |phi|^2 and the magnitude sum |w (V - R)|, in double with the same butterfly (wave_sum); lane 0 writes the event's row,
+// the strength max(a, 0) / b that minimises the energy along phi, rounded once, and the gain a^2 / (2 b) of adding it.
 #include <algorithm>
 
-#include "events.h"
+#include "event_walk.h"
 
 namespace {
 
 constexpr int kWaves = kEventThreads / 64;
-
-// the images of the shift u on one axis (atom extent a, shift extent S): their padded positions, at most two -- the table
-// of events.hip, which keeps its own copy in its own namespace
-__device__ __forceinline__ int axis_images(int mode, int u, int a, int S, int q[2]) {
-    if (mode == TNMF_MODE_VALID) {
-        q[0] = u;
-        return 1;
-    }
-    q[0] = u + a - 1;
-    if (mode == TNMF_MODE_CIRCULAR && u >= S - (a - 1)) {
-        q[1] = u - (S - (a - 1));
-        return 2;
-    }
-    if (mode == TNMF_MODE_REFLECT && u >= 1 && u <= a - 1) {
-        q[1] = (a - 1) - u;
-        return 2;
-    }
-    return 1;
-}
-
 
 template <typename T>
 __global__ __launch_bounds__(kEventThreads) void k_events_norms(EventGeo g, int mode, int Sy, int Sx,
@@ -67,33 +49,15 @@ __global__ __launch_bounds__(kEventThreads) void k_events_norms(EventGeo g, int 
     const int entries = Sy * Sx;   // (checked by the caller: fits 31 bits)
     for (int e = blockIdx.x * kEventThreads + threadIdx.x; e < entries; e += gridDim.x * kEventThreads) {
         const int uy = e / Sx, ux = e - uy * Sx;
-        int qy[2], qx[2];
-        const int ny = axis_images(mode, uy, g.Ay, Sy, qy), nx = axis_images(mode, ux, g.Ax, Sx, qx);
-        const int oy0 = qy[0] - (g.Ay - 1), ox0 = qx[0] - (g.Ax - 1);
+        const Occurrence o(g, mode, Sy, Sx, uy, ux);
+        const int oy0 = o.qy[0] - (g.Ay - 1), ox0 = o.qx[0] - (g.Ax - 1);
         double out = whole;
-        if (ny * nx != 1 || oy0 < 0 || ox0 < 0 || oy0 + g.Ay > g.Dy || ox0 + g.Ax > g.Dx) {
+        if (!o.single() || oy0 < 0 || ox0 < 0 || oy0 + g.Ay > g.Dy || ox0 + g.Ax > g.Dx) {
             out = 0.;
-            for (int iy = 0; iy < ny; ++iy) {
-                for (int ix = 0; ix < nx; ++ix) {
-                    const int oy = qy[iy] - (g.Ay - 1), ox = qx[ix] - (g.Ax - 1);
-                    for (int t = 0; t < taps; ++t) {
-                        const int c = t / AA, r = t - c * AA;
-                        const int jy = r / g.Ax, jx = r - jy * g.Ax;
-                        const int y = oy + jy, x = ox + jx;
-                        if ((unsigned)y >= (unsigned)g.Dy || (unsigned)x >= (unsigned)g.Dx) continue;
-                        double phi = 0.;   // every image that covers this pixel, in image order
-                        for (int ky = 0; ky < ny; ++ky) {
-                            const int ly = y - (qy[ky] - (g.Ay - 1));
-                            if ((unsigned)ly >= (unsigned)g.Ay) continue;
-                            for (int kx = 0; kx < nx; ++kx) {
-                                const int lx = x - (qx[kx] - (g.Ax - 1));
-                                if ((unsigned)lx < (unsigned)g.Ax) phi += (double)w[c * AA + ly * g.Ax + lx];
-                            }
-                        }
-                        out += (double)w[t] * phi;
-                    }
-                }
-            }
+            for_each_tap(g, o, 0, 1, [&](int t, int c, int y, int x) {
+                const double phi = phi_at(g, o, w, c * AA, y, x);
+                out += (double)w[t] * phi;
+            });
         }
         b[(size_t)p * entries + e] = out;
     }
@@ -179,48 +143,21 @@ __global__ __launch_bounds__(kEventThreads) void k_pursuit_pick(EventGeo g, int 
         const long long np = f / plane;
         const int u = (int)(f - np * plane);
         const int4 v = make_int4((int)(np / g.P), (int)(np % g.P), u / Sx, u % Sx);   // sample, plane, uy, ux
-        int qy[2], qx[2];
-        const int ny = axis_images(mode, v.z, g.Ay, Sy, qy), nx = axis_images(mode, v.w, g.Ax, Sx, qx);
-        const bool single = ny * nx == 1;   // (wave-uniform) phi at a pixel is the tap itself
+        const Occurrence o(g, mode, Sy, Sx, v.z, v.w);
+        const bool single = o.single();   // (wave-uniform)
         const T *w = W + (size_t)v.y * taps;
         const size_t sample = (size_t)v.x * g.C * g.Dy * g.Dx;
         double a = 0., b = 0., m = 0.;
-        for (int iy = 0; iy < ny; ++iy) {
-            for (int ix = 0; ix < nx; ++ix) {
-                const int oy = qy[iy] - (g.Ay - 1), ox = qx[ix] - (g.Ax - 1);
-                for (int t = lane; t < taps; t += 64) {
-                    const int c = t / AA, r = t - c * AA;
-                    const int jy = r / g.Ax, jx = r - jy * g.Ax;
-                    const int y = oy + jy, x = ox + jx;
-                    if ((unsigned)y < (unsigned)g.Dy && (unsigned)x < (unsigned)g.Dx) {
-                        const size_t at = sample + ((size_t)c * g.Dy + y) * g.Dx + x;
-                        const double wv = (double)w[t];
-                        double phi = wv;
-                        if (!single) {   // every image that covers this pixel, in image order
-                            phi = 0.;
-                            for (int ky = 0; ky < ny; ++ky) {
-                                const int ly = y - (qy[ky] - (g.Ay - 1));
-                                if ((unsigned)ly >= (unsigned)g.Ay) continue;
-                                for (int kx = 0; kx < nx; ++kx) {
-                                    const int lx = x - (qx[kx] - (g.Ax - 1));
-                                    if ((unsigned)lx < (unsigned)g.Ax) phi += (double)w[c * AA + ly * g.Ax + lx];
-                                }
-                            }
-                        }
-                        const double wd = wv * ((double)V[at] - (double)R[at]);
-                        a += wd;
-                        b += wv * phi;
-                        m += fabs(wd);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {   // the butterfly of k_events_gain: a fixed order of additions
-            a += __shfl_xor(a, off, 64);
-            b += __shfl_xor(b, off, 64);
-            m += __shfl_xor(m, off, 64);
-        }
+        for_each_tap(g, o, lane, 64, [&](int t, int c, int y, int x) {
+            const size_t at = sample + ((size_t)c * g.Dy + y) * g.Dx + x;
+            const double wv = (double)w[t];
+            const double phi = single ? wv : phi_at(g, o, w, c * AA, y, x);
+            const double wd = wv * ((double)V[at] - (double)R[at]);
+            a += wd;
+            b += wv * phi;
+            m += fabs(wd);
+        });
+        a = wave_sum(a), b = wave_sum(b), m = wave_sum(m);
         if (lane == 0) {
             const bool live = a > 0. && b > 0.;
             ev[e] = v;

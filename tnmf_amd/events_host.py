@@ -1,0 +1,345 @@
+"""
+The events of the front end on the host: the image table of an event, the clip of an image to the sample, and the NumPy
+fallbacks for a backend without the events hooks (tnmf_amd/backends/_Backend.py) -- peaks, render and refit, gains, norms,
+forward selection, the fit of the dictionary on a fixed support.  ``pursuit_loop``, the rounds of the forward selection, is
+shared by every backend, the hip backend included; nothing else here is on the hip path.
+"""
+import itertools
+from typing import Callable, Optional, Tuple
+
+import numpy as np
+
+from . import transforms as _transforms
+from .backends._Backend import shift_shape as _shift_shape
+
+
+def _shapes(W: np.ndarray, sample_shape: Tuple[int, ...], mode: str):
+    """(A, D, S): the atom shape of ``W[P, C, *A]``, the sample shape and the shift shape of the reconstruction mode
+    (``_Backend.shift_shape``: a mode it does not know raises ValueError; the front end has checked the mode before)."""
+    A, D = tuple(W.shape[2:]), tuple(sample_shape)
+    return A, D, _shift_shape(mode, D, A)
+
+
+def _clip(at, atom_shape: Tuple[int, ...], sample_shape: Tuple[int, ...]):
+    """An image at the padded position ``at`` clipped to the sample: (the slices of the sample axes it covers, the slices of
+    the atom axes that lie there), or None for an image without a pixel in the sample."""
+    origin = [int(x) - (a - 1) for x, a in zip(at, atom_shape)]
+    lo = [max(o, 0) for o in origin]
+    hi = [min(o + a, d) for o, a, d in zip(origin, atom_shape, sample_shape)]
+    if not all(b > a for a, b in zip(lo, hi)):
+        return None
+    return tuple(slice(a, b) for a, b in zip(lo, hi)), tuple(slice(a - o, b - o) for a, b, o in zip(lo, hi, origin))
+
+
+def find_peaks_numpy(H: np.ndarray, threshold: float, radius: Tuple[int, ...], group: int = 1):
+    """(idx, val) of the detections of ``H[N, P, *S]`` on the host, for backends without ``find_peaks``: the semantics of
+    tnmf_hip_find_peaks (include/tnmf_hip.h, "detections"), one window per candidate.  Not on the hip path."""
+    H = np.ascontiguousarray(H)
+    shape, k = H.shape, H.ndim - 2
+    assert k >= 1 and len(radius) == k and shape[1] % group == 0
+    t = H.dtype.type(threshold)          # the largest value of H's type not above the threshold: `h > t` is then exact
+    if float(t) > threshold:
+        t = np.nextafter(t, H.dtype.type(-np.inf))
+    flat = H.reshape(-1)
+    candidates = np.flatnonzero(flat > t)
+    keep = np.zeros(len(candidates), dtype=bool)
+    for i, (f, at) in enumerate(zip(candidates, zip(*np.unravel_index(candidates, shape)))):
+        n, p, u = at[0], at[1], at[2:]
+        g0 = p // group * group
+        lo = [max(0, int(x) - r) for x, r in zip(u, radius)]
+        box = H[(n, slice(g0, g0 + group)) + tuple(slice(a, int(x) + r + 1) for a, x, r in zip(lo, u, radius))]
+        h = flat[f]
+        if np.any(box > h):
+            continue
+        ties = np.argwhere(box == h)     # (the candidate itself is one of them)
+        ties = np.ravel_multi_index((np.full(len(ties), n), g0 + ties[:, 0]) + tuple(a + ties[:, 1 + j] for j, a in
+                                                                                   enumerate(lo)), shape)
+        keep[i] = not np.any(ties < f)
+    idx = candidates[keep].astype(np.int64)
+    return idx, flat[idx]
+
+
+def event_images(shift: np.ndarray, atom_shape: Tuple[int, ...], shift_shape: Tuple[int, ...], mode: str):
+    """(event [I], q [I, k]): the images of the events with shifts ``shift[K, k]`` in the padded activation frame
+    ``[D + A - 1]`` of a reconstruction mode -- the table of include/tnmf_hip.h, "events": per axis one position, and a
+    second one for a 'circular' shift in the wrap zone or a 'reflect' shift in the mirror zone; over the axes their
+    Cartesian product."""
+    shift = np.asarray(shift, dtype=np.int64).reshape(-1, len(atom_shape))
+    event, q = np.arange(len(shift), dtype=np.int64), np.empty((len(shift), 0), dtype=np.int64)
+    for i, (a, s) in enumerate(zip(atom_shape, shift_shape)):
+        u = shift[event, i]
+        first = u if mode == 'valid' else u + (a - 1)
+        if mode == 'circular':
+            more, second = np.flatnonzero(u >= s - (a - 1)), u - (s - (a - 1))
+        elif mode == 'reflect':
+            more, second = np.flatnonzero((u >= 1) & (u <= a - 1)), (a - 1) - u
+        else:
+            more, second = np.zeros(0, dtype=np.int64), u
+        q = np.concatenate([np.column_stack([q, first]), np.column_stack([q[more], second[more]])])
+        event = np.concatenate([event, event[more]])
+    return event, q
+
+
+def events_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], n_samples: int, mode: str, sample, plane, shift, strength,
+                 V: Optional[np.ndarray] = None, n_iterations: int = 0, sparsity: float = 0., eps: float = 1e-9):
+    """Events on the host, for backends without ``render_events`` / ``refit_events``: the semantics of
+    tnmf_hip_events_render / tnmf_hip_events_update (include/tnmf_hip.h, "events"), one loop over the images.  Without ``V``:
+    R ``[n_samples, C, *D]``, the render of the events (sample, plane of ``W[P, C, *A]``, shift, strength).  With ``V``
+    (the samples, ``[n_samples, C, *D]``): the strengths after ``n_iterations`` multiplicative updates on the fixed
+    support.  Not on the hip path."""
+    A, D, shift_shape = _shapes(W, sample_shape, mode)
+    h = np.array(strength, dtype=W.dtype).reshape(-1)
+    event, q = event_images(shift, A, shift_shape, mode)
+    placed = []   # per image: (event, where in the sample, the atom clipped to it)
+    for e, at in zip(event, q):
+        clipped = _clip(at, A, D)
+        if clipped:
+            placed.append((int(e), (int(sample[e]), slice(None)) + clipped[0], W[(int(plane[e]), slice(None)) + clipped[1]]))
+
+    def render():
+        R = np.zeros((n_samples, W.shape[1]) + D, dtype=W.dtype)
+        for e, where, atom in placed:
+            R[where] += h[e] * atom
+        return R
+    if V is None:
+        return render()
+    reg = eps + (sparsity if sparsity > 0 else 0.)
+    for _ in range(n_iterations):
+        R = render()
+        neg, pos = np.zeros(len(h), dtype=W.dtype), np.zeros(len(h), dtype=W.dtype)
+        for e, where, atom in placed:
+            neg[e] += np.sum(atom * V[where])
+            pos[e] += np.sum(atom * R[where])
+        h = h * neg / (pos + reg)
+    return h
+
+
+def events_gain_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], n_samples: int, mode: str, sample, plane, shift, strength,
+                      V: np.ndarray) -> np.ndarray:
+    """[K] float64: what each event explains, on the host, for backends without ``event_gains`` -- the semantics of
+    tnmf_hip_events_gain (include/tnmf_hip.h, "events"): the energy 1/2 ||V - R||^2 of the list without the event minus that
+    of the list, ``h a + h^2 b / 2`` with ``a = <phi, V - R>``, ``b = ||phi||^2`` and phi the event's images summed into a
+    dense sample (so images that overlap are added before they are squared).  Not on the hip path."""
+    A, D, shift_shape = _shapes(W, sample_shape, mode)
+    W, V = np.asarray(W, dtype=np.float64), np.asarray(V, dtype=np.float64)
+    h = np.array(strength, dtype=np.float64).reshape(-1)
+    residual = V - events_numpy(W, D, n_samples, mode, sample, plane, shift, h)
+    event, q = event_images(shift, A, shift_shape, mode)
+    gain = np.zeros(len(h))
+    for e in range(len(h)):
+        phi = np.zeros((W.shape[1],) + D)
+        for at in q[event == e]:
+            clipped = _clip(at, A, D)
+            if clipped:
+                phi[(slice(None),) + clipped[0]] += W[(int(plane[e]), slice(None)) + clipped[1]]
+        gain[e] = h[e] * np.sum(phi * residual[int(sample[e])]) + 0.5 * h[e] * h[e] * np.sum(phi * phi)
+    return gain
+
+
+def event_boxes(shift: np.ndarray, atom_shape: Tuple[int, ...], sample_shape: Tuple[int, ...], shift_shape: Tuple[int, ...],
+                mode: str):
+    """(lo [K, k], hi [K, k]): per event the bounding box ``lo .. hi - 1`` of the pixels of the sample its images cover
+    (``event_images``, each image clipped to the sample); ``hi <= lo`` on an axis for an event without such a pixel."""
+    A, D = np.asarray(atom_shape, dtype=np.int64), np.asarray(sample_shape, dtype=np.int64)
+    K = len(np.asarray(shift).reshape(-1, len(atom_shape)))
+    event, q = event_images(shift, tuple(atom_shape), tuple(shift_shape), mode)
+    first, last = np.maximum(q - (A - 1), 0), np.minimum(q + 1, D)
+    inside = np.all(last > first, axis=1)
+    lo, hi = np.tile(D, (K, 1)), np.zeros((K, len(A)), dtype=np.int64)
+    np.minimum.at(lo, event[inside], first[inside])
+    np.maximum.at(hi, event[inside], last[inside])
+    return lo, hi
+
+
+def _occurrence(W: np.ndarray, sample_shape: Tuple[int, ...], shift_shape: Tuple[int, ...], mode: str, plane: int,
+                shift) -> np.ndarray:
+    """phi [C, *D] in float64: plane ``plane`` of ``W`` at ``shift`` -- all its images (``event_images``), clipped to the
+    sample, images that overlap added."""
+    A, D = tuple(W.shape[2:]), tuple(sample_shape)
+    phi = np.zeros((W.shape[1],) + D)
+    for at in event_images(np.asarray(shift).reshape(1, -1), A, shift_shape, mode)[1]:
+        clipped = _clip(at, A, D)
+        if clipped:
+            phi[(slice(None),) + clipped[0]] += W[(int(plane), slice(None)) + clipped[1]]
+    return phi
+
+
+def events_norms_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], mode: str) -> np.ndarray:
+    """b [P, *S] float64: ``||phi_{p,u}||^2`` of every plane and shift, on the host, for backends without ``event_norms`` --
+    the semantics of tnmf_hip_events_norms (include/tnmf_hip.h, "pursuit"): the plane's sum of squares where the single
+    image of the shift lies wholly inside the sample, the occurrence summed into a dense sample everywhere else; 0 where
+    it has no pixel there.  Not on the hip path."""
+    W = np.asarray(W, dtype=np.float64)
+    A, D, S = _shapes(W, sample_shape, mode)
+    b = np.empty((W.shape[0],) + S)
+    shifts = np.stack(np.unravel_index(np.arange(int(np.prod(S))), S), axis=1)
+    event, q = event_images(shifts, A, S, mode)
+    whole = np.bincount(event, minlength=len(shifts)) == 1
+    first = q[:len(shifts)]   # (event_images lists the first image of every event, in event order, before the others)
+    whole &= np.all((first - (np.asarray(A) - 1) >= 0) & (first + 1 <= np.asarray(D)), axis=1)
+    for p in range(W.shape[0]):
+        flat = b[p].reshape(-1)
+        flat[whole] = np.sum(W[p] * W[p])
+        for e in np.flatnonzero(~whole):
+            phi = _occurrence(W, D, S, mode, p, shifts[e])
+            flat[e] = np.sum(phi * phi)
+    return b
+
+
+def pursuit_loop(shape: Tuple[int, ...], atom_shape: Tuple[int, ...], sample_shape: Tuple[int, ...], mode: str,
+                 min_gain: float, max_events: Optional[int], max_rounds: int, refit_iterations: int, sample, plane, shift,
+                 strength, candidates: Callable, score: Callable, refit: Callable):
+    """The rounds of ``TransformInvariantNMF.pursue_detections`` on the host, shared by every backend: the list (local
+    sample, plane, shift, strength) grows by each round's winners.  ``shape`` is ``[N, P, *S]``.  The arithmetic is the
+    caller's: ``candidates(sample, plane, shift, strength)`` -> (flat indices, gains) of the peaks of the gain map of the
+    residual of that list; ``score(sample, plane, shift, strength, idx)`` -> (strengths ``a / b`` in the element type,
+    exact gains in float64) of the entries ``idx`` against the same residual; ``refit(sample, plane, shift, strength, n)``
+    -> the strengths after n steps.  Returns (sample, plane, shift, strength, history [rounds, 3])."""
+    k = len(atom_shape)
+    S = tuple(int(x) for x in shape[2:])
+    history = []
+    for _ in range(max_rounds):
+        if max_events is not None and len(sample) >= max_events:
+            break
+        idx, val = candidates(sample, plane, shift, strength)
+        idx, val = np.asarray(idx, dtype=np.int64), np.asarray(val, dtype=np.float64)
+        at = np.unravel_index(idx, shape)
+        found = np.stack([a.astype(np.int64) for a in at[2:]], axis=1).reshape(len(idx), k)
+        lo, hi = event_boxes(found, atom_shape, sample_shape, S, mode)
+        # peaks are >= A apart on some axis, which does not see the wrapped and mirrored images: per sample the candidates in
+        # descending gain, ties in ascending index, kept unless their box meets one already kept in this round
+        kept, boxes = [], {}   # boxes: per sample the candidates kept in this round
+        for e in np.lexsort((idx, -val)):
+            mine = boxes.setdefault(int(at[0][e]), [])
+            if mine and np.any(np.all(np.maximum(lo[e], lo[mine]) < np.minimum(hi[e], hi[mine]), axis=1)):
+                continue
+            mine.append(e)
+            kept.append(e)
+        kept = np.sort(np.asarray(kept, dtype=np.int64))
+        h, gain = score(sample, plane, shift, strength, idx[kept])
+        h, gain = np.asarray(h), np.asarray(gain, dtype=np.float64)
+        above = gain > min_gain        # (the map only ranks: the exact gain decides)
+        kept, h, gain = kept[above], h[above], gain[above]
+        if max_events is not None and len(kept) > max_events - len(sample):
+            top = np.sort(np.lexsort((idx[kept], -gain))[:max_events - len(sample)])
+            kept, h, gain = kept[top], h[top], gain[top]
+        history.append((len(idx), len(kept), float(np.sum(gain))))
+        if not len(kept):
+            break
+        sample = np.concatenate([sample, at[0][kept].astype(np.int64)])
+        plane = np.concatenate([plane, at[1][kept].astype(np.int64)])
+        shift = np.concatenate([shift.reshape(-1, k), found[kept]])
+        strength = np.concatenate([strength, h.astype(strength.dtype)])
+        if refit_iterations:
+            strength = np.asarray(refit(sample, plane, shift, strength, refit_iterations)).astype(strength.dtype)
+    return sample, plane, shift, strength, np.array(history, dtype=np.float64).reshape(len(history), 3)
+
+
+def pursuit_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], n_samples: int, mode: str, sample, plane, shift, strength,
+                  V: np.ndarray, min_gain: float, max_events: Optional[int] = None, max_rounds: int = 100,
+                  refit_iterations: int = 10, eps: float = 1e-9):
+    """Forward selection on the host, for backends without ``pursue_events`` -- the semantics of the hip backend's hook and
+    of the entry points under "pursuit" in include/tnmf_hip.h, in float64: per round the residual ``d = V - R`` of the list,
+    the map ``a = <phi, d>`` as one correlation of d with every plane in the padded frame, folded onto the shifts by the
+    image table, ``g = a^2 / (2 b)``, its peaks, and the exact ``a`` and ``b`` of the kept ones from the occurrence summed
+    into a dense sample.  Returns (sample, plane, shift, strength, history).  Not on the hip path."""
+    A, D, S = _shapes(W, sample_shape, mode)
+    k = len(A)
+    W64, V64 = np.asarray(W, dtype=np.float64), np.asarray(V, dtype=np.float64)
+    shape = (n_samples, W.shape[0]) + S
+    b = events_norms_numpy(W64, D, mode)
+
+    def residual(sample, plane, shift, strength):
+        return V64 - events_numpy(W64, D, n_samples, mode, sample, plane, shift, np.asarray(strength, dtype=np.float64))
+
+    def candidates(sample, plane, shift, strength):
+        d = residual(sample, plane, shift, strength)
+        pad = np.pad(d, [(0, 0), (0, 0)] + [(a - 1, a - 1) for a in A])
+        Q = tuple(dd + a - 1 for dd, a in zip(D, A))
+        G = np.zeros((n_samples, W.shape[0]) + Q)   # the correlation at every position of the padded frame
+        for j in itertools.product(*[range(a) for a in A]):
+            window = pad[(slice(None), slice(None)) + tuple(slice(jj, jj + q) for jj, q in zip(j, Q))]
+            G += np.einsum('pc,nc...->np...', W64[(slice(None), slice(None)) + j], window)
+        for i, (a, s) in enumerate(zip(A, S)):      # the fold of the mode, axis by axis
+            u = np.arange(s)
+            out = np.take(G, u if mode == 'valid' else u + (a - 1), axis=2 + i)
+            if mode in ('circular', 'reflect'):
+                more = np.flatnonzero(u >= s - (a - 1)) if mode == 'circular' else np.flatnonzero((u >= 1) & (u <= a - 1))
+                second = more - (s - (a - 1)) if mode == 'circular' else (a - 1) - more
+                where = (slice(None),) * (2 + i) + (more,)
+                out[where] += np.take(G, second, axis=2 + i)
+            G = out
+        with np.errstate(divide='ignore', invalid='ignore'):
+            g = np.where((G > 0) & (b > 0), G * G / (2. * b), 0.)
+        g[(sample, plane) + tuple(np.asarray(shift).reshape(-1, k).T)] = 0.
+        return find_peaks_numpy(g, min_gain, tuple(a - 1 for a in A), W.shape[0])
+
+    def score(sample, plane, shift, strength, idx):
+        d = residual(sample, plane, shift, strength)
+        h, gain = np.zeros(len(idx), dtype=W.dtype), np.zeros(len(idx))
+        for i, at in enumerate(zip(*np.unravel_index(idx, shape))):
+            phi = _occurrence(W64, D, S, mode, at[1], at[2:])
+            a_, b_ = float(np.sum(phi * d[at[0]])), float(np.sum(phi * phi))
+            if a_ > 0 and b_ > 0:
+                h[i], gain[i] = a_ / b_, a_ * a_ / (2. * b_)
+        return h, gain
+
+    def refit(sample, plane, shift, strength, n):
+        return events_numpy(W, D, n_samples, mode, sample, plane, shift, strength, V=V, n_iterations=n, eps=eps)
+    return pursuit_loop(shape, A, D, mode, min_gain, max_events, max_rounds, refit_iterations,
+                        np.asarray(sample, dtype=np.int64), np.asarray(plane, dtype=np.int64),
+                        np.asarray(shift, dtype=np.int64).reshape(-1, k), np.asarray(strength, dtype=W.dtype), candidates,
+                        score, refit)
+
+
+def events_fit_numpy(W: np.ndarray, transforms, sample_shape: Tuple[int, ...], n_samples: int, mode: str, sample, plane,
+                     shift, strength, V: np.ndarray, n_iterations: int, update_H: bool = True, update_W: bool = True,
+                     sparsity: float = 0., eps: float = 1e-9, normalize: Optional[Callable] = None):
+    """Alternating updates of the strengths and of the dictionary on a fixed support, on the host, for backends without
+    ``fit_events``: the strengths' step of ``events_numpy`` and the W gradient of tnmf_hip_events_grad_W (include/tnmf_hip.h,
+    "events"), one loop over the images, folded onto ``W[M, C, *A]`` when ``transforms`` is given (the planes then index
+    the expanded dictionary), MU, and ``normalize(W)`` in place over the atom axes.  An atom whose summed neg is exactly zero
+    keeps its entries.  Returns (W, strengths); the arguments are left as they are.  Not on the hip path."""
+    W = np.array(W)
+    A, D, shift_shape = _shapes(W, sample_shape, mode)
+    h = np.array(strength, dtype=W.dtype).reshape(-1)
+    event, q = event_images(shift, A, shift_shape, mode)
+    placed = []   # per image: (event, where in the sample, which entries of the atom lie there)
+    for e, at in zip(event, q):
+        clipped = _clip(at, A, D)
+        if clipped:
+            placed.append((int(e), (int(sample[e]), slice(None)) + clipped[0], (int(plane[e]), slice(None)) + clipped[1]))
+    if normalize is None:
+        def normalize(arr):
+            arr /= arr.sum(axis=tuple(range(2, arr.ndim)), keepdims=True)
+
+    def render(W_eff):
+        R = np.zeros((n_samples, W.shape[1]) + D, dtype=W.dtype)
+        for e, where, entries in placed:
+            R[where] += h[e] * W_eff[entries]
+        return R
+    reg = eps + (sparsity if sparsity > 0 else 0.)
+    for _ in range(n_iterations):
+        W_eff = W if transforms is None else _transforms.expand(W, transforms)
+        if update_H:
+            R = render(W_eff)
+            neg, pos = np.zeros(len(h), dtype=W.dtype), np.zeros(len(h), dtype=W.dtype)
+            for e, where, entries in placed:
+                neg[e] += np.sum(W_eff[entries] * V[where])
+                pos[e] += np.sum(W_eff[entries] * R[where])
+            h = h * neg / (pos + reg)
+        if update_W:
+            R = render(W_eff)
+            neg, pos = np.zeros_like(W_eff), np.zeros_like(W_eff)
+            for e, where, entries in placed:
+                neg[entries] += h[e] * V[where]
+                pos[entries] += h[e] * R[where]
+            if transforms is not None:
+                neg, pos = _transforms.fold(neg, transforms), _transforms.fold(pos, transforms)
+            keep = ~neg.reshape(len(W), -1).any(axis=1)      # atoms without evidence
+            new = W * neg / (pos + eps)
+            with np.errstate(invalid='ignore', divide='ignore'):
+                normalize(new)
+            new[keep] = W[keep]
+            W = new
+    return W, h

@@ -2,7 +2,7 @@
 path='auto'; not part of bench.py).
 
     python tools/probes/pursuit_bench.py [--config 3] [--events 50] [--min-gain 1e-3] [--dense-iterations 300]
-                                         [--threshold-frac 0.05] [--warmup 1] [--repeats 3] [--out FILE]
+                                         [--threshold-frac 0.05] [--warmup 1] [--repeats 3] [--lib LIB.so] [--out FILE]
 
 A scene is planted on the device: a random normalised dictionary of the BASELINE config's shape (bench.py's CONFIGS) and
 `events` events per sample at random shifts with strengths 1 .. 2, rendered with the product's own kernel, plus noise of 1e-3.
@@ -43,6 +43,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--skip-dense', action='store_true')
+    ap.add_argument('--lib', default=None, help='an A/B build of the library under tnmf_amd/lib (make VARIANT=...)')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
 
@@ -52,6 +53,8 @@ def main():
     import torch
     from bench import CONFIGS
     from tnmf_amd import _lib
+    if args.lib:
+        _lib.LIB_PATH = args.lib if os.path.isabs(args.lib) else os.path.join(ROOT, 'tnmf_amd', 'lib', args.lib)
     from tnmf_amd.backends.HIP import _ptr
     from tnmf_amd.TransformInvariantNMF import TransformInvariantNMF
 
@@ -88,8 +91,8 @@ def main():
     nmf = model(V)
     be = nmf._backend
     half_norm = 0.5 * float(np.sum(V.astype(np.float64) ** 2))
-    common = dict(config=args.config, dtype='float32', path='auto', planted=K, events_per_sample=args.events,
-                  min_gain=args.min_gain, half_norm_V=round(half_norm, 3))
+    common = dict(library=os.path.basename(_lib.LIB_PATH), config=args.config, dtype='float32', path='auto', planted=K,
+                  events_per_sample=args.events, min_gain=args.min_gain, half_norm_V=round(half_norm, 3))
 
     def objective_of(det):
         R = nmf.reconstruct_detections(det).astype(np.float64)
