@@ -653,6 +653,38 @@ int tnmf_hip_pursuit_pick(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode
                           void *strength_out, double *gain_out /* double */, double *mag_out /* double, may be NULL */,
                           void *stream);
 
+/* ---- landscape: every event scored at its neighbouring shifts (ABI 8, additive: the version stays 8) ------------------------
+ * What the objective would be if a row of the list sat one shift over, everything else in the list held fixed: the quantity
+ * behind sub-pixel positions and behind moving a row.  For event e = (n, p, u, h_e) of a list whose render is R, the residual
+ * of the list WITHOUT the row is  d_e = V[n] - R[n] + h_e * phi_e,  phi_e = phi_{p,u} the occurrence as tnmf_hip_events_gain
+ * defines it.  For every offset delta in {-1, 0, +1}^ndim, u' = u + delta -- 3 neighbours on one shift axis, 9 on two, the
+ * neighbour index being delta_0 + 1 (ndim == 1) or (delta_0 + 1) * 3 + (delta_1 + 1) (ndim == 2) -- with t over the taps of
+ * image i of phi' = phi_{p,u'} whose pixel px(i, t) lies in the sample:
+ *   a_out[e, delta]   = sum_i sum_t w_t * d_e(px(i, t))
+ *   b_out[e, delta]   = sum_i sum_t w_t * phi'(px(i, t))        ( = ||phi'||^2, images that overlap added before squaring)
+ *   mag_out[e, delta] = sum_i sum_t |w_t * d_e(px(i, t))|       (the scale of the rounding error of a; may be NULL: not written)
+ * -- the sums of tnmf_hip_pursuit_pick with d_e in the place of d.  A neighbour whose u' lies outside the shift shape S of the
+ * mode on any axis gets a = b = mag = 0: nothing wraps from one end of the shift range to the other.  Replacing the row by
+ * one at u' at its best strength a / b lowers E = 1/2 ||V - R||^2, measured from the list without e, by a^2 / (2 b) where
+ * a > 0 and b > 0 (the caller's to form).  At delta = 0:  a - h_e * b = the a_e of tnmf_hip_events_gain, and
+ * h_e * a_e + 1/2 * h_e^2 * b = its gain[e].
+ * events, strength: those of tnmf_hip_events_gain, read and not written; duplicates are allowed, each row puts back only
+ * itself.  Outputs: [n_events, 3^ndim] DOUBLES, C-contiguous, whatever the element type.  d_e(px) = fma(h_e, phi_e(px),
+ * (double)V - (double)R) and every sum are taken in double in a fixed order -- tap t of an image in lane t % 64 in ascending
+ * t, images in image order, then the butterfly of the wave -- without atomics: the same operands give the same bits run after
+ * run, on any device.  Every element of the outputs is written -- they need no initialisation -- zeros for a row whose
+ * sample, plane or shift is out of range (no sample data is read for it).  Two paths, chosen per row by its geometry alone
+ * and giving the same bits: a row whose own occurrence and all 3^ndim neighbours are single images wholly inside the sample
+ * has its (A + 2)-sized patch of d_e staged once in LDS (when C * prod(A + 2) <= 2048 doubles) and b taken once as the
+ * plane's sum of squares; every other row walks each neighbour's images.  It reads W_eff, events, strength, V and R and
+ * writes the outputs, nothing else.  Workspace: none.  Asynchronous.  With n_events == 0 or N == 0 it does nothing.
+ * Refused before anything is written, as tnmf_hip_events_gain is: TNMF_E_NULL (ctx, geom, and with n_events > 0 and N > 0
+ * every operand but mag_out), TNMF_E_DTYPE, TNMF_E_UNSUPPORTED for volumes and for more than (2^31 - 1) / 9 events,
+ * TNMF_E_GEOM for any other ndim, sizes <= 0, a negative count, an unknown mode and the per-axis limits of the mode. */
+int tnmf_hip_events_landscape(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,
+                              const void *strength, long long n_events, const void *V, const void *R, double *a_out,
+                              double *b_out, double *mag_out /* may be NULL */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

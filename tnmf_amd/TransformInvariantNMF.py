@@ -33,7 +33,8 @@ from . import transforms as _transforms
 from .backends._Backend import Backend, sliceNone
 # (the host side of the events; the names stay importable from this module)
 from .events_host import (event_boxes, event_images, events_fit_numpy, events_gain_numpy,  # noqa: F401
-                          events_norms_numpy, events_numpy, find_peaks_numpy, pursuit_loop, pursuit_numpy)
+                          events_landscape_numpy, events_norms_numpy, events_numpy, find_peaks_numpy, landscape_gains,
+                          pursuit_loop, pursuit_numpy, relocation_hops)
 
 
 class MiniBatchAlgorithm(enum.Enum):
@@ -236,6 +237,7 @@ class TransformInvariantNMF:
         self.converged_ = False
         self._objective_buf = None   # the tap's per-sample buffer of the current fit
         self.pursuit_history_ = np.empty((0, 3))   # of the last pursue_detections
+        self.relocation_history_ = np.empty((0, 3))   # of the last relocate_detections
 
     # -- read-outs (reference :188-215) ---------------------------------------------------------------------
     @property
@@ -603,6 +605,106 @@ class TransformInvariantNMF:
         det = Detections(sample=sample, atom=plane // T, transform=plane % T, shift=shift, origin=shift - offset,
                          strength=np.asarray(strength))
         det = self.refit_detections(det, n_iterations, sparsity_H)
+        return det, self.detection_gains(det)
+
+    # -- detections moved: the landscape of the neighbouring shifts ----------------------------------------------------
+    def _landscape(self, det, distinct: bool, who: str):
+        """(a, b) ``[K, 3^k]`` float64 of the rows of ``det``, after the refusals and checks ``who`` shares with
+        ``detection_gains``, and the rows in the backend's terms."""
+        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
+            raise NotImplementedError(f'{who} covers the plain Frobenius objective (beta_loss 2, no weights)')
+        rows = sample, plane, shift, strength = self._events_of(det, distinct=distinct)
+        hook = getattr(self._backend, 'event_landscape', None)
+        if hook is not None:
+            a, b = hook(self._V, self._W_dict, sample, plane, shift, strength)
+        else:
+            a, b = events_landscape_numpy(
+                self._backend.to_ndarray(self._W_dict), self._V.shape[2:], int(self._H.shape[0]),
+                getattr(self._backend, '_reconstruction_mode', 'valid'), sample, plane, shift, strength, self._local_V())
+        return np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64), rows
+
+    def detection_landscape(self, det) -> Tuple[np.ndarray, np.ndarray]:
+        """(a, b), each ``[K] + (3,) * k`` float64: every row of ``det`` scored at its neighbouring shifts ``shift + delta``,
+        delta in {-1, 0, 1} per shift axis (index ``delta + 1``), with everything else in the list held fixed.  With R =
+        ``reconstruct_detections(det)`` and ``d = V - R + h phi`` the residual of the list without the row, ``a = <phi', d>``
+        and ``b = ||phi'||^2`` for the row's atom at the neighbouring shift (phi': all its images, clipped to the sample).  A
+        row there at its best strength ``a / b`` would take ``a^2 / (2 b)`` off the objective of the list without the row
+        (for ``a > 0``).  Zeros for a neighbour outside the shift shape: nothing wraps from one end of the shift range to the
+        other.  At the centre ``h (a - h b) + h^2 b / 2`` is the row's ``detection_gains``.  Duplicate rows put back only
+        themselves.  On a backend with ``event_landscape`` the list is rendered and scored on the device and only the
+        ``2 K 3^k`` numbers are copied.  The plain Frobenius objective only."""
+        a, b, _ = self._landscape(det, False, 'detection_landscape')
+        shape = (len(a),) + (3,) * len(self.atom_shape)
+        return a.reshape(shape), b.reshape(shape)
+
+    def refine_detections(self, det) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(offset ``[K, k]`` float64, gain ``[K]`` float64, is_peak ``[K]`` bool): sub-pixel positions from
+        ``detection_landscape``.  With ``g = a^2 / (2 b)`` (0 where ``a <= 0`` or ``b <= 0``), ``gain`` is g at the row's own
+        shift.  Per shift axis i a parabola goes through g at delta = -1, 0, +1 along that axis: with ``c = g- - 2 g0 + g+``,
+        where ``g0 >= max(g-, g+)`` and ``c < 0`` its vertex ``offset_i = (g- - g+) / (2 c)``, clipped to [-1/2, 1/2];
+        elsewhere -- the row is not a maximum along the axis, or sits where the axis ends -- ``offset_i = 0`` and ``is_peak``
+        is False for the row.  ``det.origin + offset`` is the sub-pixel origin of the atom.  The rows need not be distinct.
+        The plain Frobenius objective only."""
+        a, b, _ = self._landscape(det, False, 'refine_detections')
+        k = len(self.atom_shape)
+        g = landscape_gains(a, b).reshape((len(a),) + (3,) * k)
+        centre = (slice(None),) + (1,) * k
+        g0 = g[centre]
+        offset, is_peak = np.zeros((len(a), k)), np.ones(len(a), dtype=bool)
+        for i in range(k):
+            lo, hi = (g[centre[:1 + i] + (j,) + centre[2 + i:]] for j in (0, 2))
+            c = lo - 2. * g0 + hi
+            ok = (g0 >= np.maximum(lo, hi)) & (c < 0)
+            offset[:, i] = np.where(ok, np.clip(0.5 * (lo - hi) / np.where(ok, c, -1.), -0.5, 0.5), 0.) + 0.
+            is_peak &= ok
+        return offset, g0.copy(), is_peak
+
+    def relocate_detections(self, det, n_iterations: int = 50, sparsity_H: float = 0., max_rounds: int = 100,
+                            min_improvement: float = 0.) -> Tuple[Detections, np.ndarray]:
+        """Local search over the shifts: the rows of ``det`` moved to where the data explains them better, refitted, and
+        their gains -- the third list operation beside ``pursue_detections`` (grow) and ``prune_detections`` (shrink), and
+        what it returns is what they return.  Each round refits the strengths (``refit_detections`` with ``n_iterations`` and
+        ``sparsity_H``) and takes the landscape (``detection_landscape``).  For a row of strength h, with ``g = a^2 / (2 b)``,
+        ``improvement = max over the neighbours of g - (h a_e + h^2 b_0 / 2)``, ``a_e = a_0 - h b_0``: what the objective falls
+        by when the row hops to its best neighbour at the strength ``a / b`` there.  The candidates are the rows with
+        ``improvement > min_improvement`` whose best neighbour has ``g > 0`` -- a row the data supports nowhere around it
+        stays where it is, even with a negative gain of its own: dropping it is ``prune_detections``' part.  Per sample the
+        candidates are walked in descending improvement (ties in row order) and hop
+        -- to the neighbour of the lowest index among equal ones, ``atom`` and ``transform`` unchanged -- unless the bounding
+        box of the old and the new occurrence together meets that of a hop already made in this round (rows with disjoint
+        footprints do not interact, so their hops together are exact; the others are scored again next round), or the
+        target is already a row of the list (the list stays distinct).  It stops when a round makes no hop or after
+        ``max_rounds`` rounds of hopping; ``max_rounds=0`` is a refit with its gains.  Read-out: ``relocation_history_``
+        ([rounds, 3]: candidates, hops, the sum of the hops' improvements).  The hops are chosen on the host; refit, render
+        and landscape run where the backend runs them.  The rows must be distinct; the plain Frobenius objective only.  With
+        a process group every rank moves the rows of its own samples: the call is not collective."""
+        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
+            raise NotImplementedError('relocate_detections covers the plain Frobenius objective (beta_loss 2, no weights)')
+        if (isinstance(min_improvement, (bool, np.bool_)) or not isinstance(min_improvement, numbers.Real)
+                or not math.isfinite(min_improvement) or min_improvement < 0):
+            raise ValueError(f'min_improvement must be a finite number >= 0, not {min_improvement!r}')
+        if (isinstance(max_rounds, (bool, np.bool_)) or not isinstance(max_rounds, numbers.Integral)
+                or max_rounds < 0):
+            raise ValueError(f'max_rounds must be an int >= 0, not {max_rounds!r}')
+        mode = getattr(self._backend, '_reconstruction_mode', 'valid')
+        offset = np.array([a - 1 if mode == 'valid' else 0 for a in self.atom_shape], dtype=np.int64)
+        history, rounds = [], 0
+        while True:
+            det = self.refit_detections(det, n_iterations, sparsity_H)
+            if rounds >= max_rounds:
+                break
+            a, b, (sample, plane, shift, strength) = self._landscape(det, True, 'relocate_detections')
+            hopped, target, h, n_candidates, total = relocation_hops(
+                sample, plane, shift, strength, a, b, self.atom_shape, self._V.shape[2:],
+                tuple(int(x) for x in self._H.shape[2:]), mode, float(min_improvement))
+            history.append((n_candidates, len(hopped), total))
+            if not len(hopped):
+                break
+            shift, strength = np.array(det.shift, dtype=np.int64).reshape(len(det), -1), np.array(det.strength)
+            shift[hopped], strength[hopped] = target, h.astype(strength.dtype)
+            det = dataclasses.replace(det, shift=shift, origin=shift - offset, strength=strength)
+            rounds += 1
+        self.relocation_history_ = np.array(history, dtype=np.float64).reshape(len(history), 3)
         return det, self.detection_gains(det)
 
     def fit_detections(self, det, n_iterations: int = 50, sparsity_H: float = 0., update_H: bool = True,

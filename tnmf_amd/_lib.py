@@ -32,7 +32,7 @@ EXPORTS = (
     'tnmf_hip_ctx_set_objective_tap', 'tnmf_hip_sample_objective',
     'tnmf_hip_find_peaks',
     'tnmf_hip_events_render', 'tnmf_hip_events_update', 'tnmf_hip_events_grad_W', 'tnmf_hip_events_gain',
-    'tnmf_hip_events_norms', 'tnmf_hip_pursuit_score', 'tnmf_hip_pursuit_pick',
+    'tnmf_hip_events_norms', 'tnmf_hip_pursuit_score', 'tnmf_hip_pursuit_pick', 'tnmf_hip_events_landscape',
 )
 
 MODES = {'valid': 0, 'full': 1, 'circular': 2, 'reflect': 3}
@@ -157,6 +157,7 @@ def load() -> ctypes.CDLL:
     lib.tnmf_hip_events_norms.argtypes = [vp, gp, ci, vp, vp, vp]
     lib.tnmf_hip_pursuit_score.argtypes = [vp, gp, vp, vp, vp, vp, ll, vp]
     lib.tnmf_hip_pursuit_pick.argtypes = [vp, gp, ci, vp, vp, ll, vp, vp, vp, vp, vp, vp, vp]
+    lib.tnmf_hip_events_landscape.argtypes = [vp, gp, ci, vp, vp, vp, ll, vp, vp, vp, vp, vp, vp]
     lib.tnmf_hip_pad_H.argtypes = [vp, gp, ci, vp, vp, vp]
     lib.tnmf_hip_fold_H.argtypes = [vp, gp, ci, vp, vp, vp]
     for name in EXPORTS:

@@ -976,6 +976,38 @@ class HIP_Backend(Backend):
         R = self.render_event_list(W, images, cell_start, strength)
         return self.gain_event_list(W, events, strength, R).cpu().numpy()
 
+    def landscape_event_list(self, W: torch.Tensor, events: torch.Tensor, strength: torch.Tensor, R: torch.Tensor,
+                             with_magnitude: bool = False):
+        """(a, b) [K, 3^k] float64 on the device: every event at its neighbouring shifts against the residual of the list
+        without it, R being the render of the strengths -> tnmf_hip_events_landscape; with ``with_magnitude`` (a, b, mag),
+        mag the sum of the magnitudes of the terms of a."""
+        self._check_W(W)
+        assert strength.is_contiguous() and strength.dtype == self._torch_dtype and events.shape[0] == strength.numel()
+        assert R.is_contiguous() and R.dtype == self._torch_dtype and tuple(R.shape) == tuple(self._V_dev.shape)
+        K, nb = strength.numel(), 3 ** len(self.atom_shape)
+        a = torch.empty((K, nb), dtype=torch.float64, device=self._device)
+        b = torch.empty((K, nb), dtype=torch.float64, device=self._device)
+        mag = torch.empty((K, nb), dtype=torch.float64, device=self._device) if with_magnitude else None
+        with self._timed('events_landscape'):
+            _lib.check(self._lib.tnmf_hip_events_landscape(
+                self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0])), self._mode, _ptr(W), _ptr(events),
+                _ptr(strength), K, _ptr(self._V_dev), _ptr(R), _ptr(a), _ptr(b), _ptr(mag), self._stream()),
+                'tnmf_hip_events_landscape')
+        return (a, b, mag) if with_magnitude else (a, b)
+
+    def event_landscape(self, V, W: torch.Tensor, sample, plane, shift, strength):
+        """(a, b) [K, 3^k] float64 on the host: per event and neighbouring shift the correlation of the occurrence there
+        with the residual of the list without the event, and its norm, against the resident samples (`V` is the array given
+        to initialize(), as for the other hooks): one render of the list and one kernel; only the 2 * K * 3^k doubles are
+        copied.  Duplicate events put back only themselves."""
+        if self._G_dev is not None:
+            raise NotImplementedError('event_landscape is unweighted')
+        sample, plane, shift, strength = self._check_events(W.shape[0], sample, plane, shift, strength)
+        images, cell_start, events = self.event_list(sample, plane, shift)
+        R = self.render_event_list(W, images, cell_start, strength)
+        a, b = self.landscape_event_list(W, events, strength, R)
+        return a.cpu().numpy(), b.cpu().numpy()
+
     # -- pursuit: the list found by forward selection ---------------------------------------------------------------------
     # A round (include/tnmf_hip.h, "pursuit") is the H gradient's numerator of the residual, the gain map, its peaks and
     # the exact score of the kept ones; the rows are chosen on the host (events_host.pursuit_loop) from the

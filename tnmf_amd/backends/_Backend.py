@@ -39,7 +39,9 @@ shift in its H, strength; include/tnmf_hip.h, "events"): ``render_events(W, samp
 (backend-native ``[n_local, C, *D]``) and ``refit_events(V, W, sample, plane, shift, strength, n_iterations, sparsity=0.,
 eps=1e-9) -> strength`` (backend-native ``[K]``); without them ``reconstruct_detections`` / ``refit_detections`` run
 ``events_numpy`` on the host.  It may also offer ``event_gains(V, W, sample, plane, shift, strength) -> ndarray[K]`` (float64,
-host): what each event explains; without it ``detection_gains`` runs ``events_gain_numpy`` on the host.
+host): what each event explains; without it ``detection_gains`` runs ``events_gain_numpy`` on the host.  And
+``event_landscape(V, W, sample, plane, shift, strength) -> (a, b)`` (float64 ``[K, 3^k]``, host): every event at its
+neighbouring shifts (include/tnmf_hip.h, "landscape"); without it ``detection_landscape`` runs ``events_landscape_numpy``.
 """
 import abc
 from typing import Optional, Sequence, Tuple, Union

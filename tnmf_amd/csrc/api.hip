@@ -1501,4 +1501,19 @@ int tnmf_hip_pursuit_pick(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode
                         gain_out, mag_out, static_cast<hipStream_t>(stream));
 }
 
+int tnmf_hip_events_landscape(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,
+                              const void *strength, long long n_events, const void *V, const void *R, double *a_out,
+                              double *b_out, double *mag_out, void *stream) {
+    EventGeo g;
+    int S[2];
+    const int rc = events_enter(ctx, geom, mode, &g, S);
+    if (rc != TNMF_OK) return rc;
+    if (n_events < 0) return TNMF_E_GEOM;
+    if (n_events > 0x7fffffffLL / 9) return TNMF_E_UNSUPPORTED;
+    if (n_events > 0 && g.N > 0 && (!W_eff || !events || !strength || !V || !R || !a_out || !b_out)) return TNMF_E_NULL;
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return events_landscape(ctx, g, geom->ndim, geom->dtype, mode, S[0], S[1], W_eff, events, strength, n_events, V, R,
+                            a_out, b_out, mag_out, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

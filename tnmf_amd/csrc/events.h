@@ -65,3 +65,11 @@ int pursuit_score(tnmf_hip_ctx *ctx, int dtype, long long planes, int P, int Sy,
 int pursuit_pick(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const void *W,
                  const long long *idx, long long n_picked, const void *V, const void *R, int *events, void *strength,
                  double *gain, double *mag, hipStream_t s);
+
+// Landscape (landscape.hip; tnmf_hip_events_landscape).
+// a, b, mag[n_events, 3^ndim] (DOUBLES; mag may be NULL): per row and neighbour shift u + delta, delta in {-1, 0, 1}^ndim, the
+// sums of pursuit_pick against the residual of the list without the row, V - R + h_e phi_e; zeros for a neighbour outside
+// the shift shape and for a row out of range.  Every element is written.
+int events_landscape(tnmf_hip_ctx *ctx, const EventGeo &g, int ndim, int dtype, int mode, int Sy, int Sx, const void *W,
+                     const int *events, const void *strength, long long n_events, const void *V, const void *R, double *a,
+                     double *b, double *mag, hipStream_t s);

@@ -1,8 +1,9 @@
 """
 The events of the front end on the host: the image table of an event, the clip of an image to the sample, and the NumPy
 fallbacks for a backend without the events hooks (tnmf_amd/backends/_Backend.py) -- peaks, render and refit, gains, norms,
-forward selection, the fit of the dictionary on a fixed support.  ``pursuit_loop``, the rounds of the forward selection, is
-shared by every backend, the hip backend included; nothing else here is on the hip path.
+forward selection, the landscape of the neighbouring shifts, the fit of the dictionary on a fixed support.
+``pursuit_loop``, the rounds of the forward selection, and ``relocation_hops``, the choice of a round of relocation, work on
+lists alone and are shared by every backend, the hip backend included; nothing else here is on the hip path.
 """
 import itertools
 from typing import Callable, Optional, Tuple
@@ -184,6 +185,98 @@ def events_norms_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], mode: str) 
             phi = _occurrence(W, D, S, mode, p, shifts[e])
             flat[e] = np.sum(phi * phi)
     return b
+
+
+def events_landscape_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], n_samples: int, mode: str, sample, plane, shift,
+                           strength, V: np.ndarray, with_magnitude: bool = False):
+    """(a, b) ``[K, 3^k]`` float64 (with ``with_magnitude`` also mag): every event at its neighbouring shifts, on the host, for
+    backends without ``event_landscape`` -- the semantics of tnmf_hip_events_landscape (include/tnmf_hip.h, "landscape"):
+    with ``d_e = V - R + h_e phi_e`` the residual of the list without row e, for every offset delta in {-1, 0, 1}^k in C order
+    ``a = <phi', d_e>``, ``b = ||phi'||^2`` and ``mag = sum |w d_e|`` over the taps of the images of phi', the occurrence of
+    the row's plane at ``shift + delta`` summed into a dense sample; zeros for a neighbour outside the shift shape.
+    Duplicate rows put back only themselves.  Not on the hip path."""
+    A, D, S = _shapes(W, sample_shape, mode)
+    k = len(A)
+    W, V = np.asarray(W, dtype=np.float64), np.asarray(V, dtype=np.float64)
+    h = np.array(strength, dtype=np.float64).reshape(-1)
+    K = len(h)
+    shift = np.asarray(shift, dtype=np.int64).reshape(K, k)
+    residual = V - events_numpy(W, D, n_samples, mode, sample, plane, shift, h)
+    absW = np.abs(W)
+    a, b, mag = np.zeros((K, 3 ** k)), np.zeros((K, 3 ** k)), np.zeros((K, 3 ** k))
+    for e in range(K):
+        d = residual[int(sample[e])] + h[e] * _occurrence(W, D, S, mode, plane[e], shift[e])
+        for j, delta in enumerate(itertools.product((-1, 0, 1), repeat=k)):
+            u = shift[e] + np.asarray(delta)
+            if np.any(u < 0) or np.any(u >= np.asarray(S)):
+                continue
+            phi = _occurrence(W, D, S, mode, plane[e], u)
+            a[e, j], b[e, j] = np.sum(phi * d), np.sum(phi * phi)
+            if with_magnitude:   # (the taps of all images on a pixel share its d: their magnitudes add up)
+                mag[e, j] = np.sum(_occurrence(absW, D, S, mode, plane[e], u) * np.abs(d))
+    return (a, b, mag) if with_magnitude else (a, b)
+
+
+def landscape_gains(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """``a^2 / (2 b)`` where ``a > 0`` and ``b > 0``, else 0: what a row at that shift, at its best strength ``a / b``, takes off
+    the objective of the list without the row."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    live = (a > 0) & (b > 0)
+    return np.where(live, a * a / (2. * np.where(live, b, 1.)), 0.)
+
+
+def relocation_hops(sample, plane, shift, strength, a, b, atom_shape: Tuple[int, ...], sample_shape: Tuple[int, ...],
+                    shift_shape: Tuple[int, ...], mode: str, min_improvement: float):
+    """The choice of one round of ``TransformInvariantNMF.relocate_detections`` on the host, shared by every backend: from
+    the landscape ``(a, b) [K, 3^k]`` of the distinct rows (sample, plane, shift, strength) -> (rows [J] ascending, their new
+    shifts [J, k], their new strengths ``a / b`` [J] float64, the number of candidates, the sum of the hops' improvements).
+    ``improvement = max over delta != 0 of g - (h a_e + h^2 b_0 / 2)``, g = ``landscape_gains`` and ``a_e = a_0 - h b_0``: what
+    the objective falls by when the row hops.  Candidates have ``improvement > min_improvement`` and ``g > 0`` at their best
+    neighbour (a row with nowhere to go stays, even where its own gain is negative); per sample they are walked
+    in descending improvement, ties in row order, each to its best neighbour (the lowest neighbour index on ties), unless the
+    bounding box of its old and new occurrence together meets that of a hop already made in this round, or the target is a
+    row of the list."""
+    k = len(atom_shape)
+    K = len(sample)
+    shift = np.asarray(shift, dtype=np.int64).reshape(K, k)
+    h = np.asarray(strength, dtype=np.float64).reshape(-1)
+    a, b = np.asarray(a, dtype=np.float64).reshape(K, 3 ** k), np.asarray(b, dtype=np.float64).reshape(K, 3 ** k)
+    empty = (np.zeros(0, dtype=np.int64), np.zeros((0, k), dtype=np.int64), np.zeros(0), 0, 0.)
+    if not K:
+        return empty
+    centre = (3 ** k - 1) // 2
+    g = landscape_gains(a, b)
+    own = h * (a[:, centre] - h * b[:, centre]) + 0.5 * h * h * b[:, centre]
+    g[:, centre] = -np.inf
+    best = np.argmax(g, axis=1)           # (the first of equal maxima: the lowest neighbour index)
+    there = g[np.arange(K), best]
+    improvement = there - own
+    # a hop needs somewhere to go: g > 0 at the best neighbour, i.e. a > 0 and b > 0 there, so the strength a / b is finite
+    # and positive and the neighbour lies inside the shift shape.  A row the data does not support anywhere around it
+    # (every g = 0) stays where it is, whatever its own gain: removing it is prune_detections' business.
+    candidates = np.flatnonzero((improvement > min_improvement) & (there > 0))
+    if not len(candidates):
+        return empty
+    deltas = np.array(list(itertools.product((-1, 0, 1), repeat=k)), dtype=np.int64)
+    target = shift + deltas[best]
+    lo0, hi0 = event_boxes(shift, atom_shape, sample_shape, shift_shape, mode)
+    lo1, hi1 = event_boxes(target, atom_shape, sample_shape, shift_shape, mode)
+    lo, hi = np.minimum(lo0, lo1), np.maximum(hi0, hi1)
+    rows = set(map(tuple, np.column_stack([sample, plane, shift]).tolist()))
+    hopped, boxes = [], {}   # boxes: per sample the hops made in this round
+    for e in candidates[np.argsort(-improvement[candidates], kind='stable')]:
+        mine = boxes.setdefault(int(sample[e]), [])
+        if mine and np.any(np.all(np.maximum(lo[e], lo[mine]) < np.minimum(hi[e], hi[mine]), axis=1)):
+            continue
+        to = (int(sample[e]), int(plane[e])) + tuple(int(x) for x in target[e])
+        if to in rows:
+            continue
+        rows.add(to)
+        mine.append(e)
+        hopped.append(e)
+    hopped = np.sort(np.asarray(hopped, dtype=np.int64))
+    return (hopped, target[hopped], a[hopped, best[hopped]] / b[hopped, best[hopped]], len(candidates),
+            float(np.sum(improvement[hopped])))
 
 
 def pursuit_loop(shape: Tuple[int, ...], atom_shape: Tuple[int, ...], sample_shape: Tuple[int, ...], mode: str,
