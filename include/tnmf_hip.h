@@ -685,6 +685,79 @@ int tnmf_hip_events_landscape(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int 
                               const void *strength, long long n_events, const void *V, const void *R, double *a_out,
                               double *b_out, double *mag_out /* may be NULL */, void *stream);
 
+/* ---- events: exact strengths (ABI 8, additive: the version stays 8) -------------------------------------------------------
+ * The strengths that MINIMISE the Frobenius objective on a fixed support -- the orthogonal step of orthogonal matching
+ * pursuit -- computed on the list alone.  For K distinct events with occurrences phi_e (all images, clipped to the sample,
+ * images that overlap added: tnmf_hip_events_gain) the objective is a quadratic in the strengths,
+ *   E(h) = 1/2 ||V||^2 - c' h + 1/2 h' G h,     c_i = <phi_i, V>,     G_ij = <phi_i, phi_j>,
+ * and G_ij is non-zero only for rows of one sample whose footprints meet: G is sparse.  The samples enter once, through c.
+ * c and G are DOUBLES whatever the element type; no entry uses float atomics, each writes every element of its outputs,
+ * and the same operands give the same bits run after run.  geom as for the events (h_row_stride is not read), 1 or 2 shift
+ * axes, float32 and float64, every mode.
+ *
+ * tnmf_hip_events_pairs: the candidate pattern of G above the diagonal.  images / cell_start: THE IMAGE LIST of
+ * tnmf_hip_events_render, sorted by (sample, cell); events: the n_events rows of tnmf_hip_events_update (read for the sample
+ * of a row).  A row pair i < j of the same sample is a candidate when some image of i and some image of j are closer than
+ * the atom extent on every shift axis, |q_i - q_j| < A: a SUPERSET of the pairs with G_ij != 0 -- a candidate whose overlap
+ * lies wholly outside the sample has the value exactly 0.  The work is proportional to the images in the cells an image
+ * can reach.  Output as tnmf_hip_find_peaks': count_out (one unsigned 64-bit word on the device) is zeroed on the stream,
+ * then counts EVERY candidate found; they are appended in no particular order as pairs_out[slot] = i * n_events + j while
+ * slot < capacity, once per image pair (a row pair may appear up to 16 times: the caller sorts and removes duplicates).
+ * Nothing is written at or beyond `capacity`; a count above it is the size to come back with.  A row of the image list whose
+ * event is out of range, whose position is negative or beyond the cells, or whose event's sample is out of range is
+ * skipped, cell_start is clamped to [0, n_images]: nothing is read or written out of bounds.  Asynchronous.
+ * Refused before anything is written: TNMF_E_NULL (ctx, geom, count_out, pairs_out when capacity > 0, the lists when the
+ * counts and N are positive), TNMF_E_DTYPE, TNMF_E_UNSUPPORTED for volumes and for more than 2^31 - 1 images, events or
+ * stored entries (capacity), TNMF_E_GEOM for any other ndim, sizes <= 0 and negative counts.
+ *
+ * tnmf_hip_events_gram: val_out[p] = <phi_i, phi_j> for the n_pairs pairs (i, j) = (row_i[p], row_j[p]), i == j included:
+ * one wave per pair, the lanes over row i's taps in the order of tnmf_hip_events_gain, phi_j summed over its images at each
+ * pixel; on the diagonal it is that entry's b_e.  <phi_i, phi_j> and <phi_j, phi_i> differ in the order of their additions:
+ * a caller that wants a bit-symmetric matrix computes i <= j and mirrors.  val_out[p] = 0 for an index outside
+ * [0, n_events), a row whose sample, plane or shift is out of range, and rows of two samples.  Asynchronous.
+ * Refused before anything is written: TNMF_E_NULL (ctx, geom, and with n_pairs > 0 every operand), TNMF_E_DTYPE,
+ * TNMF_E_UNSUPPORTED for volumes and for more than 2^31 - 1 events or pairs, TNMF_E_GEOM as for tnmf_hip_events_gain.
+ *
+ * tnmf_hip_events_project: c_out[e] = <phi_e, V> = sum_i sum_t w_t * V(px(i, t)) for every row, the walk and the order of
+ * tnmf_hip_events_gain; 0 for a row out of range (no sample data is read for it).  Asynchronous.  Refusals as for
+ * tnmf_hip_events_gain (every operand with n_events > 0).
+ *
+ * tnmf_hip_events_nnls: minimise 1/2 h' G h - c' h over h >= 0, in double.  G: CSR on the device -- row_start[n_rows + 1],
+ * col[nnz] ascending within a row, val[nnz], the diagonal present, symmetric; c[n_rows]; h_inout[n_rows]: the start on
+ * entry (projected onto h >= 0; NaN counts as 0), the last iterate on return.  A row with G_ii <= 0 has no pixel in the
+ * sample: its strength is 0 and it takes no part.  The method is projected gradient with step 1 / L, L = max_i sum_j |G_ij|
+ * (Gershgorin; exact for non-negative atoms), Nesterov momentum and the gradient restart <y - x+, x+ - x> > 0.
+ * The stopping quantity, evaluated AT THE ITERATE RETURNED (not at the momentum point), is
+ *   kkt = max_i |pg_i| / max_i |c_i|,   g = G h - c,   pg_i = g_i where h_i > 0,   min(g_i, 0) where h_i = 0;
+ * with max |c| = 0 the answer is h = 0 with kkt = 0.  It stops at kkt <= tol or after max_iterations steps;
+ * max_iterations = 0 returns the projected start with its kkt.  The host reads ONE double every check_every iterations
+ * (iterations 0, check_every, 2 * check_every, ... and max_iterations) and nothing else, so the iteration count it stops
+ * at is a multiple of check_every.  This entry is SYNCHRONOUS at those reads; on return h_inout is queued on the stream.
+ * HOST outputs: iterations_out, kkt_out (the last kkt read), converged_out (kkt <= tol), history_out [history_capacity, 2]
+ * doubles (iteration, kkt) of the checks (may be NULL with capacity 0), n_history_out (may be NULL) the pairs stored.
+ * workspace: 7 * n_rows + 8 doubles on the device, uninitialised, the caller's.  Column indices outside [0, n_rows) are
+ * skipped and row_start is clamped to [0, nnz]: nothing is read out of bounds.  With n_rows == 0 it does nothing
+ * (0 iterations, converged).
+ * Refused before anything is written: TNMF_E_NULL (ctx, the three scalar outputs, and with n_rows > 0 every device
+ * operand), TNMF_E_GEOM for negative sizes, max_iterations < 0, check_every < 1, TNMF_E_UNSUPPORTED for a tol that is not
+ * finite and > 0 and for more than 2^31 - 1 rows or entries. */
+int tnmf_hip_events_pairs(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const int *images, long long n_images,
+                          const int *cell_start, const int *events, long long n_events, long long *pairs_out,
+                          size_t capacity, unsigned long long *count_out, void *stream);
+
+int tnmf_hip_events_gram(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,
+                         long long n_events, const int *row_i, const int *row_j, long long n_pairs,
+                         double *val_out /* double */, void *stream);
+
+int tnmf_hip_events_project(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,
+                            long long n_events, const void *V, double *c_out /* double */, void *stream);
+
+int tnmf_hip_events_nnls(tnmf_hip_ctx *ctx, long long n_rows, long long nnz, const int *row_start, const int *col,
+                         const double *val, const double *c, double *h_inout, double tol, int max_iterations,
+                         int check_every, double *workspace, int *iterations_out /* host */, double *kkt_out /* host */,
+                         int *converged_out /* host */, double *history_out /* host, may be NULL */, int history_capacity,
+                         int *n_history_out /* host, may be NULL */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

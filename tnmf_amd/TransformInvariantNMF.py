@@ -33,8 +33,9 @@ from . import transforms as _transforms
 from .backends._Backend import Backend, sliceNone
 # (the host side of the events; the names stay importable from this module)
 from .events_host import (event_boxes, event_images, events_fit_numpy, events_gain_numpy,  # noqa: F401
-                          events_landscape_numpy, events_norms_numpy, events_numpy, find_peaks_numpy, landscape_gains,
-                          pursuit_loop, pursuit_numpy, relocation_hops)
+                          events_gram_numpy, events_landscape_numpy, events_norms_numpy, events_numpy,
+                          events_solve_numpy, find_peaks_numpy, landscape_gains, pursuit_loop, pursuit_numpy,
+                          relocation_hops)
 
 
 class MiniBatchAlgorithm(enum.Enum):
@@ -238,6 +239,9 @@ class TransformInvariantNMF:
         self._objective_buf = None   # the tap's per-sample buffer of the current fit
         self.pursuit_history_ = np.empty((0, 3))   # of the last pursue_detections
         self.relocation_history_ = np.empty((0, 3))   # of the last relocate_detections
+        self.solve_history_ = np.empty((0, 2))   # of the last solve_detections: (iteration, kkt) of its checks
+        self.solve_n_iter_ = 0
+        self.solve_converged_ = False
 
     # -- read-outs (reference :188-215) ---------------------------------------------------------------------
     @property
@@ -474,6 +478,66 @@ class TransformInvariantNMF:
         return Detections(sample=as_rows(det.sample), atom=as_rows(det.atom), transform=as_rows(det.transform),
                           shift=shift, origin=shift - offset, strength=new)
 
+    def solve_detections(self, det, tol: float = 1e-8, max_iterations: int = 10000) -> Detections:
+        """The detections with the strengths that MINIMISE the objective on the fixed support ``det`` and the fixed
+        dictionary, against the model's own V: the non-negative least-squares strengths of the list, the orthogonal step of
+        orthogonal matching pursuit.  With phi_i the occurrence of row i the objective is the quadratic
+        ``1/2 ||V||^2 - c'h + 1/2 h'Gh``, ``c_i = <phi_i, V>`` and ``G_ij = <phi_i, phi_j>`` (sparse: rows couple only where
+        their footprints meet); it is minimised over ``h >= 0`` in float64 by an accelerated projected gradient method on
+        the list alone, from the strengths of ``det``.  Unlike ``refit_detections`` a strength of 0 may grow, and there is a
+        stopping rule: with ``g = Gh - c``, ``pg_i = g_i`` where ``h_i > 0`` and ``min(g_i, 0)`` where ``h_i = 0``, it stops at
+        ``kkt = max |pg| / max |c| <= tol`` or after ``max_iterations`` steps (0: the start, projected, with its kkt).  A
+        row without a pixel inside the sample gets 0.  The returned strengths are the solution rounded once to the
+        model's element type.  Read-outs: ``solve_history_`` ([checks, 2]: iteration, kkt), ``solve_n_iter_``,
+        ``solve_converged_`` -- a run that ends unconverged returns its last iterate and says so there.  The rows must be
+        distinct; the plain Frobenius objective only.  On a backend with ``solve_events`` everything runs on the device.
+        With a process group every rank solves its own samples: the call is not collective."""
+        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
+            raise NotImplementedError('solve_detections covers the plain Frobenius objective (beta_loss 2, no weights)')
+        self._check_solve_args(tol, max_iterations)
+        sample, plane, shift, strength = self._events_of(det, distinct=True)
+        hook = getattr(self._backend, 'solve_events', None)
+        if hook is not None:
+            new, info = hook(self._V, self._W_dict, sample, plane, shift, strength, float(tol), int(max_iterations))
+            new = np.asarray(self._backend.to_ndarray(new), dtype=np.float64)
+        else:
+            G, c = events_gram_numpy(self._backend.to_ndarray(self._W_dict), self._V.shape[2:], int(self._H.shape[0]),
+                                     getattr(self._backend, '_reconstruction_mode', 'valid'), sample, plane, shift,
+                                     V=self._local_V(), sparse=True)
+            new, info = events_solve_numpy(G, c, strength, float(tol), int(max_iterations))
+        self.solve_history_ = np.asarray(info['history'], dtype=np.float64).reshape(-1, 2)
+        self.solve_n_iter_ = int(info['iterations'])
+        self.solve_converged_ = bool(info['converged'])
+        mode = getattr(self._backend, '_reconstruction_mode', 'valid')
+        offset = np.array([a - 1 if mode == 'valid' else 0 for a in self.atom_shape], dtype=np.int64)
+        as_rows = lambda x: np.asarray(x).astype(np.int64).reshape(len(new))   # noqa: E731
+        return Detections(sample=as_rows(det.sample), atom=as_rows(det.atom), transform=as_rows(det.transform),
+                          shift=shift, origin=shift - offset, strength=new.astype(self._V.dtype))
+
+    @staticmethod
+    def _check_solve_args(tol, max_iterations) -> None:
+        if isinstance(tol, (bool, np.bool_)) or not isinstance(tol, numbers.Real) or not math.isfinite(tol) or not tol > 0:
+            raise ValueError(f'tol must be a finite number > 0, not {tol!r}')
+        if (isinstance(max_iterations, (bool, np.bool_)) or not isinstance(max_iterations, numbers.Integral)
+                or max_iterations < 0):
+            raise ValueError(f'max_iterations must be an int >= 0, not {max_iterations!r}')
+
+    def _list_strengths(self, who: str, strengths, n_iterations, sparsity_H, tol, max_iterations):
+        """det -> det with the strengths of a round of ``who``: ``refit_detections`` ('mu') or ``solve_detections``
+        ('solve'), after the checks of the keyword."""
+        if strengths == 'mu':
+            return lambda det: self.refit_detections(det, n_iterations, sparsity_H)
+        if strengths != 'solve':
+            raise ValueError(f"strengths must be 'mu' or 'solve', not {strengths!r}")
+        if (isinstance(sparsity_H, (bool, np.bool_)) or not isinstance(sparsity_H, numbers.Real)
+                or not math.isfinite(sparsity_H) or sparsity_H < 0):
+            raise ValueError(f'sparsity_H must be a finite number >= 0, not {sparsity_H!r}')
+        if sparsity_H != 0:
+            raise ValueError(f"{who}: strengths='solve' minimises the objective without a sparsity term: sparsity_H must "
+                             f'be 0, not {sparsity_H!r}')
+        self._check_solve_args(tol, max_iterations)
+        return lambda det: self.solve_detections(det, tol, max_iterations)
+
     def detection_gains(self, det) -> np.ndarray:
         """[K] float64: what each detection of ``det`` explains -- the objective 1/2 ||V - R||^2 of the list without the row
         minus that of the list, R being ``reconstruct_detections(det)``: ``h a + h^2 b / 2`` with phi the row's occurrence
@@ -493,7 +557,8 @@ class TransformInvariantNMF:
                                  self._local_V())
 
     def prune_detections(self, det, min_gain: float, n_iterations: int = 50, sparsity_H: float = 0.,
-                         max_rounds: int = 100) -> Tuple[Detections, np.ndarray]:
+                         max_rounds: int = 100, strengths: str = 'mu', tol: float = 1e-8,
+                         max_iterations: int = 10000) -> Tuple[Detections, np.ndarray]:
         """Backward elimination: the rows of ``det`` the data needs, refitted, and their gains.  Each round refits the
         strengths (``refit_detections`` with ``n_iterations`` and ``sparsity_H``), scores the rows (``detection_gains``) and
         takes those with a gain below ``min_gain`` as candidates.  Per sample the candidates are walked in ascending gain
@@ -502,7 +567,9 @@ class TransformInvariantNMF:
         exact, and overlapping ones are scored again in the next round, after a refit without their neighbour.  It stops
         when a round finds no candidate or after ``max_rounds`` rounds of dropping; ``max_rounds=0`` is a refit with its
         gains.  The rows are chosen on the host -- the list is small; refit, render and gains run where the backend runs
-        them.  The rows must be distinct; the plain Frobenius objective only."""
+        them.  The rows must be distinct; the plain Frobenius objective only.  With ``strengths='solve'`` the strengths of
+        every round are ``solve_detections(tol=, max_iterations=)``' -- the gains are then those of the true minimiser;
+        ``n_iterations`` is unused and ``sparsity_H`` must be 0."""
         if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
             raise NotImplementedError('prune_detections covers the plain Frobenius objective (beta_loss 2, no weights)')
         if (isinstance(min_gain, (bool, np.bool_)) or not isinstance(min_gain, numbers.Real)
@@ -512,9 +579,10 @@ class TransformInvariantNMF:
                 or max_rounds < 0):
             raise ValueError(f'max_rounds must be an int >= 0, not {max_rounds!r}')
         mode = getattr(self._backend, '_reconstruction_mode', 'valid')
+        fitted = self._list_strengths('prune_detections', strengths, n_iterations, sparsity_H, tol, max_iterations)
         rounds = 0
         while True:
-            det = self.refit_detections(det, n_iterations, sparsity_H)
+            det = fitted(det)
             gains = self.detection_gains(det)
             if rounds >= max_rounds:
                 break
@@ -537,7 +605,8 @@ class TransformInvariantNMF:
 
     def pursue_detections(self, min_gain: float, max_events: Optional[int] = None, max_rounds: int = 100,
                           refit_iterations: int = 10, n_iterations: int = 50, sparsity_H: float = 0.,
-                          start=None) -> Tuple[Detections, np.ndarray]:
+                          start=None, strengths: str = 'mu', tol: float = 1e-8,
+                          max_iterations: int = 10000) -> Tuple[Detections, np.ndarray]:
         """Forward selection: the detections the data asks for, found without a dense fit of H -- convolutional matching
         pursuit in its batched, locally greedy form -- and their gains, the pair ``prune_detections`` returns.  It works on
         the model's own V and its current dictionary; to detect in new data with a learnt dictionary call
@@ -560,7 +629,10 @@ class TransformInvariantNMF:
         ``pursue_events`` the map, its peaks and the scores are computed on the device; only the candidates (index, gain)
         and the kept rows are copied.
         The model's dense ``H`` is left as it is.  The plain Frobenius objective only.  With a process group every rank
-        pursues its own samples: the call is not collective."""
+        pursues its own samples: the call is not collective.
+        With ``strengths='solve'`` the list's strengths after every round, and at the end, are
+        ``solve_detections(tol=, max_iterations=)``' -- orthogonal matching pursuit; ``refit_iterations`` and
+        ``n_iterations`` are unused and ``sparsity_H`` must be 0."""
         if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
             raise NotImplementedError('pursue_detections covers the plain Frobenius objective (beta_loss 2, no weights)')
         if (isinstance(min_gain, (bool, np.bool_)) or not isinstance(min_gain, numbers.Real)
@@ -574,6 +646,8 @@ class TransformInvariantNMF:
         if (isinstance(sparsity_H, (bool, np.bool_)) or not isinstance(sparsity_H, numbers.Real)
                 or not math.isfinite(sparsity_H) or sparsity_H < 0):
             raise ValueError(f'sparsity_H must be a finite number >= 0, not {sparsity_H!r}')
+        fitted = self._list_strengths('pursue_detections', strengths, n_iterations, sparsity_H, tol, max_iterations)
+        solve = (float(tol), int(max_iterations)) if strengths == 'solve' else None
         k = len(self.atom_shape)
         if start is None:
             start = Detections(sample=np.zeros(0, dtype=np.int64), atom=np.zeros(0, dtype=np.int64),
@@ -583,15 +657,16 @@ class TransformInvariantNMF:
         mode = getattr(self._backend, '_reconstruction_mode', 'valid')
         max_events = None if max_events is None else int(max_events)
         hook = getattr(self._backend, 'pursue_events', None)
+        more = {} if solve is None else {'solve': solve}   # (a hook without the keyword keeps serving strengths='mu')
         if hook is not None:
             sample, plane, shift, strength, history = hook(
                 self._V, self._W_dict, sample, plane, shift, strength, float(min_gain), max_events=max_events,
-                max_rounds=int(max_rounds), refit_iterations=int(refit_iterations), eps=self.eps)
+                max_rounds=int(max_rounds), refit_iterations=int(refit_iterations), eps=self.eps, **more)
         else:
             sample, plane, shift, strength, history = pursuit_numpy(
                 self._backend.to_ndarray(self._W_dict), self._V.shape[2:], int(self._H.shape[0]), mode, sample, plane, shift,
                 strength, self._local_V(), float(min_gain), max_events=max_events, max_rounds=int(max_rounds),
-                refit_iterations=int(refit_iterations), eps=self.eps)
+                refit_iterations=int(refit_iterations), eps=self.eps, **more)
         self.pursuit_history_ = history
         sample = np.asarray(sample, dtype=np.int64)
         if self._shuffle_idx is not None:   # (the inverse of _events_of: internal sample a[i] is shown at place i)
@@ -604,7 +679,7 @@ class TransformInvariantNMF:
         T = self.n_transforms
         det = Detections(sample=sample, atom=plane // T, transform=plane % T, shift=shift, origin=shift - offset,
                          strength=np.asarray(strength))
-        det = self.refit_detections(det, n_iterations, sparsity_H)
+        det = fitted(det)
         return det, self.detection_gains(det)
 
     # -- detections moved: the landscape of the neighbouring shifts ----------------------------------------------------
@@ -660,7 +735,8 @@ class TransformInvariantNMF:
         return offset, g0.copy(), is_peak
 
     def relocate_detections(self, det, n_iterations: int = 50, sparsity_H: float = 0., max_rounds: int = 100,
-                            min_improvement: float = 0.) -> Tuple[Detections, np.ndarray]:
+                            min_improvement: float = 0., strengths: str = 'mu', tol: float = 1e-8,
+                            max_iterations: int = 10000) -> Tuple[Detections, np.ndarray]:
         """Local search over the shifts: the rows of ``det`` moved to where the data explains them better, refitted, and
         their gains -- the third list operation beside ``pursue_detections`` (grow) and ``prune_detections`` (shrink), and
         what it returns is what they return.  Each round refits the strengths (``refit_detections`` with ``n_iterations`` and
@@ -677,7 +753,9 @@ class TransformInvariantNMF:
         ``max_rounds`` rounds of hopping; ``max_rounds=0`` is a refit with its gains.  Read-out: ``relocation_history_``
         ([rounds, 3]: candidates, hops, the sum of the hops' improvements).  The hops are chosen on the host; refit, render
         and landscape run where the backend runs them.  The rows must be distinct; the plain Frobenius objective only.  With
-        a process group every rank moves the rows of its own samples: the call is not collective."""
+        a process group every rank moves the rows of its own samples: the call is not collective.  With
+        ``strengths='solve'`` the strengths of every round are ``solve_detections(tol=, max_iterations=)``';
+        ``n_iterations`` is unused and ``sparsity_H`` must be 0."""
         if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
             raise NotImplementedError('relocate_detections covers the plain Frobenius objective (beta_loss 2, no weights)')
         if (isinstance(min_improvement, (bool, np.bool_)) or not isinstance(min_improvement, numbers.Real)
@@ -688,9 +766,10 @@ class TransformInvariantNMF:
             raise ValueError(f'max_rounds must be an int >= 0, not {max_rounds!r}')
         mode = getattr(self._backend, '_reconstruction_mode', 'valid')
         offset = np.array([a - 1 if mode == 'valid' else 0 for a in self.atom_shape], dtype=np.int64)
+        fitted = self._list_strengths('relocate_detections', strengths, n_iterations, sparsity_H, tol, max_iterations)
         history, rounds = [], 0
         while True:
-            det = self.refit_detections(det, n_iterations, sparsity_H)
+            det = fitted(det)
             if rounds >= max_rounds:
                 break
             a, b, (sample, plane, shift, strength) = self._landscape(det, True, 'relocate_detections')

@@ -33,6 +33,7 @@ EXPORTS = (
     'tnmf_hip_find_peaks',
     'tnmf_hip_events_render', 'tnmf_hip_events_update', 'tnmf_hip_events_grad_W', 'tnmf_hip_events_gain',
     'tnmf_hip_events_norms', 'tnmf_hip_pursuit_score', 'tnmf_hip_pursuit_pick', 'tnmf_hip_events_landscape',
+    'tnmf_hip_events_pairs', 'tnmf_hip_events_gram', 'tnmf_hip_events_project', 'tnmf_hip_events_nnls',
 )
 
 MODES = {'valid': 0, 'full': 1, 'circular': 2, 'reflect': 3}
@@ -158,6 +159,11 @@ def load() -> ctypes.CDLL:
     lib.tnmf_hip_pursuit_score.argtypes = [vp, gp, vp, vp, vp, vp, ll, vp]
     lib.tnmf_hip_pursuit_pick.argtypes = [vp, gp, ci, vp, vp, ll, vp, vp, vp, vp, vp, vp, vp]
     lib.tnmf_hip_events_landscape.argtypes = [vp, gp, ci, vp, vp, vp, ll, vp, vp, vp, vp, vp, vp]
+    lib.tnmf_hip_events_pairs.argtypes = [vp, gp, vp, ll, vp, vp, ll, vp, sz, vp, vp]
+    lib.tnmf_hip_events_gram.argtypes = [vp, gp, ci, vp, vp, ll, vp, vp, ll, vp, vp]
+    lib.tnmf_hip_events_project.argtypes = [vp, gp, ci, vp, vp, ll, vp, vp, vp]
+    lib.tnmf_hip_events_nnls.argtypes = [vp, ll, ll, vp, vp, vp, vp, vp, cd, ci, ci, vp, pi, ctypes.POINTER(cd), pi,
+                                         ctypes.POINTER(cd), ci, pi, vp]
     lib.tnmf_hip_pad_H.argtypes = [vp, gp, ci, vp, vp, vp]
     lib.tnmf_hip_fold_H.argtypes = [vp, gp, ci, vp, vp, vp]
     for name in EXPORTS:

@@ -1008,6 +1008,108 @@ class HIP_Backend(Backend):
         a, b = self.landscape_event_list(W, events, strength, R)
         return a.cpu().numpy(), b.cpu().numpy()
 
+    # -- events: exact strengths ---------------------------------------------------------------------------------------------
+    # The objective of a list is a quadratic in its strengths (include/tnmf_hip.h, "events: exact strengths"): the samples
+    # enter once, through c = <phi, V>; the solver then works on K-vectors and the non-zeros of the Gram matrix alone.
+    def gram_event_list(self, W: torch.Tensor, images: torch.Tensor, cell_start: torch.Tensor, events: torch.Tensor,
+                        capacity: Optional[int] = None):
+        """(row_start [K + 1] int32, col [nnz] int32, val [nnz] float64) on the device: the Gram matrix G_ij = <phi_i, phi_j> of
+        the rows ``events`` (event_list) in CSR, columns ascending, the diagonal present, bit-symmetric ->
+        tnmf_hip_events_pairs (sized by a guess, ``capacity``; once more with the count when it did not fit), the pairs
+        made unique and ordered here, tnmf_hip_events_gram on i <= j, the values mirrored.  The timeline books the two
+        kernels alone ('events_pairs', 'events_gram') and the torch work on the lists under 'events_gram_lists'."""
+        self._check_W(W)
+        K = int(events.shape[0])
+        g = self._geom(self.n_local_samples, W.shape[0])
+        every = torch.arange(K, dtype=torch.int64, device=self._device)
+        count = torch.zeros(1, dtype=torch.int64, device=self._device)
+        cap = max(4096, 16 * int(images.shape[0])) if capacity is None else int(capacity)
+        for _ in range(2):   # a guess, and once more with the count when it did not fit
+            keys = torch.empty(cap, dtype=torch.int64, device=self._device)
+            with self._timed('events_pairs'):
+                _lib.check(self._lib.tnmf_hip_events_pairs(self._ctx, ctypes.byref(g), _ptr(images), images.shape[0],
+                                                           _ptr(cell_start), _ptr(events), K, _ptr(keys), cap, _ptr(count),
+                                                           self._stream()), 'tnmf_hip_events_pairs')
+            total = int(count.item())
+            if total <= cap:
+                break
+            cap = total
+        assert total <= cap, 'the same lists give the same count'
+        with self._timed('events_gram_lists'):
+            upper = torch.unique(keys[:total])            # sorted: i * K + j, i < j
+            upper = torch.cat([every * K + every, upper])  # the diagonal first, then the rows above it
+            ri = torch.div(upper, max(K, 1), rounding_mode='floor')
+            rj = upper - ri * K
+            ri32, rj32 = ri.to(torch.int32).contiguous(), rj.to(torch.int32).contiguous()
+            val = torch.empty(upper.numel(), dtype=torch.float64, device=self._device)
+        with self._timed('events_gram'):
+            _lib.check(self._lib.tnmf_hip_events_gram(self._ctx, ctypes.byref(g), self._mode, _ptr(W), _ptr(events), K,
+                                                      _ptr(ri32), _ptr(rj32), upper.numel(), _ptr(val), self._stream()),
+                       'tnmf_hip_events_gram')
+        with self._timed('events_gram_lists'):
+            # both triangles from the one value of a pair; a candidate whose value is exactly 0 is dropped
+            live = val[K:] != 0
+            ui, uj, uv = ri[K:][live], rj[K:][live], val[K:][live]
+            key = torch.cat([upper[:K], ui * K + uj, uj * K + ui])
+            key, order = torch.sort(key)
+            v = torch.cat([val[:K], uv, uv])[order].contiguous()
+            row = torch.div(key, max(K, 1), rounding_mode='floor')
+            col = (key - row * K).to(torch.int32).contiguous()
+            row_start = torch.searchsorted(row, torch.arange(K + 1, dtype=torch.int64, device=self._device)
+                                           ).to(torch.int32).contiguous()
+        if v.numel() >= 2 ** 31:
+            raise NotImplementedError('events: more than 2^31 - 1 entries in the Gram matrix')
+        return row_start, col, v
+
+    def project_event_list(self, W: torch.Tensor, events: torch.Tensor) -> torch.Tensor:
+        """c [K] float64 on the device: <phi_e, V> of every row against the resident samples -> tnmf_hip_events_project."""
+        self._check_W(W)
+        K = int(events.shape[0])
+        c = torch.empty(K, dtype=torch.float64, device=self._device)
+        with self._timed('events_project'):
+            _lib.check(self._lib.tnmf_hip_events_project(
+                self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0])), self._mode, _ptr(W), _ptr(events), K,
+                _ptr(self._V_dev), _ptr(c), self._stream()), 'tnmf_hip_events_project')
+        return c
+
+    def nnls_event_list(self, csr, c: torch.Tensor, start: torch.Tensor, tol: float, max_iterations: int,
+                        check_every: int = 10):
+        """(h [K] float64 on the device, info): min 1/2 h'Gh - c'h over h >= 0 from ``start`` projected ->
+        tnmf_hip_events_nnls; info: iterations, kkt, converged, nnz, history [checks, 2]."""
+        row_start, col, val = csr
+        K = c.numel()
+        assert row_start.dtype == torch.int32 and col.dtype == torch.int32 and val.dtype == torch.float64
+        assert c.dtype == torch.float64 and row_start.numel() == K + 1 and col.numel() == val.numel()
+        h = start.to(torch.float64).reshape(-1).clone().contiguous()
+        assert h.numel() == K
+        ws = torch.empty(7 * K + 8, dtype=torch.float64, device=self._device)
+        cap = int(max_iterations) // int(check_every) + 2
+        history = np.zeros((cap, 2), dtype=np.float64)
+        it, conv, nh, kkt = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_double(0.)
+        with self._timed('events_nnls'):
+            _lib.check(self._lib.tnmf_hip_events_nnls(
+                self._ctx, K, val.numel(), _ptr(row_start), _ptr(col), _ptr(val), _ptr(c), _ptr(h), float(tol),
+                int(max_iterations), int(check_every), _ptr(ws), ctypes.byref(it), ctypes.byref(kkt), ctypes.byref(conv),
+                history.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), cap, ctypes.byref(nh), self._stream()),
+                'tnmf_hip_events_nnls')
+        return h, dict(iterations=int(it.value), kkt=float(kkt.value), converged=bool(conv.value), nnz=int(val.numel()),
+                       history=history[:nh.value].copy())
+
+    def solve_events(self, V, W: torch.Tensor, sample, plane, shift, strength, tol: float, max_iterations: int,
+                     check_every: int = 10):
+        """(strength [K] float64 on the device, info): the strengths that minimise the plain Frobenius objective on the
+        fixed support, against the resident samples (`V` is the array given to initialize(), as for the other hooks), from
+        the given ones: the lists, the Gram matrix, the projection, the solver -- no render of the sample frame.  info:
+        iterations, kkt, converged, nnz, history [checks, 2] (iteration, kkt).  The events must be distinct.  With a process
+        group every rank solves its own samples: rows of different samples never couple, so there is no collective."""
+        if self._G_dev is not None:
+            raise NotImplementedError('solve_events is unweighted')
+        sample, plane, shift, strength = self._check_events(W.shape[0], sample, plane, shift, strength)
+        images, cell_start, events = self.event_list(sample, plane, shift)
+        csr = self.gram_event_list(W, images, cell_start, events)
+        c = self.project_event_list(W, events)
+        return self.nnls_event_list(csr, c, strength, tol, max_iterations, check_every)
+
     # -- pursuit: the list found by forward selection ---------------------------------------------------------------------
     # A round (include/tnmf_hip.h, "pursuit") is the H gradient's numerator of the residual, the gain map, its peaks and
     # the exact score of the kept ones; the rows are chosen on the host (events_host.pursuit_loop) from the
@@ -1094,12 +1196,13 @@ class HIP_Backend(Backend):
 
     def pursue_events(self, V, W: torch.Tensor, sample, plane, shift, strength, min_gain: float,
                       max_events: Optional[int] = None, max_rounds: int = 100, refit_iterations: int = 10,
-                      eps: float = 1e-9):
+                      eps: float = 1e-9, solve: Optional[Tuple[float, int]] = None):
         """(sample, plane, shift, strength, history) on the host: the list (this rank's local samples) grown from the given
         one by forward selection against the resident samples (`V` is the array given to initialize(), as for the other
         hooks) -- per round one render of the list, the residual, pursuit_round, the host's choice among the candidates,
         pick_events for the kept ones and refit_events for the list; only candidates and kept rows cross to the host.  The
-        resident samples and the model's activations are left as they are.  The plain Frobenius objective."""
+        resident samples and the model's activations are left as they are.  The plain Frobenius objective.  With
+        ``solve = (tol, max_iterations)`` the list's strengths of a round are solve_events', not refit_events'."""
         if self._G_dev is not None:
             raise NotImplementedError('pursue_events is unweighted')
         P, k = int(W.shape[0]), len(self.atom_shape)
@@ -1130,9 +1233,11 @@ class HIP_Backend(Backend):
             return h.cpu().numpy(), gain.cpu().numpy()
 
         def refit(sample, plane, shift, strength, n):
+            if solve is not None:
+                return self.solve_events(V, W, sample, plane, shift, strength, solve[0], solve[1])[0].cpu().numpy()
             return self.refit_events(V, W, sample, plane, shift, strength, n, 0., eps).cpu().numpy()
         return pursuit_loop(shape, self.atom_shape, self._sample_shape, self._reconstruction_mode, min_gain, max_events,
-                            max_rounds, refit_iterations, sample.cpu().numpy(), plane.cpu().numpy(),
+                            max_rounds, refit_iterations if solve is None else 1, sample.cpu().numpy(), plane.cpu().numpy(),
                             shift.cpu().numpy().reshape(-1, k), strength.cpu().numpy(), candidates, score, refit)
 
     # -- events: the dictionary learnt from the detections ------------------------------------------------------------------

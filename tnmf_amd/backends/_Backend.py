@@ -42,6 +42,11 @@ eps=1e-9) -> strength`` (backend-native ``[K]``); without them ``reconstruct_det
 host): what each event explains; without it ``detection_gains`` runs ``events_gain_numpy`` on the host.  And
 ``event_landscape(V, W, sample, plane, shift, strength) -> (a, b)`` (float64 ``[K, 3^k]``, host): every event at its
 neighbouring shifts (include/tnmf_hip.h, "landscape"); without it ``detection_landscape`` runs ``events_landscape_numpy``.
+And ``solve_events(V, W, sample, plane, shift, strength, tol, max_iterations, check_every=10) -> (strength, info)``
+(backend-native float64 ``[K]``; info: iterations, kkt, converged, nnz, history ``[checks, 2]``): the strengths that minimise
+the Frobenius objective on the fixed support (include/tnmf_hip.h, "events: exact strengths"); without it ``solve_detections``
+runs ``events_gram_numpy`` and ``events_solve_numpy``.  A ``pursue_events`` hook takes ``solve=(tol, max_iterations)`` when
+the front end asks for ``strengths='solve'``.
 """
 import abc
 from typing import Optional, Sequence, Tuple, Union

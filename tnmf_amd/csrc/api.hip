@@ -9,6 +9,7 @@
 
 #include "beta.h"
 #include "events.h"
+#include "solve.h"
 #include "fft.h"
 #include "generic.h"
 #include "mfma.h"
@@ -1514,6 +1515,71 @@ int tnmf_hip_events_landscape(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int 
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
     return events_landscape(ctx, g, geom->ndim, geom->dtype, mode, S[0], S[1], W_eff, events, strength, n_events, V, R,
                             a_out, b_out, mag_out, static_cast<hipStream_t>(stream));
+}
+
+int tnmf_hip_events_pairs(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const int *images, long long n_images,
+                          const int *cell_start, const int *events, long long n_events, long long *pairs_out,
+                          size_t capacity, unsigned long long *count_out, void *stream) {
+    if (!ctx || !geom) return TNMF_E_NULL;
+    EventGeo g;
+    const int rc = events_geo(geom, &g);
+    if (rc != TNMF_OK) return rc;
+    if (n_images < 0 || n_events < 0) return TNMF_E_GEOM;
+    if (n_images > 0x7fffffffLL || n_events > 0x7fffffffLL || capacity > 0x7fffffffULL) return TNMF_E_UNSUPPORTED;
+    if (!count_out || (capacity > 0 && !pairs_out)) return TNMF_E_NULL;
+    if (n_images > 0 && n_events > 0 && g.N > 0 && (!images || !cell_start || !events)) return TNMF_E_NULL;
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return events_pairs(ctx, g, images, n_images, cell_start, events, n_events, pairs_out, capacity, count_out,
+                        static_cast<hipStream_t>(stream));
+}
+
+int tnmf_hip_events_gram(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,
+                         long long n_events, const int *row_i, const int *row_j, long long n_pairs, double *val_out,
+                         void *stream) {
+    EventGeo g;
+    int S[2];
+    const int rc = events_enter(ctx, geom, mode, &g, S);
+    if (rc != TNMF_OK) return rc;
+    if (n_events < 0 || n_pairs < 0) return TNMF_E_GEOM;
+    if (n_events > 0x7fffffffLL || n_pairs > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
+    if (n_pairs > 0 && (!row_i || !row_j || !val_out || (n_events > 0 && (!W_eff || !events)))) return TNMF_E_NULL;
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return events_gram(ctx, g, geom->dtype, mode, S[0], S[1], W_eff, events, n_events, row_i, row_j, n_pairs, val_out,
+                       static_cast<hipStream_t>(stream));
+}
+
+int tnmf_hip_events_project(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,
+                            long long n_events, const void *V, double *c_out, void *stream) {
+    EventGeo g;
+    int S[2];
+    const int rc = events_enter(ctx, geom, mode, &g, S);
+    if (rc != TNMF_OK) return rc;
+    if (n_events < 0) return TNMF_E_GEOM;
+    if (n_events > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
+    if (n_events > 0 && (!events || !c_out || (g.N > 0 && (!W_eff || !V)))) return TNMF_E_NULL;
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return events_project(ctx, g, geom->dtype, mode, S[0], S[1], W_eff, events, n_events, V, c_out,
+                          static_cast<hipStream_t>(stream));
+}
+
+int tnmf_hip_events_nnls(tnmf_hip_ctx *ctx, long long n_rows, long long nnz, const int *row_start, const int *col,
+                         const double *val, const double *c, double *h_inout, double tol, int max_iterations,
+                         int check_every, double *workspace, int *iterations_out, double *kkt_out, int *converged_out,
+                         double *history_out, int history_capacity, int *n_history_out, void *stream) {
+    if (!ctx || !iterations_out || !kkt_out || !converged_out) return TNMF_E_NULL;
+    if (n_rows < 0 || nnz < 0 || max_iterations < 0 || check_every < 1 || history_capacity < 0) return TNMF_E_GEOM;
+    if (!(tol > 0) || !std::isfinite(tol) || n_rows > 0x7fffffffLL || nnz > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
+    if (history_capacity > 0 && !history_out) return TNMF_E_NULL;
+    if (n_rows > 0 && (!row_start || !c || !h_inout || !workspace || (nnz > 0 && (!col || !val)))) return TNMF_E_NULL;
+    if (n_rows == 0) {
+        *iterations_out = 0, *kkt_out = 0., *converged_out = 1;
+        if (n_history_out) *n_history_out = 0;
+        return TNMF_OK;
+    }
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return events_nnls(ctx, (int)n_rows, (int)nnz, row_start, col, val, c, h_inout, tol, max_iterations, check_every,
+                       workspace, iterations_out, kkt_out, converged_out, history_out, history_capacity, n_history_out,
+                       static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

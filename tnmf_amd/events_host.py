@@ -1,7 +1,8 @@
 """
 The events of the front end on the host: the image table of an event, the clip of an image to the sample, and the NumPy
 fallbacks for a backend without the events hooks (tnmf_amd/backends/_Backend.py) -- peaks, render and refit, gains, norms,
-forward selection, the landscape of the neighbouring shifts, the fit of the dictionary on a fixed support.
+forward selection, the landscape of the neighbouring shifts, the Gram matrix of a list and its exact strengths, the fit of the
+dictionary on a fixed support.
 ``pursuit_loop``, the rounds of the forward selection, and ``relocation_hops``, the choice of a round of relocation, work on
 lists alone and are shared by every backend, the hip backend included; nothing else here is on the hip path.
 """
@@ -217,6 +218,95 @@ def events_landscape_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], n_sampl
     return (a, b, mag) if with_magnitude else (a, b)
 
 
+def events_gram_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], n_samples: int, mode: str, sample, plane, shift,
+                      V: Optional[np.ndarray] = None, sparse: bool = False):
+    """The quadratic form of a list on the host, for backends without ``gram_event_list`` -- the semantics of
+    tnmf_hip_events_gram / tnmf_hip_events_project (include/tnmf_hip.h, "events: exact strengths"), in float64:
+    ``G_ij = <phi_i, phi_j>`` for rows of one sample (0 across samples) and, with ``V``, ``c_i = <phi_i, V>``, phi the
+    occurrence summed into a dense sample.  Dense ``G [K, K]``, or with ``sparse`` the CSR triple ``(row_start [K + 1],
+    col, val)`` of its non-zeros plus the diagonal.  Returns G (or the triple), and ``(G, c)`` with ``V``.  Not on the hip
+    path."""
+    W = np.asarray(W, dtype=np.float64)
+    A, D, S = _shapes(W, sample_shape, mode)
+    sample = np.asarray(sample, dtype=np.int64).reshape(-1)
+    K = len(sample)
+    shift = np.asarray(shift, dtype=np.int64).reshape(K, len(A))
+    Phi = np.zeros((K, int(W.shape[1] * np.prod(D))))
+    for e in range(K):
+        Phi[e] = _occurrence(W, D, S, mode, plane[e], shift[e]).reshape(-1)
+    G = np.zeros((K, K))
+    for n in np.unique(sample):
+        rows = np.flatnonzero(sample == n)
+        G[np.ix_(rows, rows)] = Phi[rows] @ Phi[rows].T
+    out = G
+    if sparse:
+        keep = (G != 0) | np.eye(K, dtype=bool)
+        i, j = np.nonzero(keep)
+        out = (np.concatenate([[0], np.cumsum(keep.sum(axis=1))]).astype(np.int64), j.astype(np.int64), G[i, j])
+    if V is None:
+        return out
+    V = np.asarray(V, dtype=np.float64).reshape(n_samples, -1)
+    return out, np.einsum('kd,kd->k', Phi, V[sample]) if K else np.zeros(0)
+
+
+def _csr_ops(G, K: int):
+    """(x -> G x, diag(G)) for a dense matrix or a CSR triple (row_start, col, val)."""
+    if isinstance(G, tuple):
+        row_start, col, val = (np.asarray(a) for a in G)
+        row = np.repeat(np.arange(K), np.diff(row_start))
+        diag = np.zeros(K)
+        np.add.at(diag, row[row == col], val[row == col])
+        return (lambda x: np.bincount(row, weights=val * x[col], minlength=K)), diag
+    G = np.asarray(G, dtype=np.float64).reshape(K, K)
+    return (lambda x: G @ x), np.diag(G).copy()
+
+
+def events_solve_numpy(G, c: np.ndarray, start: np.ndarray, tol: float, max_iterations: int, check_every: int = 10):
+    """The exact non-negative strengths of a list on the host, for backends without ``solve_events`` -- the algorithm and
+    the stopping rule of tnmf_hip_events_nnls (include/tnmf_hip.h, "events: exact strengths"): minimise
+    ``1/2 h'Gh - c'h`` over ``h >= 0`` in float64 from ``start`` projected, by projected gradient with the step ``1 / L``,
+    ``L = max_i sum_j |G_ij|``, Nesterov momentum and the gradient restart; ``kkt = max |pg| / max |c|`` (``g = Gh - c``,
+    ``pg_i = g_i`` where ``h_i > 0``, ``min(g_i, 0)`` where ``h_i = 0``, over the rows with ``G_ii > 0``) is taken at the
+    iterate, every ``check_every`` iterations and at ``max_iterations``.  G dense or a CSR triple.  Returns ``(h, info)``,
+    info a dict with ``iterations``, ``kkt``, ``converged``, ``nnz`` and ``history`` ([checks, 2]).  Not on the hip path."""
+    c = np.asarray(c, dtype=np.float64).reshape(-1)
+    K = len(c)
+    matvec, diag = _csr_ops(G, K)
+    nnz = int(len(G[1])) if isinstance(G, tuple) else int(np.count_nonzero(np.asarray(G)))
+    if not K:
+        return np.zeros(0), dict(iterations=0, kkt=0., converged=True, nnz=0, history=np.zeros((0, 2)))
+    absG = (lambda: np.bincount(np.repeat(np.arange(K), np.diff(G[0])), weights=np.abs(G[2]), minlength=K)) \
+        if isinstance(G, tuple) else (lambda: np.abs(np.asarray(G, dtype=np.float64)).sum(axis=1))
+    L = float(np.max(absG()))
+    invL = 1. / L if L > 0 else 0.
+    cmax = float(np.max(np.abs(c)))
+    act = (diag > 0) & (cmax > 0)
+    start = np.asarray(start, dtype=np.float64).reshape(-1)
+    x = np.where(act & (start > 0), start, 0.)
+    xp, beta, t = x.copy(), 0., 1.
+    history = []
+    it = 0
+    while True:
+        y = x + beta * (x - xp)
+        gx = matvec(x) - c
+        if it % check_every == 0 or it == max_iterations:
+            pg = np.where(x > 0, np.abs(gx), np.maximum(-gx, 0.))
+            kkt = float(np.max(pg[act], initial=0.)) / cmax if cmax > 0 else 0.
+            history.append((it, kkt))
+            if kkt <= tol or it == max_iterations:
+                break
+        xn = np.where(act, np.maximum(y - (matvec(y) - c) * invL, 0.), 0.)
+        if float(np.sum((y - xn) * (xn - x))) > 0:
+            t, beta = 1., 0.
+        else:
+            t_next = 0.5 * (1. + np.sqrt(1. + 4. * t * t))
+            t, beta = t_next, (t - 1.) / t_next
+        xp, x = x, xn
+        it += 1
+    return x, dict(iterations=it, kkt=kkt, converged=bool(kkt <= tol), nnz=nnz,
+                   history=np.array(history, dtype=np.float64).reshape(len(history), 2))
+
+
 def landscape_gains(a: np.ndarray, b: np.ndarray) -> np.ndarray:
     """``a^2 / (2 b)`` where ``a > 0`` and ``b > 0``, else 0: what a row at that shift, at its best strength ``a / b``, takes off
     the objective of the list without the row."""
@@ -330,12 +420,13 @@ def pursuit_loop(shape: Tuple[int, ...], atom_shape: Tuple[int, ...], sample_sha
 
 def pursuit_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], n_samples: int, mode: str, sample, plane, shift, strength,
                   V: np.ndarray, min_gain: float, max_events: Optional[int] = None, max_rounds: int = 100,
-                  refit_iterations: int = 10, eps: float = 1e-9):
+                  refit_iterations: int = 10, eps: float = 1e-9, solve: Optional[Tuple[float, int]] = None):
     """Forward selection on the host, for backends without ``pursue_events`` -- the semantics of the hip backend's hook and
     of the entry points under "pursuit" in include/tnmf_hip.h, in float64: per round the residual ``d = V - R`` of the list,
     the map ``a = <phi, d>`` as one correlation of d with every plane in the padded frame, folded onto the shifts by the
     image table, ``g = a^2 / (2 b)``, its peaks, and the exact ``a`` and ``b`` of the kept ones from the occurrence summed
-    into a dense sample.  Returns (sample, plane, shift, strength, history).  Not on the hip path."""
+    into a dense sample.  With ``solve = (tol, max_iterations)`` the list's strengths of a round are ``events_solve_numpy``'s,
+    not the multiplicative update's.  Returns (sample, plane, shift, strength, history).  Not on the hip path."""
     A, D, S = _shapes(W, sample_shape, mode)
     k = len(A)
     W64, V64 = np.asarray(W, dtype=np.float64), np.asarray(V, dtype=np.float64)
@@ -378,8 +469,11 @@ def pursuit_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], n_samples: int, 
         return h, gain
 
     def refit(sample, plane, shift, strength, n):
+        if solve is not None:
+            G, c = events_gram_numpy(W64, D, n_samples, mode, sample, plane, shift, V=V64, sparse=True)
+            return events_solve_numpy(G, c, strength, solve[0], solve[1])[0]
         return events_numpy(W, D, n_samples, mode, sample, plane, shift, strength, V=V, n_iterations=n, eps=eps)
-    return pursuit_loop(shape, A, D, mode, min_gain, max_events, max_rounds, refit_iterations,
+    return pursuit_loop(shape, A, D, mode, min_gain, max_events, max_rounds, refit_iterations if solve is None else 1,
                         np.asarray(sample, dtype=np.int64), np.asarray(plane, dtype=np.int64),
                         np.asarray(shift, dtype=np.int64).reshape(-1, k), np.asarray(strength, dtype=W.dtype), candidates,
                         score, refit)

@@ -46,7 +46,7 @@ def main():
             m = re.search(r'Function Name: (\S+)', line)
             if m:
                 kernel = subprocess.run(['c++filt', m.group(1)], capture_output=True, text=True).stdout.strip()
-                kernel = re.sub(r'^void \(anonymous namespace\)::', '', kernel).split('(')[0]
+                kernel = re.sub(r'^(void )?\(anonymous namespace\)::', '', kernel).split('(')[0]
                 rows[kernel] = {}
             m = re.search(r'remark.*:\s+(' + '|'.join(map(re.escape, FIELDS)) + r'): (\d+)', line)
             if m and kernel:
