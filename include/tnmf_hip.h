@@ -685,6 +685,44 @@ int tnmf_hip_events_landscape(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int 
                               const void *strength, long long n_events, const void *V, const void *R, double *a_out,
                               double *b_out, double *mag_out /* may be NULL */, void *stream);
 
+/* ---- alternatives: every event scored under other planes at its own shift (ABI 8, additive: the version stays 8) ------------
+ * The landscape turned by 90 degrees: what the objective would be if a row of the list had another atom or another
+ * orientation, everything else in the list held fixed -- the quantity behind re-estimating the label of a row.  For event
+ * e = (n, p, u, h_e) of a list whose render is R, d_e = V[n] - R[n] + h_e * phi_e is the residual of the list WITHOUT the row
+ * (tnmf_hip_events_landscape).  The candidates are an arithmetic progression of planes through the row's own plane, given
+ * by n_alt >= 1 and stride >= 1 with block = n_alt * stride a divisor of P:
+ *   first_e = (p / block) * block + p % stride,   p'_j = first_e + j * stride  (j = 0 .. n_alt - 1),   j_own = (p - first_e) / stride
+ * -- with plane = atom * T + transform, (n_alt, stride) = (T, 1) are the orientations of the row's atom, (M, T) every atom in
+ * the row's orientation, (P, 1) every plane.  For every j, phi' = phi_{p'_j,u}, the occurrence as tnmf_hip_events_gain defines
+ * it at the row's own shift (the image geometry is the same for every j: every plane has the atom shape), w' the taps of
+ * p'_j, t over the taps of image i whose pixel px(i, t) lies in the sample:
+ *   a_out[e, j]   = sum_i sum_t w'_t * d_e(px(i, t))
+ *   b_out[e, j]   = sum_i sum_t w'_t * phi'(px(i, t))       ( = ||phi'||^2, images that overlap added before squaring)
+ *   mag_out[e, j] = sum_i sum_t |w'_t * d_e(px(i, t))|      (the scale of the rounding error of a; may be NULL: not written)
+ * -- the sums of tnmf_hip_events_landscape at delta = 0 taken with the taps of plane p'_j.  Replacing the row by plane p'_j at
+ * its best strength a / b lowers E = 1/2 ||V - R||^2, measured from the list without e, by a^2 / (2 b) where a > 0 and b > 0
+ * (the caller's to form).  At j_own:  a - h_e * b = the a_e of tnmf_hip_events_gain, and h_e * a_e + 1/2 * h_e^2 * b = its
+ * gain[e]; the three sums there are those of tnmf_hip_events_landscape at delta = 0.
+ * events, strength: those of tnmf_hip_events_gain, read and not written; duplicates are allowed, each row puts back only
+ * itself.  Outputs: [n_events, n_alt] DOUBLES, C-contiguous, whatever the element type.  d_e(px) = fma(h_e, phi_e(px),
+ * (double)V - (double)R) and every sum are taken in double in a fixed order -- tap t of an image in lane t % 64 in ascending
+ * t, images in image order, then the butterfly of the wave -- without atomics: the same operands give the same bits run after
+ * run, on any device.  Every element of the outputs is written -- they need no initialisation -- zeros for a row whose
+ * sample, plane or shift is out of range (no sample data is read for it).  Two paths, chosen per row by its geometry alone
+ * and giving the same bits: a row whose occurrence is a single image wholly inside the sample has its C * prod(A) patch of
+ * d_e staged once in LDS (when that is <= 2048 doubles) -- V and R are read once per row, not n_alt times -- and b taken as
+ * the plane's sum of squares in the same lane order; every other row -- clipped, wrapped or mirrored -- walks its images
+ * once per batch of candidates.  It reads W_eff, events, strength, V and R and writes the outputs, nothing else.
+ * Workspace: none.  Asynchronous.  With n_events == 0 or N == 0 it does nothing.
+ * Refused before anything is written, as tnmf_hip_events_landscape is: TNMF_E_NULL (ctx, geom, and with n_events > 0 and
+ * N > 0 every operand but mag_out), TNMF_E_DTYPE, TNMF_E_UNSUPPORTED for volumes and for n_events * n_alt > 2^31 - 1,
+ * TNMF_E_GEOM for any other ndim, sizes <= 0, a negative count, an unknown mode, the per-axis limits of the mode, n_alt < 1,
+ * stride < 1 and a block n_alt * stride that does not divide P. */
+int tnmf_hip_events_alternatives(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff,
+                                 const int *events, const void *strength, long long n_events, const void *V, const void *R,
+                                 int n_alt, int stride, double *a_out, double *b_out,
+                                 double *mag_out /* may be NULL */, void *stream);
+
 /* ---- events: exact strengths (ABI 8, additive: the version stays 8) -------------------------------------------------------
  * The strengths that MINIMISE the Frobenius objective on a fixed support -- the orthogonal step of orthogonal matching
  * pursuit -- computed on the list alone.  For K distinct events with occurrences phi_e (all images, clipped to the sample,

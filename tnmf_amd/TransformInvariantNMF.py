@@ -32,10 +32,10 @@ import numpy as np
 from . import transforms as _transforms
 from .backends._Backend import Backend, sliceNone
 # (the host side of the events; the names stay importable from this module)
-from .events_host import (event_boxes, event_images, events_fit_numpy, events_gain_numpy,  # noqa: F401
-                          events_gram_numpy, events_landscape_numpy, events_norms_numpy, events_numpy,
+from .events_host import (event_boxes, event_images, events_alternatives_numpy, events_fit_numpy,  # noqa: F401
+                          events_gain_numpy, events_gram_numpy, events_landscape_numpy, events_norms_numpy, events_numpy,
                           events_solve_numpy, find_peaks_numpy, landscape_gains, pursuit_loop, pursuit_numpy,
-                          relocation_hops)
+                          relabel_hops, relocation_hops)
 
 
 class MiniBatchAlgorithm(enum.Enum):
@@ -784,6 +784,104 @@ class TransformInvariantNMF:
             det = dataclasses.replace(det, shift=shift, origin=shift - offset, strength=strength)
             rounds += 1
         self.relocation_history_ = np.array(history, dtype=np.float64).reshape(len(history), 3)
+        return det, self.detection_gains(det)
+
+    # -- detections relabelled: the alternatives under the other atoms and orientations ---------------------------------
+    _OVER = ('transforms', 'atoms', 'all')
+
+    def _alternative_set(self, over) -> Tuple[int, int]:
+        """(n_alt, stride) of the candidate planes ``over`` names, with plane = atom * T + transform."""
+        if not isinstance(over, str) or over not in self._OVER:
+            raise ValueError(f'over must be one of {self._OVER}, not {over!r}')
+        if over == 'transforms' and self._transforms is None:
+            raise ValueError("over='transforms' needs a model with transforms")
+        T = self.n_transforms
+        return {'transforms': (T, 1), 'atoms': (self.n_atoms, T), 'all': (self.n_atoms * T, 1)}[over]
+
+    def _alternatives(self, det, over, distinct: bool, who: str):
+        """(a, b) ``[K, n_alt]`` float64 of the rows of ``det``, after the refusals and checks ``who`` shares with
+        ``detection_gains``, (n_alt, stride), and the rows in the backend's terms."""
+        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
+            raise NotImplementedError(f'{who} covers the plain Frobenius objective (beta_loss 2, no weights)')
+        rows = sample, plane, shift, strength = self._events_of(det, distinct=distinct)
+        n_alt, stride = self._alternative_set(over)
+        hook = getattr(self._backend, 'event_alternatives', None)
+        if hook is not None:
+            a, b = hook(self._V, self._W_dict, sample, plane, shift, strength, n_alt, stride)
+        else:
+            a, b = events_alternatives_numpy(
+                self._backend.to_ndarray(self._W_dict), self._V.shape[2:], int(self._H.shape[0]),
+                getattr(self._backend, '_reconstruction_mode', 'valid'), sample, plane, shift, strength, self._local_V(),
+                n_alt, stride)
+        return np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64), (n_alt, stride), rows
+
+    def detection_alternatives(self, det, over: str = 'transforms') -> Tuple[np.ndarray, np.ndarray]:
+        """(a, b) float64: every row of ``det`` scored under other labels at its own shift, with everything else in the
+        list held fixed -- ``over='transforms'`` the T orientations of the row's atom (``[K, T]``), ``'atoms'`` every atom in
+        the row's orientation (``[K, M]``), ``'all'`` every atom and orientation (``[K, M, T]``).  With R =
+        ``reconstruct_detections(det)`` and ``d = V - R + h phi`` the residual of the list without the row, ``a = <phi', d>``
+        and ``b = ||phi'||^2`` for the candidate atom and orientation at the row's shift (phi': all its images, clipped to
+        the sample).  The row relabelled so, at its best strength ``a / b``, would take ``a^2 / (2 b)`` off the objective of
+        the list without the row (for ``a > 0``).  At the row's own label ``h (a - h b) + h^2 b / 2`` is its
+        ``detection_gains`` and (a, b) are the centre of ``detection_landscape``.  Duplicate rows put back only themselves.
+        On a backend with ``event_alternatives`` the list is rendered and scored on the device and only the ``2 K n_alt``
+        numbers are copied.  The plain Frobenius objective only."""
+        a, b, _, _ = self._alternatives(det, over, False, 'detection_alternatives')
+        shape = (len(a), self.n_atoms, self.n_transforms) if over == 'all' else (len(a), a.shape[1])
+        return a.reshape(shape), b.reshape(shape)
+
+    def relabel_detections(self, det, over: str = 'transforms', n_iterations: int = 50, sparsity_H: float = 0.,
+                           max_rounds: int = 100, min_improvement: float = 0., strengths: str = 'mu', tol: float = 1e-8,
+                           max_iterations: int = 10000) -> Tuple[Detections, np.ndarray]:
+        """Local search over the labels: the rows of ``det`` given the atom and orientation the data explains them better
+        with, refitted, and their gains -- the fourth list operation beside ``pursue_detections`` (grow),
+        ``prune_detections`` (shrink) and ``relocate_detections`` (move), and what it returns is what they return.  Each
+        round refits the strengths (``refit_detections`` with ``n_iterations`` and ``sparsity_H``) and takes the alternatives
+        (``detection_alternatives`` over ``over``).  For a row of strength h, with ``g = a^2 / (2 b)``, ``improvement = max
+        over the other candidates of g - (h a_e + h^2 b_own / 2)``, ``a_e = a_own - h b_own``: what the objective falls by when
+        the row takes its best other label at the strength ``a / b`` there.  The candidates are the rows with ``improvement >
+        min_improvement`` whose best other label has ``g > 0``.  Per sample they are walked in descending improvement (ties in
+        row order) and hop -- to the candidate of the lowest index among equal ones, ``shift`` and ``origin`` unchanged --
+        unless the bounding box of the occurrence meets that of a hop already made in this round (rows with disjoint
+        footprints do not interact, so their hops together are exact; the others are scored again next round), or the target
+        is already a row of the list (the list stays distinct).  It stops when a round makes no hop or after ``max_rounds``
+        rounds of hopping; ``max_rounds=0`` is a refit with its gains.  Read-out: ``relabel_history_`` ([rounds, 3]:
+        candidates, hops, the sum of the hops' improvements).  The hops are chosen on the host; refit, render and
+        alternatives run where the backend runs them.  The rows must be distinct; the plain Frobenius objective only.  With
+        a process group every rank relabels the rows of its own samples: the call is not collective.  With
+        ``strengths='solve'`` the strengths of every round are ``solve_detections(tol=, max_iterations=)``';
+        ``n_iterations`` is unused and ``sparsity_H`` must be 0."""
+        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
+            raise NotImplementedError('relabel_detections covers the plain Frobenius objective (beta_loss 2, no weights)')
+        if self._H is not None and len(self.atom_shape) != 3:
+            self._alternative_set(over)
+        if (isinstance(min_improvement, (bool, np.bool_)) or not isinstance(min_improvement, numbers.Real)
+                or not math.isfinite(min_improvement) or min_improvement < 0):
+            raise ValueError(f'min_improvement must be a finite number >= 0, not {min_improvement!r}')
+        if (isinstance(max_rounds, (bool, np.bool_)) or not isinstance(max_rounds, numbers.Integral)
+                or max_rounds < 0):
+            raise ValueError(f'max_rounds must be an int >= 0, not {max_rounds!r}')
+        mode = getattr(self._backend, '_reconstruction_mode', 'valid')
+        T = self.n_transforms
+        fitted = self._list_strengths('relabel_detections', strengths, n_iterations, sparsity_H, tol, max_iterations)
+        history, rounds = [], 0
+        while True:
+            det = fitted(det)
+            if rounds >= max_rounds:
+                break
+            a, b, (n_alt, stride), (sample, plane, shift, strength) = self._alternatives(det, over, True,
+                                                                                         'relabel_detections')
+            hopped, target, h, n_candidates, total = relabel_hops(
+                sample, plane, shift, strength, a, b, n_alt, stride, self.atom_shape, self._V.shape[2:],
+                tuple(int(x) for x in self._H.shape[2:]), mode, float(min_improvement))
+            history.append((n_candidates, len(hopped), total))
+            if not len(hopped):
+                break
+            atom, transform, strength = np.array(det.atom), np.array(det.transform), np.array(det.strength)
+            atom[hopped], transform[hopped], strength[hopped] = target // T, target % T, h.astype(strength.dtype)
+            det = dataclasses.replace(det, atom=atom, transform=transform, strength=strength)
+            rounds += 1
+        self.relabel_history_ = np.array(history, dtype=np.float64).reshape(len(history), 3)
         return det, self.detection_gains(det)
 
     def fit_detections(self, det, n_iterations: int = 50, sparsity_H: float = 0., update_H: bool = True,

@@ -33,6 +33,7 @@ EXPORTS = (
     'tnmf_hip_find_peaks',
     'tnmf_hip_events_render', 'tnmf_hip_events_update', 'tnmf_hip_events_grad_W', 'tnmf_hip_events_gain',
     'tnmf_hip_events_norms', 'tnmf_hip_pursuit_score', 'tnmf_hip_pursuit_pick', 'tnmf_hip_events_landscape',
+    'tnmf_hip_events_alternatives',
     'tnmf_hip_events_pairs', 'tnmf_hip_events_gram', 'tnmf_hip_events_project', 'tnmf_hip_events_nnls',
 )
 
@@ -159,6 +160,7 @@ def load() -> ctypes.CDLL:
     lib.tnmf_hip_pursuit_score.argtypes = [vp, gp, vp, vp, vp, vp, ll, vp]
     lib.tnmf_hip_pursuit_pick.argtypes = [vp, gp, ci, vp, vp, ll, vp, vp, vp, vp, vp, vp, vp]
     lib.tnmf_hip_events_landscape.argtypes = [vp, gp, ci, vp, vp, vp, ll, vp, vp, vp, vp, vp, vp]
+    lib.tnmf_hip_events_alternatives.argtypes = [vp, gp, ci, vp, vp, vp, ll, vp, vp, ci, ci, vp, vp, vp, vp]
     lib.tnmf_hip_events_pairs.argtypes = [vp, gp, vp, ll, vp, vp, ll, vp, sz, vp, vp]
     lib.tnmf_hip_events_gram.argtypes = [vp, gp, ci, vp, vp, ll, vp, vp, ll, vp, vp]
     lib.tnmf_hip_events_project.argtypes = [vp, gp, ci, vp, vp, ll, vp, vp, vp]

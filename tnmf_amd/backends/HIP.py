@@ -1008,6 +1008,40 @@ class HIP_Backend(Backend):
         a, b = self.landscape_event_list(W, events, strength, R)
         return a.cpu().numpy(), b.cpu().numpy()
 
+    def alternatives_event_list(self, W: torch.Tensor, events: torch.Tensor, strength: torch.Tensor, R: torch.Tensor,
+                                n_alt: int, stride: int, with_magnitude: bool = False):
+        """(a, b) [K, n_alt] float64 on the device: every event under the planes ``first + j * stride`` of its block of
+        ``n_alt * stride`` planes, at its own shift, against the residual of the list without it, R being the render of the
+        strengths -> tnmf_hip_events_alternatives; with ``with_magnitude`` (a, b, mag), mag the sum of the magnitudes of the
+        terms of a."""
+        self._check_W(W)
+        assert strength.is_contiguous() and strength.dtype == self._torch_dtype and events.shape[0] == strength.numel()
+        assert R.is_contiguous() and R.dtype == self._torch_dtype and tuple(R.shape) == tuple(self._V_dev.shape)
+        K, n_alt, stride = strength.numel(), int(n_alt), int(stride)
+        shape = (K, max(n_alt, 0))
+        a = torch.empty(shape, dtype=torch.float64, device=self._device)
+        b = torch.empty(shape, dtype=torch.float64, device=self._device)
+        mag = torch.empty(shape, dtype=torch.float64, device=self._device) if with_magnitude else None
+        with self._timed('events_alternatives'):
+            _lib.check(self._lib.tnmf_hip_events_alternatives(
+                self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0])), self._mode, _ptr(W), _ptr(events),
+                _ptr(strength), K, _ptr(self._V_dev), _ptr(R), n_alt, stride, _ptr(a), _ptr(b), _ptr(mag),
+                self._stream()), 'tnmf_hip_events_alternatives')
+        return (a, b, mag) if with_magnitude else (a, b)
+
+    def event_alternatives(self, V, W: torch.Tensor, sample, plane, shift, strength, n_alt: int, stride: int):
+        """(a, b) [K, n_alt] float64 on the host: per event and candidate plane the correlation of that plane's occurrence
+        at the event's shift with the residual of the list without the event, and its norm, against the resident samples
+        (`V` is the array given to initialize(), as for the other hooks): one render of the list and one kernel; only the
+        2 * K * n_alt doubles are copied.  Duplicate events put back only themselves."""
+        if self._G_dev is not None:
+            raise NotImplementedError('event_alternatives is unweighted')
+        sample, plane, shift, strength = self._check_events(W.shape[0], sample, plane, shift, strength)
+        images, cell_start, events = self.event_list(sample, plane, shift)
+        R = self.render_event_list(W, images, cell_start, strength)
+        a, b = self.alternatives_event_list(W, events, strength, R, n_alt, stride)
+        return a.cpu().numpy(), b.cpu().numpy()
+
     # -- events: exact strengths ---------------------------------------------------------------------------------------------
     # The objective of a list is a quadratic in its strengths (include/tnmf_hip.h, "events: exact strengths"): the samples
     # enter once, through c = <phi, V>; the solver then works on K-vectors and the non-zeros of the Gram matrix alone.

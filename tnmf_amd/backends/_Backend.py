@@ -42,6 +42,9 @@ eps=1e-9) -> strength`` (backend-native ``[K]``); without them ``reconstruct_det
 host): what each event explains; without it ``detection_gains`` runs ``events_gain_numpy`` on the host.  And
 ``event_landscape(V, W, sample, plane, shift, strength) -> (a, b)`` (float64 ``[K, 3^k]``, host): every event at its
 neighbouring shifts (include/tnmf_hip.h, "landscape"); without it ``detection_landscape`` runs ``events_landscape_numpy``.
+And ``event_alternatives(V, W, sample, plane, shift, strength, n_alt, stride) -> (a, b)`` (float64 ``[K, n_alt]``, host): every
+event under the other planes of its block at its own shift (include/tnmf_hip.h, "alternatives"); without it
+``detection_alternatives`` runs ``events_alternatives_numpy``.
 And ``solve_events(V, W, sample, plane, shift, strength, tol, max_iterations, check_every=10) -> (strength, info)``
 (backend-native float64 ``[K]``; info: iterations, kkt, converged, nnz, history ``[checks, 2]``): the strengths that minimise
 the Frobenius objective on the fixed support (include/tnmf_hip.h, "events: exact strengths"); without it ``solve_detections``

@@ -1517,6 +1517,22 @@ int tnmf_hip_events_landscape(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int 
                             a_out, b_out, mag_out, static_cast<hipStream_t>(stream));
 }
 
+int tnmf_hip_events_alternatives(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff,
+                                 const int *events, const void *strength, long long n_events, const void *V, const void *R,
+                                 int n_alt, int stride, double *a_out, double *b_out, double *mag_out, void *stream) {
+    EventGeo g;
+    int S[2];
+    const int rc = events_enter(ctx, geom, mode, &g, S);
+    if (rc != TNMF_OK) return rc;
+    if (n_events < 0 || n_alt < 1 || stride < 1) return TNMF_E_GEOM;
+    if ((long long)n_alt * stride > g.P || g.P % (n_alt * stride) != 0) return TNMF_E_GEOM;
+    if (n_events > 0x7fffffffLL / n_alt) return TNMF_E_UNSUPPORTED;
+    if (n_events > 0 && g.N > 0 && (!W_eff || !events || !strength || !V || !R || !a_out || !b_out)) return TNMF_E_NULL;
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return events_alternatives(ctx, g, geom->dtype, mode, S[0], S[1], W_eff, events, strength, n_events, V, R, n_alt,
+                               stride, a_out, b_out, mag_out, static_cast<hipStream_t>(stream));
+}
+
 int tnmf_hip_events_pairs(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const int *images, long long n_images,
                           const int *cell_start, const int *events, long long n_events, long long *pairs_out,
                           size_t capacity, unsigned long long *count_out, void *stream) {

@@ -73,3 +73,12 @@ int pursuit_pick(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int 
 int events_landscape(tnmf_hip_ctx *ctx, const EventGeo &g, int ndim, int dtype, int mode, int Sy, int Sx, const void *W,
                      const int *events, const void *strength, long long n_events, const void *V, const void *R, double *a,
                      double *b, double *mag, hipStream_t s);
+
+// Alternatives (alternatives.hip; tnmf_hip_events_alternatives).
+// a, b, mag[n_events, n_alt] (DOUBLES; mag may be NULL): per row and candidate plane p'_j = first + j * stride at the row's own
+// shift, first = (p / (n_alt * stride)) * (n_alt * stride) + p % stride (n_alt * stride divides P), the sums of the landscape
+// at delta = 0 with the taps of p'_j against the residual of the list without the row; zeros for a row out of range.  Every
+// element is written.
+int events_alternatives(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const void *W,
+                        const int *events, const void *strength, long long n_events, const void *V, const void *R, int n_alt,
+                        int stride, double *a, double *b, double *mag, hipStream_t s);

@@ -27,62 +27,6 @@ constexpr int kPatchMax = 2048;   // doubles of LDS per wave the staged path may
 #define TNMF_LANDSCAPE_BLOCKS_PER_CU 4   // the grid: at most this many workgroups per CU, each wave looping over its rows
 #endif
 
-// d_e at a pixel: the residual with the row's own contribution h * phi put back (phi = 0 off the row's occurrence)
-template <typename T>
-__device__ __forceinline__ double residual_without(T v, T r, double h, double phi) {
-    return fma(h, phi, (double)v - (double)r);
-}
-
-// The sums over the 64 lanes of N values at once, each bit for bit the wave_sum of its value: the same butterfly (offsets
-// 32 .. 1; a + b commutes, so every lane of wave_sum holds the same bits and which lane adds is free), but at every step a lane
-// keeps half of the values it holds and hands the other half to its partner -- a step moves ceil(n / 2) values, not n, and
-// they are independent of each other.  A value without a partner value is added the plain way, in both lanes.
-template <int N, int OFF>
-__device__ __forceinline__ void wave_sum_step(double *v, int lane) {
-    constexpr int H = (N + 1) / 2;
-    const bool upper = (lane & OFF) != 0;
-#pragma unroll
-    for (int i = 0; i < N - H; ++i) {   // the pair (i, i + H): the lower lane keeps i, the upper one i + H
-        const double send = upper ? v[i] : v[i + H], keep = upper ? v[i + H] : v[i];
-        v[i] = keep + __shfl_xor(send, OFF, 64);
-    }
-    if (N & 1) v[H - 1] += __shfl_xor(v[H - 1], OFF, 64);
-    if constexpr (OFF > 1) wave_sum_step<H, OFF / 2>(v, lane);
-}
-
-// -> v[0] = the sum of the value *which; true in exactly one lane per value, the one that reports it.  Which value a lane
-// ends with is read backwards off its bits: the slot s after a step came from s + H in an upper lane, from s in a lower one,
-// and a slot without a partner is reported by the lower lane.
-template <int N>
-__device__ __forceinline__ bool wave_sum_many(double (&v)[N], int lane, int *which) {
-    wave_sum_step<N, 32>(v, lane);
-    int n[6] = {N, 0, 0, 0, 0, 0};   // the values a lane holds before the steps of offsets 32, 16, 8, 4, 2, 1
-#pragma unroll
-    for (int k = 1; k < 6; ++k) n[k] = (n[k - 1] + 1) / 2;
-    int s = 0;
-    bool own = true;
-#pragma unroll
-    for (int k = 5; k >= 0; --k) {
-        const int H = (n[k] + 1) / 2;
-        const bool upper = (lane & (32 >> k)) != 0;
-        if (s < n[k] - H)
-            s += upper ? H : 0;
-        else
-            own = own && !upper;
-    }
-    *which = s;
-    return own;
-}
-
-// the shift u on one axis is in range and its occurrence is one image wholly inside the sample
-__device__ __forceinline__ bool axis_whole(int mode, int u, int a, int S, int D) {
-    if ((unsigned)u >= (unsigned)S) return false;
-    int q[2];
-    if (axis_images(mode, u, a, S, q) != 1) return false;
-    const int o = q[0] - (a - 1);
-    return o >= 0 && o + a <= D;
-}
-
 // the rule of the staged path: geometry only.  ry = 1 with two shift axes, 0 with one (no neighbours on the leading axis).
 __device__ __forceinline__ bool landscape_staged(const EventGeo &g, int mode, int Sy, int Sx, int ry, int uy, int ux,
                                                  int patch) {

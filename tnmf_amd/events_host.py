@@ -1,10 +1,11 @@
 """
 The events of the front end on the host: the image table of an event, the clip of an image to the sample, and the NumPy
 fallbacks for a backend without the events hooks (tnmf_amd/backends/_Backend.py) -- peaks, render and refit, gains, norms,
-forward selection, the landscape of the neighbouring shifts, the Gram matrix of a list and its exact strengths, the fit of the
-dictionary on a fixed support.
-``pursuit_loop``, the rounds of the forward selection, and ``relocation_hops``, the choice of a round of relocation, work on
-lists alone and are shared by every backend, the hip backend included; nothing else here is on the hip path.
+forward selection, the landscape of the neighbouring shifts, the alternatives under other planes, the Gram matrix of a list
+and its exact strengths, the fit of the dictionary on a fixed support.
+``pursuit_loop``, the rounds of the forward selection, ``relocation_hops``, the choice of a round of relocation, and
+``relabel_hops``, the choice of a round of relabelling, work on lists alone and are shared by every backend, the hip backend
+included; nothing else here is on the hip path.
 """
 import itertools
 from typing import Callable, Optional, Tuple
@@ -218,6 +219,47 @@ def events_landscape_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], n_sampl
     return (a, b, mag) if with_magnitude else (a, b)
 
 
+def alternative_planes(plane, n_alt: int, stride: int):
+    """(planes [K, n_alt], j_own [K]): the candidate planes ``first + j * stride`` of every row of plane ``plane`` --
+    ``first = (p // block) * block + p % stride``, ``block = n_alt * stride`` -- and the column of the row's own plane
+    (include/tnmf_hip.h, "alternatives")."""
+    plane = np.asarray(plane, dtype=np.int64).reshape(-1)
+    block = int(n_alt) * int(stride)
+    first = plane // block * block + plane % stride
+    return first[:, None] + np.arange(int(n_alt), dtype=np.int64)[None, :] * int(stride), (plane - first) // int(stride)
+
+
+def events_alternatives_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], n_samples: int, mode: str, sample, plane, shift,
+                              strength, V: np.ndarray, n_alt: int, stride: int, with_magnitude: bool = False):
+    """(a, b) ``[K, n_alt]`` float64 (with ``with_magnitude`` also mag): every event under the candidate planes of its block
+    (``alternative_planes``) at its own shift, on the host, for backends without ``event_alternatives`` -- the semantics of
+    tnmf_hip_events_alternatives (include/tnmf_hip.h, "alternatives"): with ``d_e = V - R + h_e phi_e`` the residual of the list
+    without row e, per candidate ``a = <phi', d_e>``, ``b = ||phi'||^2`` and ``mag = sum |w' d_e|`` over the taps of the images of
+    phi', the occurrence of the candidate plane at the row's shift summed into a dense sample.  Duplicate rows put back only
+    themselves.  Not on the hip path."""
+    A, D, S = _shapes(W, sample_shape, mode)
+    k = len(A)
+    n_alt, stride = int(n_alt), int(stride)
+    if n_alt < 1 or stride < 1 or W.shape[0] % (n_alt * stride):
+        raise ValueError(f'alternatives: n_alt * stride = {n_alt} * {stride} must be >= 1 each and divide the {W.shape[0]} planes')
+    W, V = np.asarray(W, dtype=np.float64), np.asarray(V, dtype=np.float64)
+    h = np.array(strength, dtype=np.float64).reshape(-1)
+    K = len(h)
+    shift = np.asarray(shift, dtype=np.int64).reshape(K, k)
+    residual = V - events_numpy(W, D, n_samples, mode, sample, plane, shift, h)
+    absW = np.abs(W)
+    planes, _ = alternative_planes(plane, n_alt, stride)
+    a, b, mag = np.zeros((K, n_alt)), np.zeros((K, n_alt)), np.zeros((K, n_alt))
+    for e in range(K):
+        d = residual[int(sample[e])] + h[e] * _occurrence(W, D, S, mode, plane[e], shift[e])
+        for j, p in enumerate(planes[e]):
+            phi = _occurrence(W, D, S, mode, p, shift[e])
+            a[e, j], b[e, j] = np.sum(phi * d), np.sum(phi * phi)
+            if with_magnitude:   # (the taps of all images on a pixel share its d: their magnitudes add up)
+                mag[e, j] = np.sum(_occurrence(absW, D, S, mode, p, shift[e]) * np.abs(d))
+    return (a, b, mag) if with_magnitude else (a, b)
+
+
 def events_gram_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], n_samples: int, mode: str, sample, plane, shift,
                       V: Optional[np.ndarray] = None, sparse: bool = False):
     """The quadratic form of a list on the host, for backends without ``gram_event_list`` -- the semantics of
@@ -359,6 +401,59 @@ def relocation_hops(sample, plane, shift, strength, a, b, atom_shape: Tuple[int,
         if mine and np.any(np.all(np.maximum(lo[e], lo[mine]) < np.minimum(hi[e], hi[mine]), axis=1)):
             continue
         to = (int(sample[e]), int(plane[e])) + tuple(int(x) for x in target[e])
+        if to in rows:
+            continue
+        rows.add(to)
+        mine.append(e)
+        hopped.append(e)
+    hopped = np.sort(np.asarray(hopped, dtype=np.int64))
+    return (hopped, target[hopped], a[hopped, best[hopped]] / b[hopped, best[hopped]], len(candidates),
+            float(np.sum(improvement[hopped])))
+
+
+def relabel_hops(sample, plane, shift, strength, a, b, n_alt: int, stride: int, atom_shape: Tuple[int, ...],
+                 sample_shape: Tuple[int, ...], shift_shape: Tuple[int, ...], mode: str, min_improvement: float):
+    """The choice of one round of ``TransformInvariantNMF.relabel_detections`` on the host, shared by every backend: from
+    the alternatives ``(a, b) [K, n_alt]`` of the distinct rows (sample, plane, shift, strength) -> (rows [J] ascending, their
+    new planes [J], their new strengths ``a / b`` [J] float64, the number of candidates, the sum of the hops' improvements).
+    With ``j_own`` the column of the row's own plane (``alternative_planes``), ``improvement = max over j != j_own of g -
+    (h a_e + h^2 b_own / 2)``, g = ``landscape_gains`` and ``a_e = a_own - h b_own``: what the objective falls by when the row
+    takes the other plane.  Candidates have ``improvement > min_improvement`` and ``g > 0`` at their best j (the lowest j on
+    ties); per sample they are walked in descending improvement, ties in row order, unless the bounding box of the row's
+    occurrence -- the same for every plane -- meets that of a hop already made in this round, or the target is a row of the
+    list."""
+    k = len(atom_shape)
+    K = len(sample)
+    n_alt, stride = int(n_alt), int(stride)
+    shift = np.asarray(shift, dtype=np.int64).reshape(K, k)
+    h = np.asarray(strength, dtype=np.float64).reshape(-1)
+    a, b = np.asarray(a, dtype=np.float64).reshape(K, n_alt), np.asarray(b, dtype=np.float64).reshape(K, n_alt)
+    empty = (np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(0), 0, 0.)
+    if not K or n_alt < 2:
+        return empty
+    planes, own_j = alternative_planes(plane, n_alt, stride)
+    every = np.arange(K)
+    g = landscape_gains(a, b)
+    own = h * (a[every, own_j] - h * b[every, own_j]) + 0.5 * h * h * b[every, own_j]
+    g[every, own_j] = -np.inf
+    best = np.argmax(g, axis=1)           # (the first of equal maxima: the lowest j)
+    there = g[every, best]
+    improvement = there - own
+    # a hop needs somewhere to go: g > 0 at the best plane, i.e. a > 0 and b > 0 there, so the strength a / b is finite and
+    # positive.  A row the data supports under no plane (every g = 0) keeps its label, whatever its own gain: removing it is
+    # prune_detections' business.
+    candidates = np.flatnonzero((improvement > min_improvement) & (there > 0))
+    if not len(candidates):
+        return empty
+    target = planes[every, best]
+    lo, hi = event_boxes(shift, atom_shape, sample_shape, shift_shape, mode)
+    rows = set(map(tuple, np.column_stack([sample, plane, shift]).tolist()))
+    hopped, boxes = [], {}   # boxes: per sample the hops made in this round
+    for e in candidates[np.argsort(-improvement[candidates], kind='stable')]:
+        mine = boxes.setdefault(int(sample[e]), [])
+        if mine and np.any(np.all(np.maximum(lo[e], lo[mine]) < np.minimum(hi[e], hi[mine]), axis=1)):
+            continue
+        to = (int(sample[e]), int(target[e])) + tuple(int(x) for x in shift[e])
         if to in rows:
             continue
         rows.add(to)
