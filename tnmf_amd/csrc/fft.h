@@ -78,6 +78,49 @@ constexpr int mix_w3_waves(int Ay) {
 }
 bool mixed_grad_W3_takes(const Geo &g, int KXP);
 
+// k_mix_reconstruct_sh, the one-channel 2-D mixed reconstruct of large calls: a workgroup of 16 kx x kMixRShStrips strips
+// of 16 output rows brings every row-spectrum entry it needs from global memory ONCE, with 16-byte loads, into an LDS
+// tile (the atom's rows of W spectra behind it) and its threads take their 16 + Ay - 1 rows from there; taken from
+// kMixRShMinBytes of row spectra of H on (mixed_reconstruct_sh_takes(), fft_mixed.hip).  A CU holds kMixRShPerCU
+// workgroups (the launch tops their LDS up so that no further one fits): with 256 threads each that many waves per SIMD,
+// which is also the floor __launch_bounds__ asks for (mix_rsh_waves(); hipcc's kernel-resource-usage remarks, ROCm 7.2:
+// 122 VGPRs, no scratch, 37 856 bytes of LDS at Ay = 12 -- read them again when the kernel or the compiler changes).
+// The defaults are what measured fastest at config 3 (profiles/mix_reconstruct_sh_ab.md); the macros are
+// A/B flavours of the library (Makefile: VARIANT):
+//   TNMF_MIX_RSH_STRIPS  8 | 16   strips per workgroup (128 | 256 output rows)
+//   TNMF_MIX_RSH_TILES   1 | 2    LDS tiles: 1 = a barrier before and one after the write of the next atom's tile,
+//                                 2 = it goes to the other tile, one barrier per atom
+//   TNMF_MIX_RSH_PER_CU           workgroups per CU
+//   TNMF_MIX_RSH_FENCE   0 .. 16  the LDS reads of the first 16 + FENCE rows of an atom step are issued before any
+//                                 multiply-add (0: left to the compiler)
+//   TNMF_MIX_RSH_AUX     0 | 2    cache policy of the loads of T (2: non-temporal, every entry is used once)
+#ifndef TNMF_MIX_RSH_STRIPS
+#define TNMF_MIX_RSH_STRIPS 16
+#endif
+#ifndef TNMF_MIX_RSH_TILES
+#define TNMF_MIX_RSH_TILES 1
+#endif
+#ifndef TNMF_MIX_RSH_PER_CU
+#define TNMF_MIX_RSH_PER_CU 3
+#endif
+#ifndef TNMF_MIX_RSH_FENCE
+#define TNMF_MIX_RSH_FENCE 0
+#endif
+#ifndef TNMF_MIX_RSH_AUX
+#define TNMF_MIX_RSH_AUX 2
+#endif
+constexpr int kMixRShStrips = TNMF_MIX_RSH_STRIPS, kMixRShTiles = TNMF_MIX_RSH_TILES, kMixRShPerCU = TNMF_MIX_RSH_PER_CU;
+constexpr int kMixRShFence = TNMF_MIX_RSH_FENCE, kMixRShAux = TNMF_MIX_RSH_AUX;
+constexpr int kMixRShWaves = kMixRShPerCU * kMixRShStrips / 16, kMixRShMaxAy = 12;
+constexpr long kMixRShMinBytes = 24L << 20;
+// LDS of a workgroup: kMixRShTiles tiles of 16 * kMixRShStrips + Ay - 1 rows of T at a pitch of 17 entries (rounded up to
+// 16 bytes), each followed by the atom's Ay rows of W spectra
+constexpr unsigned mix_rsh_lds_bytes(int Ay) {
+    return kMixRShTiles * (((16 * kMixRShStrips + Ay - 1) * 17 + 1) / 2 * 2 + Ay * 16) * 8u;
+}
+constexpr int mix_rsh_waves(int Ay) { return kMixRShWaves; }
+bool mixed_reconstruct_sh_takes(const Geo &g, int KXP);
+
 // streaming contractions on resident full spectra of H (fft_spectral.hip): no transform inside
 int spectral_contract_R(const Geo &g, int dtype, const void *SH, const void *SW, void *SR, int Ly, int KX, int KXP,
                         hipStream_t s);

@@ -190,6 +190,118 @@ __global__ __launch_bounds__(kMixCols *STRIPS, 2) void k_mix_reconstruct(const c
     }
 }
 
+// Kernels that read their operands from LDS one ds_read_b64 at a time are compiled (device pass) without hipcc's pairing
+// of DS accesses: a ds_read2_b64 / ds_read2st64_b64 moves half the bytes per LDS clock.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TNMF_MIX_NO_DS_PAIRING __attribute__((target("no-load-store-opt")))
+#else
+#define TNMF_MIX_NO_DS_PAIRING
+#endif
+
+// Large one-channel 2-D calls (mixed_reconstruct_sh_takes): the arithmetic of k_mix_reconstruct<T, AY, 1, 16, 8>, the same
+// packed multiply-adds on the same values in the same order per output -- bit-identical results -- with the row spectra
+// staged through LDS.  There a thread loads the S + AY - 1 rows its strip depends on itself, and since neighbouring strips
+// overlap by AY - 1 rows every entry of T is asked for (S + AY - 1) / S = 1.69 times (AY = 12) by 8-byte loads.  Here the
+// workgroup -- 16 kx x STRIPS strips -- loads the S * STRIPS + AY - 1 rows of its tile ONCE per atom, 16 bytes per lane
+// (eight lanes per 128-byte row segment), together with the AY rows of W spectra of that atom, one atom ahead: the loads of
+// atom m + 1 are in flight, in registers, under the multiply-adds of atom m, and are written to LDS behind them.  With
+// TILES = 2 they go to the other tile (its readers passed the barrier of the previous atom step): one barrier per atom;
+// with TILES = 1 a barrier before and one after the write.  A thread then takes its rows with S + AY - 1 ds_read_b64 and
+// the atom rows with AY broadcast ds_read_b64.  The tile's row pitch is 17 entries (136 bytes): the two strips of a
+// 32-lane half are 16 tile rows apart, 16 * 136 bytes = 8 * 256 + 128, so they fall into different halves of the 256-byte
+// bank row (a pitch of 128 bytes puts them on the same banks: a two-way conflict on every read).
+// Addresses: a wave-uniform buffer descriptor per plane of T (and per atom of W spectra) and ONE constant per-lane byte
+// offset per piece, row index clamped to the plane: rows past the plane are needed only by outputs that are never
+// stored, so nothing beyond a plane is read (the slack rows behind T are not touched by this kernel); the padding
+// columns KX .. KXP - 1 of a row segment are loaded like any other (KXP is whole segments), a thread reads column
+// min(kx, KX - 1).  The loads of T carry the non-temporal hint (kMixRShAux): an entry is used once per launch, and keeping
+// it out of the way of the W spectra in L2 measured 3 % of the kernel.  grid (kx tiles, row blocks of S * STRIPS, samples)
+template <typename T, int AY, int STRIPS, int TILES>
+__global__ __launch_bounds__(kMixCols *STRIPS, kMixRShWaves) TNMF_MIX_NO_DS_PAIRING void k_mix_reconstruct_sh(
+    const cplx<T> *Tsp, const cplx<T> *WT, cplx<T> *OT, int M, int Hy, int Dy, int KX, int KXP) {
+    constexpr int S = 16, NT = kMixCols * STRIPS, ROWS = S * STRIPS + AY - 1, PITCH = kMixCols + 1;
+    constexpr int SEG = kMixCols / 2;                                    // 16-byte pieces per row segment
+    constexpr int PIECES = ROWS * SEG, NPP = (PIECES + NT - 1) / NT, WPIECES = AY * SEG;
+    constexpr int TROWS = (ROWS * PITCH + 1) / 2 * 2, TILE = TROWS + AY * kMixCols;   // entries: rows of T, rows of W
+    static_assert(sizeof(cplx<T>) == 8 && WPIECES <= NT && (TILES == 1 || TILES == 2), "float spectra, one W piece per thread");
+    static_assert(STRIPS != kMixRShStrips || TILES != kMixRShTiles || TILES * TILE * 8 == mix_rsh_lds_bytes(AY), "fft.h");
+    typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
+    typedef float f4v __attribute__((ext_vector_type(4)));
+    __shared__ __align__(16) cplx<T> tile[TILES][TILE];
+    const int col = threadIdx.x & (kMixCols - 1), strip = threadIdx.x / kMixCols;
+    const int kx = blockIdx.x * kMixCols + col, colc = min(kx, KX - 1) - blockIdx.x * kMixCols;
+    const int yb = blockIdx.y * (S * STRIPS), y0 = yb + strip * S, n = blockIdx.z;
+    cplx<T> acc[S];
+#pragma unroll
+    for (int y = 0; y < S; ++y) acc[y] = {0, 0};
+    const long tplane = (long)Hy * KXP, wplane = (long)AY * KXP;
+    // loader: piece p = (tile row p / 8, kx pair p % 8); the host checks that a plane's bytes fit 31 bits.  Pieces past
+    // the tile (and past the atom's rows) repeat the last row's: the same bytes to the same place, so that neither a load
+    // nor a write sits in a branch (hipcc sinks a load into the branch of its only use and waits for it there)
+    auto trow = [](int k) { return min((int)(threadIdx.x + k * NT) / SEG, ROWS - 1); };
+    const int pcol = (blockIdx.x * kMixCols + 2 * (threadIdx.x & (SEG - 1))) * 8;
+    int toff[NPP];
+#pragma unroll
+    for (int k = 0; k < NPP; ++k) toff[k] = min(yb + trow(k), Hy - 1) * (KXP * 8) + pcol;
+    const int wrow = min((int)threadIdx.x / SEG, AY - 1), woff = wrow * (KXP * 8) + pcol;
+    f4v pre[NPP], wpre;
+    auto fetch = [&](int m) {   // unconditional loads on clamped addresses
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+            (void *)(Tsp + ((long)n * M + m) * tplane), 0, (int)(tplane * 8), 0x00020000);
+        const __amdgpu_buffer_rsrc_t ws =
+            __builtin_amdgcn_make_buffer_rsrc((void *)(WT + m * wplane), 0, (int)(wplane * 8), 0x00020000);
+#pragma unroll
+        for (int k = 0; k < NPP; ++k)
+            pre[k] = __builtin_bit_cast(f4v, (u32x4v)__builtin_amdgcn_raw_buffer_load_b128(rs, toff[k], 0, kMixRShAux));
+        wpre = __builtin_bit_cast(f4v, (u32x4v)__builtin_amdgcn_raw_buffer_load_b128(ws, woff, 0, 0));
+    };
+    auto park = [&](int buf) {
+        cplx<T> *tl = tile[buf];
+#pragma unroll
+        for (int k = 0; k < NPP; ++k) {
+            const int e = trow(k) * PITCH + 2 * (threadIdx.x & (SEG - 1));   // (8-byte aligned: the pitch is odd)
+            tl[e] = cplx<T>{pre[k][0], pre[k][1]};
+            tl[e + 1] = cplx<T>{pre[k][2], pre[k][3]};
+        }
+        *reinterpret_cast<f4v *>(&tl[TROWS + wrow * kMixCols + 2 * (threadIdx.x & (SEG - 1))]) = wpre;
+    };
+    fetch(0);
+    park(0);
+    __syncthreads();
+    const int mine = strip * S * PITCH + colc;
+#pragma unroll 1
+    for (int m = 0; m < M; ++m) {
+        const int buf = TILES == 2 ? (m & 1) : 0;
+        fetch(min(m + 1, M - 1));
+        const cplx<T> *tl = &tile[buf][mine], *wl = &tile[buf][TROWS + colc];
+        cplx<T> w[AY], t[S + AY - 1];
+        // LDS reads in the order the multiply-adds want them.  kMixRShFence > 0 (an A/B flavour): nothing is scheduled
+        // across a fence behind the first 16 + kMixRShFence rows, so those reads are issued before any multiply-add --
+        // it pays only where registers are plentiful (two waves per SIMD); by default hipcc places each read itself
+#pragma unroll
+        for (int r = 0; r < S; ++r) t[r] = tl[r * PITCH];
+        w[0] = wl[(AY - 1) * kMixCols];
+#pragma unroll
+        for (int a = 1; a < AY; ++a) {
+            t[S - 1 + a] = tl[(S - 1 + a) * PITCH];
+            w[a] = wl[(AY - 1 - a) * kMixCols];
+            if (a == kMixRShFence) __builtin_amdgcn_sched_barrier(0);
+        }
+        if (kMixRShFence >= AY) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int a = 0; a < AY; ++a)
+#pragma unroll
+            for (int y = 0; y < S; ++y) cfma(acc[y], t[y + a], w[a]);
+        if (TILES == 1) __syncthreads();   // the tile's readers are done
+        park(TILES == 2 ? buf ^ 1 : 0);    // (the last step parks the last atom again: never read)
+        __syncthreads();
+    }
+    if (kx >= KX) return;
+#pragma unroll
+    for (int y = 0; y < S; ++y)
+        if (y0 + y < Dy) OT[(long)n * ((long)Dy * KXP) + (long)(y0 + y) * KXP + kx] = acc[y];
+}
+
 // 1-D signals (one row per plane): OT[n,c,kx] = sum_m T[n,m,kx] * WT[m,c,kx] -- a thread per (sample, kx), all channels
 // of the sample in registers, the atom loop unrolled by four so that four loads of T are in flight.
 template <typename T, int CG, int SAMPLES>
@@ -235,6 +347,22 @@ int launch_mix_reconstruct(const void *Tsp, const void *WT, void *OT, const Geo 
             hipLaunchKernelGGL((k_mix_reconstruct_1d<T, 3, SAMPLES>), dim3(tiles, (unsigned)cdiv(g.N, SAMPLES)),
                                dim3(kMixCols * SAMPLES), 0, s, (const cplx<T> *)Tsp, (const cplx<T> *)WT, (cplx<T> *)OT,
                                g.N, g.M, g.C, KX, KXP);
+            TNMF_LAUNCH_CHECK();
+            return TNMF_OK;
+        }
+    }
+    if constexpr (AY <= kMixRShMaxAy) {
+        // large calls: the same arithmetic with the row spectra staged through LDS, every entry loaded once
+        if (mixed_reconstruct_sh_takes(g, KXP)) {
+            // kMixRShPerCU workgroups per CU and no more: unused dynamic LDS tops the tiles up to just over a
+            // (kMixRShPerCU + 1)-th of the CU's 160 KiB
+            constexpr unsigned tiles_lds = mix_rsh_lds_bytes(AY), hold = (160u << 10) / (kMixRShPerCU + 1) + 1;
+            static_assert(tiles_lds * kMixRShPerCU <= 160u << 10, "the tiles of kMixRShPerCU workgroups fit a CU");
+            hipLaunchKernelGGL((k_mix_reconstruct_sh<T, AY, kMixRShStrips, kMixRShTiles>),
+                               dim3(tiles, (unsigned)cdiv(g.Dy, 16 * kMixRShStrips), (unsigned)g.N),
+                               dim3(kMixCols * kMixRShStrips), tiles_lds < hold ? hold - tiles_lds : 0u, s,
+                               (const cplx<T> *)Tsp, (const cplx<T> *)WT,
+                               (cplx<T> *)OT, g.M, g.Hy, g.Dy, KX, KXP);
             TNMF_LAUNCH_CHECK();
             return TNMF_OK;
         }
@@ -480,12 +608,7 @@ __global__ __launch_bounds__(kMixCols *GROUPS, 2) void k_mix_grad_W2(const cplx<
 // picked by op_sel like p and q.  One ring period = one chunk.
 // grid: 1-D, logical (atom blocks, kx tiles, groups), atom blocks fastest, XCD remap as above; partial sums
 // [group][M][AY][KXP] as k_fft_sum_groups reads them.  Groups without samples store zeros.
-// (device pass: without hipcc's pairing of DS accesses -- a ds_read2_b64 of X1 and X2 moves half the bytes per LDS clock)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define TNMF_MIX_NO_DS_PAIRING __attribute__((target("no-load-store-opt")))
-#else
-#define TNMF_MIX_NO_DS_PAIRING
-#endif
+// (TNMF_MIX_NO_DS_PAIRING: a ds_read2_b64 of X1 and X2 moves half the bytes per LDS clock)
 template <typename T, int AY>
 __global__ __launch_bounds__(kMixCols *kMixW3Atoms, kMixW3Waves) TNMF_MIX_NO_DS_PAIRING void k_mix_grad_W3(
     const cplx<T> *Tsp, const cplx<T> *VT, const cplx<T> *RT, cplx<T> *Gn, cplx<T> *Gp, int N, int M, int Hy, int Dy,
@@ -726,6 +849,19 @@ bool mixed_grad_W3_takes(const Geo &g, int KXP) {
     const long span = (long)kMixW3Atoms * g.Hy * KXP * 8;
     const long spectra = (long)g.N * g.M * g.Hy * KXP * 8;
     return g.C == 1 && g.Ay <= kMixW3MaxAy && !(g.Dy == 1 && g.Ay == 1) && span < (1L << 31) && spectra >= kMixW3MinBytes;
+}
+
+// k_mix_reconstruct_sh takes the 2-D one-channel calls with atoms up to 12 rows whose row spectra of H reach 24 MiB (the
+// threshold of the W gradient's large-call kernel: the same calls run both); below that the grid of the register form
+// fills the chip as well and every geometry of the FFT matrix stays on the kernel its mirror names.  Its per-lane byte
+// offsets (last row of a plane) must fit 31 bits.
+bool mixed_reconstruct_sh_takes(const Geo &g, int KXP) {
+#ifdef TNMF_MIX_NO_RSH   // A/B flavour of the library (Makefile: VARIANT): every reconstruct stays on the register form
+    return false;
+#endif
+    const long plane = (long)g.Hy * KXP * 8;
+    const long spectra = (long)g.N * g.M * g.Hy * KXP * 8;
+    return g.C == 1 && g.Ay <= kMixRShMaxAy && !(g.Dy == 1 && g.Ay == 1) && plane < (1L << 31) && spectra >= kMixRShMinBytes;
 }
 
 int mixed_reconstruct(const Geo &g, const void *Tsp, const void *WT, void *OT, int KX, int KXP, hipStream_t s) {

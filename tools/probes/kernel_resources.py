@@ -1,12 +1,15 @@
 """What the compiler reports per kernel of a HIP source, without a GPU: registers, LDS, scratch and occupancy.
 
-    python tools/probes/kernel_resources.py events.hip pursuit.hip [--root OTHER_CHECKOUT] [--no-lds KERNEL ...]
+    python tools/probes/kernel_resources.py events.hip pursuit.hip [--root OTHER_CHECKOUT] [--no-lds KERNEL ...] [--only KERNEL ...]
 
 Compiles tnmf_amd/csrc/<file> for gfx950 with the Makefile's flags and -Rpass-analysis=kernel-resource-usage and prints one
 markdown row per kernel.  Exits 1 when a kernel uses scratch, when the device assembly holds a function call
 (s_swappc_b64: something was not inlined), or when a kernel whose name starts with one of --no-lds has LDS -- the check
 behind event_walk.h, whose Occurrence has to stay in registers:
     python tools/probes/kernel_resources.py events.hip pursuit.hip --no-lds k_events_update k_events_gain k_pursuit_pick
+--only restricts the rows and the scratch check to kernels whose name starts with one of the given prefixes -- the row
+behind fft.h's mix_rsh_waves() and mix_rsh_lds_bytes() (one line per atom height: VGPRs, LDS, no scratch):
+    python tools/probes/kernel_resources.py fft_mixed.hip --only k_mix_reconstruct_sh
 """
 import argparse
 import os
@@ -27,6 +30,7 @@ def main():
     ap.add_argument('sources', nargs='+')
     ap.add_argument('--root', default=ROOT)
     ap.add_argument('--no-lds', nargs='*', default=[])
+    ap.add_argument('--only', nargs='*', default=[])
     args = ap.parse_args()
     csrc = os.path.join(args.root, 'tnmf_amd', 'csrc')
     bad = []
@@ -52,6 +56,8 @@ def main():
             if m and kernel:
                 rows[kernel][FIELDS[m.group(1)]] = int(m.group(2))
         for kernel, row in rows.items():
+            if args.only and not any(kernel.startswith(k) for k in args.only):
+                continue
             print(f'| `{kernel}` | ' + ' | '.join(str(row[f]) for f in FIELDS.values()) + ' |')
             if row['scratch']:
                 bad.append(f'{kernel}: scratch')
