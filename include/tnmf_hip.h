@@ -796,6 +796,46 @@ int tnmf_hip_events_nnls(tnmf_hip_ctx *ctx, long long n_rows, long long nnz, con
                          int *converged_out /* host */, double *history_out /* host, may be NULL */, int history_capacity,
                          int *n_history_out /* host, may be NULL */, void *stream);
 
+/* ---- events: standard errors (ABI 8, additive: the version stays 8) -------------------------------------------------------
+ * How well the strengths of a list are determined.  At the solution of tnmf_hip_events_nnls the strengths of the active
+ * rows A = {i : h_i > 0} are the least-squares estimate on that support: Cov(h_A) = sigma^2 (G_AA)^-1.  This entry gives
+ * the DIAGONAL of (G_AA)^-1, exactly: G is sparse, G_AA is block diagonal over the connected components of its coupling
+ * graph (rows couple where their footprints meet), and each component is a small dense problem -- one Cholesky
+ * factorisation, the inverse of the factor, d_i = sum_{k >= i} (L^-1)_ki^2.  All in double.
+ *
+ * tnmf_hip_events_inverse_diag.  On the DEVICE: the CSR triple of tnmf_hip_events_nnls (row_start[n_rows + 1], col[nnz],
+ * val[nnz]; columns ascending within a row, the diagonal present, symmetric); comp_start[n_comp + 1], the boundaries of
+ * the components in member[n_active]: the active rows grouped by component and ascending inside each; local[n_rows]: a
+ * row's position inside its component, -1 for a row that is not active; scratch: scratch_doubles doubles, uninitialised,
+ * the caller's.  On the HOST: comp_sizes[n_comp], the sizes comp_start[c + 1] - comp_start[c], from which every launch is
+ * planned.  The components are given in ASCENDING SIZE.  Three paths by the size n of a component:
+ *   n = 1                               d = 1 / G_ii, elementwise over such components: no workgroup per component;
+ *   2 <= n <= TNMF_EVENTS_INVERSE_LDS   one workgroup per component, the packed lower triangle in LDS (column-major, so
+ *                                       that the lanes of every inner loop read consecutive doubles); TNMF_EVENTS_INVERSE_LDS
+ *                                       = 200 is the largest n with n (n + 1) / 2 + n doubles (the triangle and the original
+ *                                       diagonal) inside 160 KB: 20 300 of 20 480;
+ *   n > TNMF_EVENTS_INVERSE_LDS         the same steps on a dense n x n tile plus one column, n^2 + n doubles of scratch, one
+ *                                       workgroup per component; launched in batches whose tiles fit scratch_doubles.  No
+ *                                       component of at most TNMF_EVENTS_INVERSE_LDS rows reads the scratch (it may be NULL).
+ * Outputs on the device: d_out[n_rows] = ((G_AA)^-1)_ii for an active row, NaN for any other -- every element is written --
+ * and status_out[n_comp] = 0, or 1 for a component that is numerically singular: a pivot of its factorisation
+ * <= n * 2^-52 * (that row's original G_ii); its rows get d = +inf, the other components are not affected.  (Two orientations
+ * of a symmetric atom at one place are collinear: this happens on legitimate lists.)  An entry of a component's rows whose
+ * column is not active or belongs to another component is skipped; indices outside their ranges are skipped and runs are
+ * clamped: nothing is read or written out of bounds.  The sums run in a fixed order, there are no atomics: the same
+ * operands give the same bits run after run.  Asynchronous.  With n_rows == 0 it does nothing.
+ * Refused before anything is written and without touching a device: TNMF_E_NULL for a NULL ctx, a NULL operand that the
+ * sizes make necessary and any negative size; TNMF_E_UNSUPPORTED for more than 2^31 - 1 rows or entries; TNMF_E_GEOM for
+ * n_active > n_rows, n_comp > n_active, sizes below 1, not ascending or not adding up to n_active, and a largest component
+ * above TNMF_EVENTS_INVERSE_LDS whose tile does not fit the scratch. */
+#define TNMF_EVENTS_INVERSE_LDS 200
+
+int tnmf_hip_events_inverse_diag(tnmf_hip_ctx *ctx, long long n_rows, long long nnz, const int *row_start, const int *col,
+                                 const double *val, long long n_comp, const int *comp_start,
+                                 const int *comp_sizes /* host */, long long n_active, const int *member, const int *local,
+                                 double *scratch /* may be NULL */, long long scratch_doubles, double *d_out /* double */,
+                                 int *status_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

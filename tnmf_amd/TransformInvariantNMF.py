@@ -33,8 +33,8 @@ from . import transforms as _transforms
 from .backends._Backend import Backend, sliceNone
 # (the host side of the events; the names stay importable from this module)
 from .events_host import (event_boxes, event_images, events_alternatives_numpy, events_fit_numpy,  # noqa: F401
-                          events_gain_numpy, events_gram_numpy, events_landscape_numpy, events_norms_numpy, events_numpy,
-                          events_solve_numpy, find_peaks_numpy, landscape_gains, pursuit_loop, pursuit_numpy,
+                          events_gain_numpy, events_gram_numpy, events_inverse_diag_numpy, events_landscape_numpy,
+                          events_norms_numpy, events_numpy, events_solve_numpy, find_peaks_numpy, landscape_gains, pursuit_loop, pursuit_numpy,
                           relabel_hops, relocation_hops)
 
 
@@ -513,6 +513,70 @@ class TransformInvariantNMF:
         as_rows = lambda x: np.asarray(x).astype(np.int64).reshape(len(new))   # noqa: E731
         return Detections(sample=as_rows(det.sample), atom=as_rows(det.atom), transform=as_rows(det.transform),
                           shift=shift, origin=shift - offset, strength=new.astype(self._V.dtype))
+
+    def detection_errors(self, det, noise: Optional[float] = None, max_component: int = 2048) -> Tuple[np.ndarray, np.ndarray]:
+        """(stderr [K], vif [K]) in float64: how well the strengths of ``det`` are determined.  Meant for the output of
+        ``solve_detections``: at that solution the strengths of the active rows ``A = {i : strength_i > 0}`` are the
+        least-squares estimate on their support, so ``Cov(h_A) = sigma^2 (G_AA)^-1`` with ``G_ij = <phi_i, phi_j>`` the Gram
+        matrix of the occurrences.  ``stderr_i = sigma sqrt(((G_AA)^-1)_ii)`` is the standard error of a strength --
+        ``z = det.strength / stderr`` is a threshold without units -- and ``vif_i = G_ii ((G_AA)^-1)_ii >= 1`` the variance
+        inflation: how much the neighbours of a row blur it, exactly 1 for a row that touches no other active row.  G is
+        sparse and ``G_AA`` block diagonal over the connected components of its coupling graph, so the diagonal of the inverse
+        is exact: one small dense factorisation per component.  A row of strength 0 gets NaN in both; the rows of a component
+        that is numerically singular (two orientations of a symmetric atom at one place are collinear) get +inf.
+
+        noise : the standard deviation sigma of the data, finite and > 0.  ``None`` estimates it from the residual of the
+                list, ``sigma^2 = ||V - R(det)||^2 / (n_obs - K_A)`` with ``n_obs`` the entries of this model's (rank's)
+                samples and ``K_A`` the active rows; ValueError when ``n_obs <= K_A``.
+        max_component : the largest component that is inverted (int >= 1); a larger one raises ValueError.
+
+        Read-out: ``errors_info_``, a dict with noise, dof, residual_energy, n_active, n_components, largest_component,
+        n_singular and rounds (of the component search).  The rows must be distinct; the plain Frobenius objective only.
+        ``H``, ``W`` and ``det`` are not touched.  On a backend with ``event_errors`` everything runs on the device.  With a
+        process group every rank uses its own samples and the call is not collective: a sigma shared by the ranks is the
+        caller's to pass in as ``noise``."""
+        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
+            raise NotImplementedError('detection_errors covers the plain Frobenius objective (beta_loss 2, no weights)')
+        if noise is not None and (isinstance(noise, (bool, np.bool_)) or not isinstance(noise, numbers.Real)
+                                  or not math.isfinite(noise) or not noise > 0):
+            raise ValueError(f'noise must be None or a finite number > 0, not {noise!r}')
+        if (isinstance(max_component, (bool, np.bool_)) or not isinstance(max_component, numbers.Integral)
+                or max_component < 1):
+            raise ValueError(f'max_component must be an int >= 1, not {max_component!r}')
+        sample, plane, shift, strength = self._events_of(det, distinct=True)
+        hook = getattr(self._backend, 'event_errors', None)
+        if hook is not None:
+            d, b, energy, info = hook(self._V, self._W_dict, sample, plane, shift, strength, int(max_component))
+            d, b = (np.asarray(self._backend.to_ndarray(x), dtype=np.float64) for x in (d, b))
+            row_size = np.asarray(self._backend.to_ndarray(info['row_size']))
+        else:
+            V = np.asarray(self._local_V(), dtype=np.float64)
+            G, c = events_gram_numpy(self._backend.to_ndarray(self._W_dict), self._V.shape[2:], int(self._H.shape[0]),
+                                     getattr(self._backend, '_reconstruction_mode', 'valid'), sample, plane, shift,
+                                     V=V, sparse=True)
+            h = strength.astype(np.float64)
+            d, info = events_inverse_diag_numpy(G, h > 0, int(max_component))
+            row_of = np.repeat(np.arange(len(h)), np.diff(G[0]))
+            b = np.zeros(len(h))
+            b[row_of[row_of == G[1]]] = G[2][row_of == G[1]]
+            energy = max(float(np.sum(V * V) - 2. * (c @ h) + np.sum(G[2] * h[row_of] * h[G[1]])), 0.)
+            row_size = info['row_size']
+        n_obs = int(self._H.shape[0]) * int(np.prod(self._V.shape[1:]))
+        dof = n_obs - int(info['n_active'])
+        if noise is None:
+            if dof <= 0:
+                raise ValueError(f'detection_errors: {n_obs} observations do not determine the noise of '
+                                 f'{info["n_active"]} active rows: pass noise=')
+            sigma = math.sqrt(energy / dof)
+        else:
+            sigma = float(noise)
+        with np.errstate(invalid='ignore'):
+            stderr = sigma * np.sqrt(d)
+            vif = np.where(row_size == 1, 1., b * d)
+        self.errors_info_ = dict(noise=sigma, dof=dof, residual_energy=float(energy), n_active=int(info['n_active']),
+                                 n_components=int(info['n_components']), largest_component=int(info['largest_component']),
+                                 n_singular=int(info['n_singular']), rounds=int(info['rounds']))
+        return stderr, vif
 
     @staticmethod
     def _check_solve_args(tol, max_iterations) -> None:

@@ -35,6 +35,7 @@ EXPORTS = (
     'tnmf_hip_events_norms', 'tnmf_hip_pursuit_score', 'tnmf_hip_pursuit_pick', 'tnmf_hip_events_landscape',
     'tnmf_hip_events_alternatives',
     'tnmf_hip_events_pairs', 'tnmf_hip_events_gram', 'tnmf_hip_events_project', 'tnmf_hip_events_nnls',
+    'tnmf_hip_events_inverse_diag',
 )
 
 MODES = {'valid': 0, 'full': 1, 'circular': 2, 'reflect': 3}
@@ -46,6 +47,8 @@ GROUPS = {'flip': 0, 'mirrors': 1, 'rot90': 2, 'dihedral': 3}
 EVENT_CELLS = {1: (256,), 2: (16, 16)}
 # the events of a plane that tnmf_hip_events_grad_W sums into one slab: TNMF_EVENTS_SEGMENT
 EVENT_SEGMENT = 64
+# the largest component tnmf_hip_events_inverse_diag factors in LDS: TNMF_EVENTS_INVERSE_LDS
+EVENT_INVERSE_LDS = 200
 
 PATHS = {'auto': 0, 'generic': 1, 'mfma': 2, 'fft': 3, 'hybrid': 4, 'split': 5}
 
@@ -166,6 +169,7 @@ def load() -> ctypes.CDLL:
     lib.tnmf_hip_events_project.argtypes = [vp, gp, ci, vp, vp, ll, vp, vp, vp]
     lib.tnmf_hip_events_nnls.argtypes = [vp, ll, ll, vp, vp, vp, vp, vp, cd, ci, ci, vp, pi, ctypes.POINTER(cd), pi,
                                          ctypes.POINTER(cd), ci, pi, vp]
+    lib.tnmf_hip_events_inverse_diag.argtypes = [vp, ll, ll, vp, vp, vp, ll, vp, pi, ll, vp, vp, vp, ll, vp, vp, vp]
     lib.tnmf_hip_pad_H.argtypes = [vp, gp, ci, vp, vp, vp]
     lib.tnmf_hip_fold_H.argtypes = [vp, gp, ci, vp, vp, vp]
     for name in EXPORTS:

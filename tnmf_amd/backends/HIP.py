@@ -1144,6 +1144,124 @@ class HIP_Backend(Backend):
         c = self.project_event_list(W, events)
         return self.nnls_event_list(csr, c, strength, tol, max_iterations, check_every)
 
+    # -- events: standard errors ---------------------------------------------------------------------------------------------
+    # Cov(h_A) = sigma^2 (G_AA)^-1 on the active rows A (include/tnmf_hip.h, "events: standard errors"): G_AA is block diagonal
+    # over the connected components of its coupling graph, found here on the device; the kernel inverts each block.
+    def _csr_rows(self, csr) -> torch.Tensor:
+        """row [nnz] int64: the row of every stored entry."""
+        row_start, col, _ = csr
+        K = row_start.numel() - 1
+        return torch.repeat_interleave(torch.arange(K, dtype=torch.int64, device=self._device),
+                                       (row_start[1:] - row_start[:-1]).to(torch.int64), output_size=col.numel())
+
+    def event_components(self, csr, active: torch.Tensor):
+        """The connected components of the graph of ``csr`` (gram_event_list) restricted to the entries whose row and column
+        are both ``active`` ([K] bool on the device) -> dict(comp_start [n_comp + 1] int32, member [K_A] int32: the active
+        rows grouped by component and ascending inside each, local [K] int32: a row's position inside its component, -1 for
+        a row that is not active, row_size [K] int64: the size of a row's component, 0 where not active -- all on the device
+        -- and on the host sizes [n_comp] int32 and rounds).  The components come in ascending size, equal sizes by their
+        smallest row.  Labels by min-label hooking with pointer jumping: in a round the root of every tree takes the
+        smallest label its members see across an edge, then ceil(log2 K) jumps label <- label[label] flatten the trees
+        again; a round halves the trees that can still merge, where plain propagation moves a label one edge.  The host reads
+        one flag per round, the counts of the result, and no array of the size of the matrix."""
+        row_start, col, _ = csr
+        K = int(row_start.numel()) - 1
+        with self._timed('events_components'):
+            active = active.to(device=self._device, dtype=torch.bool).reshape(-1)
+            assert active.numel() == K
+            every = torch.arange(K, dtype=torch.int64, device=self._device)
+            label, rounds = every, 0
+            if col.numel() > K:   # (the diagonal alone: no edges)
+                u, c = self._csr_rows(csr), col.to(torch.int64)
+                v = torch.where(active[u] & active[c], c, u)   # (an entry that is no edge of the graph: a loop at its row)
+                jumps = max(1, (K - 1).bit_length())
+                while True:
+                    rounds += 1
+                    new = label.scatter_reduce(0, label[u], label[v], 'amin', include_self=True)
+                    for _ in range(jumps):
+                        new = new[new]
+                    changed = bool((new != label).any())   # the one scalar of the round
+                    label = new
+                    if not changed:
+                        break
+            rows = torch.nonzero(active).reshape(-1)
+            roots, which, counts = torch.unique(label[rows], return_inverse=True, return_counts=True)
+            order = torch.argsort(counts * (K + 1) + roots)         # ascending size, then the smallest row
+            rank = torch.empty_like(order)
+            rank[order] = torch.arange(order.numel(), dtype=torch.int64, device=self._device)
+            comp = rank[which]                                      # the component of every active row
+            by_comp = torch.argsort(comp * max(K, 1) + rows)
+            member, comp = rows[by_comp], comp[by_comp]
+            sizes = counts[order]
+            comp_start = torch.cat([torch.zeros(1, dtype=torch.int64, device=self._device), torch.cumsum(sizes, 0)])
+            local = torch.full((K,), -1, dtype=torch.int64, device=self._device)
+            local[member] = torch.arange(member.numel(), dtype=torch.int64, device=self._device) - comp_start[comp]
+            row_size = torch.zeros(K, dtype=torch.int64, device=self._device)
+            row_size[member] = sizes[comp]
+            return dict(comp_start=comp_start.to(torch.int32).contiguous(), member=member.to(torch.int32).contiguous(),
+                        local=local.to(torch.int32).contiguous(), row_size=row_size,
+                        sizes=np.ascontiguousarray(sizes.cpu().numpy().astype(np.int32)), rounds=rounds)
+
+    def inverse_diag_event_list(self, csr, active: torch.Tensor, max_component: int = 2048,
+                                out: Optional[torch.Tensor] = None, scratch_doubles: Optional[int] = None):
+        """(d [K] float64 on the device, info): d_i = ((G_AA)^-1)_ii for the rows of ``active``, NaN for the others, +inf
+        for the rows of a component that is numerically singular -> event_components, tnmf_hip_events_inverse_diag.
+        ValueError, before ``out`` (d, when given) is written, for a component of more than ``max_component`` rows.  info:
+        n_active, n_components, largest_component, n_singular, rounds, sizes [n_comp] and status [n_comp] on the host,
+        row_size [K] on the device.  ``scratch_doubles``: the scratch of the components beyond the LDS path (default: what
+        they all take, at most 2^24 doubles or one tile of the largest)."""
+        row_start, col, val = csr
+        K = int(row_start.numel()) - 1
+        assert row_start.dtype == torch.int32 and col.dtype == torch.int32 and val.dtype == torch.float64
+        comps = self.event_components(csr, active)
+        sizes = comps['sizes']
+        largest = int(sizes[-1]) if len(sizes) else 0
+        if largest > int(max_component):
+            raise ValueError(f'events: the largest component of the active rows has {largest} rows, more than '
+                             f'max_component={int(max_component)}')
+        d = torch.empty(K, dtype=torch.float64, device=self._device) if out is None else out
+        assert d.dtype == torch.float64 and d.is_contiguous() and d.numel() == K
+        tiles = [int(n) * int(n) + int(n) for n in sizes if n > _lib.EVENT_INVERSE_LDS]
+        if scratch_doubles is None:
+            scratch_doubles = min(sum(tiles), max(2 ** 24, tiles[-1])) if tiles else 0
+        scratch = torch.empty(int(scratch_doubles), dtype=torch.float64, device=self._device)
+        status = torch.zeros(len(sizes), dtype=torch.int32, device=self._device)
+        args = (self._ctx, K, val.numel(), _ptr(row_start), _ptr(col), _ptr(val), len(sizes), _ptr(comps['comp_start']),
+                sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), comps['member'].numel(), _ptr(comps['member']),
+                _ptr(comps['local']), _ptr(scratch) if scratch.numel() else None, scratch.numel(), _ptr(d), _ptr(status),
+                self._stream())
+        with self._timed('events_inverse_diag'):
+            code = self._lib.tnmf_hip_events_inverse_diag(*args)
+        _lib.check(code, 'tnmf_hip_events_inverse_diag')
+        status = status.cpu().numpy()
+        return d, dict(n_active=int(comps['member'].numel()), n_components=len(sizes), largest_component=largest,
+                       n_singular=int(np.count_nonzero(status)), rounds=int(comps['rounds']), sizes=sizes, status=status,
+                       row_size=comps['row_size'])
+
+    def event_errors(self, V, W: torch.Tensor, sample, plane, shift, strength, max_component: int = 2048):
+        """(d [K], b [K], residual energy, info) for the standard errors of the strengths of a list against the resident
+        samples (`V` is the array given to initialize(), as for the other hooks): with A the rows of strength > 0,
+        d = diag (G_AA)^-1 (inverse_diag_event_list: NaN off A, +inf on a singular component), b = diag G, and
+        ||V - R(list)||^2 = ||V||^2 - 2 c'h + h'Gh in double from c, G, h and the samples' own energy -- no render --, not
+        below 0.  d and b are float64 on the device, the energy a float.  The events must be distinct.  With a process
+        group every rank takes its own samples: there is no collective."""
+        if self._G_dev is not None:
+            raise NotImplementedError('event_errors is unweighted')
+        sample, plane, shift, strength = self._check_events(W.shape[0], sample, plane, shift, strength)
+        images, cell_start, events = self.event_list(sample, plane, shift)
+        csr = self.gram_event_list(W, images, cell_start, events)
+        c = self.project_event_list(W, events)
+        h = strength.to(torch.float64)
+        d, info = self.inverse_diag_event_list(csr, h > 0, max_component)
+        K = h.numel()
+        row, col, val = self._csr_rows(csr), csr[1].to(torch.int64), csr[2]
+        b = torch.zeros(K, dtype=torch.float64, device=self._device)
+        on_diagonal = row == col
+        b[row[on_diagonal]] = val[on_diagonal]
+        v = self._V_dev.to(torch.float64)
+        energy = torch.sum(v * v) - 2. * torch.sum(c * h) + torch.sum(val * h[row] * h[col])
+        return d, b, max(float(energy), 0.), info
+
     # -- pursuit: the list found by forward selection ---------------------------------------------------------------------
     # A round (include/tnmf_hip.h, "pursuit") is the H gradient's numerator of the residual, the gain map, its peaks and
     # the exact score of the kept ones; the rows are chosen on the host (events_host.pursuit_loop) from the

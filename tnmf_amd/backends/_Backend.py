@@ -50,6 +50,11 @@ And ``solve_events(V, W, sample, plane, shift, strength, tol, max_iterations, ch
 the Frobenius objective on the fixed support (include/tnmf_hip.h, "events: exact strengths"); without it ``solve_detections``
 runs ``events_gram_numpy`` and ``events_solve_numpy``.  A ``pursue_events`` hook takes ``solve=(tol, max_iterations)`` when
 the front end asks for ``strengths='solve'``.
+And ``event_errors(V, W, sample, plane, shift, strength, max_component) -> (d, b, residual_energy, info)`` (backend-native
+float64 ``[K]`` twice, a float; info: n_active, n_components, largest_component, n_singular, rounds, row_size ``[K]``): the
+diagonal of the inverse of the active block of the Gram matrix, the diagonal of the matrix and ``||V - R(list)||^2``
+(include/tnmf_hip.h, "events: standard errors"); without it ``detection_errors`` runs ``events_gram_numpy`` and
+``events_inverse_diag_numpy``.
 """
 import abc
 from typing import Optional, Sequence, Tuple, Union

@@ -10,6 +10,7 @@
 #include "beta.h"
 #include "events.h"
 #include "solve.h"
+#include "covariance.h"
 #include "fft.h"
 #include "generic.h"
 #include "mfma.h"
@@ -1596,6 +1597,35 @@ int tnmf_hip_events_nnls(tnmf_hip_ctx *ctx, long long n_rows, long long nnz, con
     return events_nnls(ctx, (int)n_rows, (int)nnz, row_start, col, val, c, h_inout, tol, max_iterations, check_every,
                        workspace, iterations_out, kkt_out, converged_out, history_out, history_capacity, n_history_out,
                        static_cast<hipStream_t>(stream));
+}
+
+int tnmf_hip_events_inverse_diag(tnmf_hip_ctx *ctx, long long n_rows, long long nnz, const int *row_start, const int *col,
+                                 const double *val, long long n_comp, const int *comp_start, const int *comp_sizes,
+                                 long long n_active, const int *member, const int *local, double *scratch,
+                                 long long scratch_doubles, double *d_out, int *status_out, void *stream) {
+    if (!ctx) return TNMF_E_NULL;
+    if (n_rows < 0 || nnz < 0 || n_comp < 0 || n_active < 0 || scratch_doubles < 0) return TNMF_E_NULL;
+    if (n_rows > 0 && (!row_start || !local || !d_out || (nnz > 0 && (!col || !val)))) return TNMF_E_NULL;
+    if (n_comp > 0 && (!comp_start || !comp_sizes || !member || !status_out)) return TNMF_E_NULL;
+    if (n_rows > 0x7fffffffLL || nnz > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
+    if (n_active > n_rows || n_comp > n_active) return TNMF_E_GEOM;
+    long long total = 0, previous = 1;
+    for (long long c = 0; c < n_comp; ++c) {   // (the host copy of the sizes: every launch is planned from it)
+        const long long n = comp_sizes[c];
+        if (n < previous) return TNMF_E_GEOM;
+        previous = n, total += n;
+        if (total > n_active) return TNMF_E_GEOM;
+    }
+    if (total != n_active) return TNMF_E_GEOM;
+    if (n_comp > 0 && previous > kInverseDiagLds) {
+        if (events_inverse_diag_tile(previous) > scratch_doubles) return TNMF_E_GEOM;
+        if (!scratch) return TNMF_E_NULL;
+    }
+    if (n_rows == 0) return TNMF_OK;
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return events_inverse_diag(ctx, (int)n_rows, (int)nnz, row_start, col, val, (int)n_comp, comp_start, comp_sizes,
+                               (int)n_active, member, local, scratch, scratch_doubles, d_out, status_out,
+                               static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

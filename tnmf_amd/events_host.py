@@ -349,6 +349,78 @@ def events_solve_numpy(G, c: np.ndarray, start: np.ndarray, tol: float, max_iter
                    history=np.array(history, dtype=np.float64).reshape(len(history), 2))
 
 
+def events_inverse_diag_numpy(G, active, max_component: int = 2048):
+    """The diagonal of the inverse of the active block of a list's Gram matrix on the host, for backends without
+    ``event_errors`` -- the semantics of tnmf_hip_events_inverse_diag (include/tnmf_hip.h, "events: standard errors") in
+    float64: ``d_i = ((G_AA)^-1)_ii`` for the rows of ``active`` ([K] bool), NaN for the others.  G: the CSR triple of
+    ``events_gram_numpy(..., sparse=True)`` (or a dense matrix).  G_AA is block diagonal over the connected components of
+    the graph of its active-active entries (union-find over the entries); every component is inverted on its own with
+    ``numpy.linalg``.  A component whose Cholesky factorisation (rows ascending) meets a pivot ``<= n * 2^-52 *`` (that
+    row's G_ii) is numerically singular: its rows get +inf.  ValueError for a component of more than ``max_component`` rows.
+    Returns ``(d, info)``: n_active, n_components, largest_component, n_singular, rounds (0: no rounds on the host), sizes
+    and status ([n_comp], ascending size, equal sizes by their smallest row), row_size [K] (0 where not active).  Not on the
+    hip path."""
+    active = np.asarray(active, dtype=bool).reshape(-1)
+    K = len(active)
+    if isinstance(G, tuple):
+        row_start, col, val = (np.asarray(a) for a in G)
+        row = np.repeat(np.arange(K), np.diff(row_start))
+        col = col.astype(np.int64)
+    else:
+        dense = np.asarray(G, dtype=np.float64).reshape(K, K)
+        row, col = np.nonzero((dense != 0) | np.eye(K, dtype=bool))
+        val = dense[row, col]
+    parent = np.arange(K)
+
+    def find(i):
+        while parent[i] != i:
+            parent[i] = parent[parent[i]]
+            i = parent[i]
+        return i
+    for i, j in zip(row.tolist(), col.tolist()):
+        if i < j and active[i] and active[j]:
+            a, b = find(i), find(j)
+            if a != b:
+                parent[max(a, b)] = min(a, b)
+    rows = np.flatnonzero(active)
+    roots = np.array([find(i) for i in rows.tolist()], dtype=np.int64)
+    by_root = np.argsort(roots, kind='stable')
+    groups = np.split(rows[by_root], np.flatnonzero(np.diff(roots[by_root])) + 1) if len(rows) else []
+    groups.sort(key=lambda g: (len(g), g[0]))
+    sizes = np.array([len(g) for g in groups], dtype=np.int32)
+    if len(sizes) and sizes[-1] > max_component:
+        raise ValueError(f'events: the largest component of the active rows has {int(sizes[-1])} rows, more than '
+                         f'max_component={int(max_component)}')
+    comp, where = np.full(K, -1, dtype=np.int64), np.full(K, -1, dtype=np.int64)
+    for c, g in enumerate(groups):
+        comp[g], where[g] = c, np.arange(len(g))
+    inside = (comp[row] >= 0) & (comp[row] == comp[col])      # the entries of the blocks, sorted by block
+    er, ec, ev = row[inside], col[inside], val[inside]
+    order = np.argsort(comp[er], kind='stable')
+    er, ec, ev = er[order], ec[order], ev[order]
+    first = np.searchsorted(comp[er], np.arange(len(groups) + 1))
+    d = np.full(K, np.nan)
+    status = np.zeros(len(groups), dtype=np.int32)
+    row_size = np.zeros(K, dtype=np.int64)
+    for c, g in enumerate(groups):
+        n = len(g)
+        row_size[g] = n
+        block = np.zeros((n, n))
+        mine = slice(first[c], first[c + 1])
+        block[where[er[mine]], where[ec[mine]]] = ev[mine]
+        L = np.zeros((n, n))
+        for j in range(n):   # the pivots of the factorisation, against the bar of the header
+            pivot = block[j, j] - L[j, :j] @ L[j, :j]
+            if not pivot > n * 2. ** -52 * block[j, j]:
+                status[c] = 1
+                break
+            L[j, j] = np.sqrt(pivot)
+            L[j + 1:, j] = (block[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
+        d[g] = np.inf if status[c] else np.diag(np.linalg.inv(block))
+    return d, dict(n_active=int(len(rows)), n_components=len(groups), largest_component=int(sizes[-1]) if len(sizes) else 0,
+                   n_singular=int(np.count_nonzero(status)), rounds=0, sizes=sizes, status=status, row_size=row_size)
+
+
 def landscape_gains(a: np.ndarray, b: np.ndarray) -> np.ndarray:
     """``a^2 / (2 b)`` where ``a > 0`` and ``b > 0``, else 0: what a row at that shift, at its best strength ``a / b``, takes off
     the objective of the list without the row."""
