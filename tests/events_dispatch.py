@@ -16,7 +16,7 @@ import numpy as np
 
 import events_reference as eref
 
-NUM_CU = 256            # compute units of one MI355X (what grid_for() reads from ctx->num_cu there)
+NUM_CU = 256            # compute units of one MI355X (what events_grid() reads from ctx->num_cu there)
 
 THREADS = 256           # events.h, kEventThreads
 CHAN = 4                # events.hip, kChan
@@ -108,7 +108,7 @@ def shift_shape(geometry):
 
 
 def grid_for(blocks, num_cu=NUM_CU):
-    """events.hip grid_for."""
+    """events.h events_grid, per_cu = 64."""
     return max(1, min(blocks, num_cu * 64))
 
 

@@ -60,13 +60,18 @@ def test_mirrored_rules_are_those_of_the_sources():
                  'const bool active = t < taps && sub < L;',
                  'for (int i = sub; i < count; i += L) {',
                  'const int chunks = (taps + kEventThreads - 1) / kEventThreads;',
-                 'return (unsigned)std::max<long long>(1, std::min<long long>(blocks, (long long)ctx->num_cu * 64));',
-                 'const unsigned grid = grid_for(ctx, (long long)g.N * nty * ntx);',
-                 'const unsigned grid = grid_for(ctx, (n_events + kWaves - 1) / kWaves);',
+                 # (the grid rule lives in events.h, below; per_cu is its default here)
+                 'const unsigned grid = events_grid(ctx, (long long)g.N * nty * ntx);',
+                 'const unsigned grid = events_grid(ctx, (n_events + kWaves - 1) / kWaves);',
                  'long long events_grad_W_slabs(long long n_events, int P) { return n_events / TNMF_EVENTS_SEGMENT + P; }',
                  'dim3((unsigned)n_slabs), dim3(kEventThreads)',
                  'const dim3 grid((unsigned)((long long)cdiv(taps, kEventThreads) * g.P));'):
         assert line in src, line
+    assert src.count('const unsigned grid = events_grid(ctx, (n_events + kWaves - 1) / kWaves);') == 2   # update, gain
+    events_h = _read(CSRC, 'events.h')
+    for line in ('inline unsigned events_grid(const tnmf_hip_ctx *ctx, long long blocks, int per_cu = 64) {',
+                 'return (unsigned)std::max<long long>(1, std::min<long long>(blocks, (long long)ctx->num_cu * per_cu));'):
+        assert line in events_h, line
     # the occurrence walk the wave kernels share: the image table and the lane loop, and one call per wave kernel with a
     # lane's first tap and stride
     walk = _read(CSRC, 'event_walk.h')

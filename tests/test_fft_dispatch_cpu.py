@@ -124,8 +124,8 @@ def test_lencfg_and_ladders_agree():
         assert line in spec, line
     assert spec.count('const int cg = g.C < kSpecCG ? g.C : kSpecCG;') == 2
     for macro in ('SPEC_R', 'SPEC_G'):
-        assert re.findall(r'case (\d): %s\(T_, (\d)\); break;' % macro, spec) == [('1', '1'), ('2', '2'), ('3', '3')]
-        assert 'default: %s(T_, 4); break;' % macro in spec
+        assert re.findall(r'case (\d): %s\(T, (\d)\); break;' % macro, spec) == [('1', '1'), ('2', '2'), ('3', '3')]
+        assert 'default: %s(T, 4); break;' % macro in spec
 
 
 def test_layout_and_dispatch_rules_are_those_of_the_source():

@@ -76,7 +76,8 @@ def test_mirrored_constants_and_rules_are_those_of_the_source():
             'if (ntaps < 1 || ntaps > kMaxTaps || (ntaps & 1) == 0) return TNMF_E_UNSUPPORTED;',
             'const int src = i + rad - t;'):
         assert line in gen, line
-    assert len(re.findall(r'return TNMF_E_GEOM;', gen[gen.index('int launch_pad_fold('):gen.index('#define LAUNCH_PF')])) == 3
+    pad_fold = gen.index('int launch_pad_fold(')
+    assert len(re.findall(r'return TNMF_E_GEOM;', gen[pad_fold:gen.index('with_dtype(', pad_fold)])) == 3
     for line in (
             # update_H_2d
             'const bool lateral = inhibition > 0 || cross_inhibition > 0;',
@@ -113,20 +114,23 @@ def test_mirrored_constants_and_rules_are_those_of_the_source():
 
 
 def test_launch_chain_is_that_of_the_source():
-    """The INH_LAUNCH chain: three compile-time instances in this order, then the run-time one; both dtypes."""
+    """The INH_LAUNCH chain: three compile-time instances in this order, then the run-time one; both dtypes, which every
+    launcher reaches as <T> inside a with_dtype call (common.h: a float arm and a double arm)."""
     src = _flat(_read('inhibit.hip'))
     chain = src[src.index('if (ly == 23 && lx == 23)'):src.index('#undef INH_LAUNCH')]
     arms = re.findall(r'(?:if \(ly == (\d+) && lx == (\d+)\)|else) INH_LAUNCH\((\d+), (\d+)\);', chain)
     assert [(int(c), int(d)) for _, _, c, d in arms] == list(ld.COMPILED) + [(0, 0)]
     assert all((a, b) == (c, d) for a, b, c, d in arms[:-1]) and arms[-1][:2] == ('', '')
-    assert 'launch_inhibition_t<float>(' in src and 'launch_inhibition_t<double>(' in src
+    common = _flat(_read('common.h'))
+    assert 'if (dtype == 0) return f(float{}); return f(double{});' in common[common.index('with_dtype(int dtype, F &&f)'):]
+    assert 'return with_dtype(dtype, [&](auto zero) { return launch_inhibition_t<decltype(zero)>(' in src
     assert len(ld.all_inhibition_instances()) == 8
     for k in ('k_mu_update_extra', 'k_fold_update'):
-        assert f'hipLaunchKernelGGL({k}<float>' in src and f'hipLaunchKernelGGL({k}<double>' in src
+        assert f'with_dtype(dtype, [&](auto zero) {{ using T = decltype(zero); hipLaunchKernelGGL({k}<T>' in src
     gen = _flat(_read('generic.hip'))
-    assert 'if (dtype == 0) LAUNCH_PF(k_fold_H, float); else LAUNCH_PF(k_fold_H, double);' in gen
-    assert 'if (dtype == 0) LAUNCH_PF(k_pad_H, float); else LAUNCH_PF(k_pad_H, double);' in gen
-    assert 'hipLaunchKernelGGL(k_convolve_axis<float>' in gen and 'hipLaunchKernelGGL(k_convolve_axis<double>' in gen
+    for k in ('k_fold_H', 'k_pad_H', 'k_convolve_axis'):
+        assert f'with_dtype(dtype, [&](auto zero) {{ using T = decltype(zero); hipLaunchKernelGGL({k}<T>' in gen
+    assert re.search(r'if \(fold\) with_dtype\(.*?k_fold_H<T>.*?\}\); else with_dtype\(.*?k_pad_H<T>', gen)
 
 
 def test_lengths_quoted_in_the_design_notes():

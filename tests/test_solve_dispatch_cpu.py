@@ -45,7 +45,8 @@ def test_constants_are_those_of_the_sources():
     assert sd.ROW_LANES == int(re.search(r'constexpr int kRowLanes = (\d+);', solve).group(1))
     assert 'constexpr int kRowsPerBlock = kEventThreads / kRowLanes;' in solve
     assert sd.ROWS_PER_BLOCK == sd.THREADS // sd.ROW_LANES == 16
-    assert 'return (unsigned)std::max<long long>(1, std::min<long long>(blocks, (long long)ctx->num_cu * 64));' in solve
+    assert 'inline unsigned events_grid(const tnmf_hip_ctx *ctx, long long blocks, int per_cu = 64) {' in events_h
+    assert 'return (unsigned)std::max<long long>(1, std::min<long long>(blocks, (long long)ctx->num_cu * per_cu));' in events_h
     assert sd.grid_for is ed.grid_for and sd.grid_for(10 ** 9, 7) == 7 * 64 and sd.grid_for(0) == 1
     assert 'long long events_nnls_workspace(long long n_rows) { return 7 * n_rows + kScalars; }' in solve
     assert 'kScalars = 8 }' in solve and 'ws = torch.empty(7 * K + 8, dtype=torch.float64' in _read('tnmf_amd', 'backends', 'HIP.py')
@@ -75,9 +76,10 @@ def test_mirrored_rules_are_those_of_the_sources():
                  'if (slot < capacity) pairs[slot] = (long long)me.w * K + other;',
                  'for (long long p = (long long)blockIdx.x * kWaves + wave; p < n_pairs; p += (long long)gridDim.x * kWaves) {',
                  'for (long long e = (long long)blockIdx.x * kWaves + wave; e < n_events; e += (long long)gridDim.x * kWaves) {',
-                 'const unsigned grid = grid_for(ctx, (n_images + kWaves - 1) / kWaves);',
-                 'const unsigned grid = grid_for(ctx, (n_pairs + kWaves - 1) / kWaves);',
-                 'const unsigned grid = grid_for(ctx, (n_events + kWaves - 1) / kWaves);',
+                 # (events_grid of events.h with its default per_cu = 64: test_constants_are_those_of_the_sources)
+                 'const unsigned grid = events_grid(ctx, (n_images + kWaves - 1) / kWaves);',
+                 'const unsigned grid = events_grid(ctx, (n_pairs + kWaves - 1) / kWaves);',
+                 'const unsigned grid = events_grid(ctx, (n_events + kWaves - 1) / kWaves);',
                  # the solver
                  '*a = min(max(row_start[i], 0), nnz);',
                  '*b = min(max(row_start[i + 1], *a), nnz);',

@@ -150,9 +150,10 @@ __global__ __launch_bounds__(kEventThreads) void k_events_alternatives(EventGeo 
 
 }  // namespace
 
-int events_alternatives(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const void *W,
-                        const int *events, const void *strength, long long n_events, const void *V, const void *R, int n_alt,
-                        int stride, double *a, double *b, double *mag, hipStream_t s) {
+int events_alternatives(tnmf_hip_ctx *ctx, const EventFrame &f, int dtype, const void *W, const int *events,
+                        const void *strength, long long n_events, const void *V, const void *R, int n_alt, int stride,
+                        double *a, double *b, double *mag, hipStream_t s) {
+    const EventGeo &g = f.g;
     if (n_events <= 0 || g.N <= 0) return TNMF_OK;
     const long long cells = (long long)g.C * g.Ay * g.Ax;
 #ifdef TNMF_ALTERNATIVES_WALK_ONLY   // (an A/B build for tools/probes/alternatives_bench.py: every row walks)
@@ -162,16 +163,13 @@ int events_alternatives(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mod
 #endif
     const int patch = stage && cells <= kPatchMax ? (int)cells : 0;
     const size_t lds = (size_t)kWaves * patch * sizeof(double);
-    const unsigned grid = (unsigned)std::max<long long>(
-        1, std::min<long long>((n_events + kWaves - 1) / kWaves, (long long)ctx->num_cu * TNMF_ALTERNATIVES_BLOCKS_PER_CU));
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_events_alternatives<float>, dim3(grid), dim3(kEventThreads), lds, s, g, mode, Sy, Sx, patch,
-                           n_alt, stride, (const float *)W, (const int4 *)events, (const float *)strength, n_events,
-                           (const float *)V, (const float *)R, a, b, mag);
-    else
-        hipLaunchKernelGGL(k_events_alternatives<double>, dim3(grid), dim3(kEventThreads), lds, s, g, mode, Sy, Sx, patch,
-                           n_alt, stride, (const double *)W, (const int4 *)events, (const double *)strength, n_events,
-                           (const double *)V, (const double *)R, a, b, mag);
+    const unsigned grid = events_grid(ctx, (n_events + kWaves - 1) / kWaves, TNMF_ALTERNATIVES_BLOCKS_PER_CU);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_events_alternatives<T>, dim3(grid), dim3(kEventThreads), lds, s, g, f.mode, f.Sy, f.Sx, patch,
+                           n_alt, stride, (const T *)W, (const int4 *)events, (const T *)strength, n_events, (const T *)V,
+                           (const T *)R, a, b, mag);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }

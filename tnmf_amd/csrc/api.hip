@@ -47,8 +47,6 @@ int to_geo(const tnmf_hip_geom *in, Geo *g) {
     return TNMF_OK;
 }
 
-inline size_t esize(int dtype) { return dtype == 0 ? 4 : 8; }
-
 // three shift axes (volumes): a kernel family of its own (volume.hip); H is C-contiguous there
 inline bool is_vol(const tnmf_hip_geom *in) { return in && in->ndim == 3; }
 
@@ -1385,10 +1383,13 @@ static int events_shift_shape(const EventGeo &g, int mode, int S[2]) {
 
 // the preamble of the events entry points that take a mode: the arguments that must be there, the geometry, the shift shape
 // (a mode out of range is events_shift_shape's TNMF_E_GEOM)
-static int events_enter(const tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, EventGeo *g, int S[2]) {
+static int events_enter(const tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, EventFrame *f) {
     if (!ctx || !geom) return TNMF_E_NULL;
-    const int rc = events_geo(geom, g);
-    return rc != TNMF_OK ? rc : events_shift_shape(*g, mode, S);
+    int S[2] = {0, 0};
+    int rc = events_geo(geom, &f->g);
+    if (rc == TNMF_OK) rc = events_shift_shape(f->g, mode, S);
+    f->mode = mode, f->Sy = S[0], f->Sx = S[1];
+    return rc;
 }
 
 int tnmf_hip_events_render(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *W_eff, const int *images,
@@ -1409,60 +1410,56 @@ int tnmf_hip_events_render(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const v
 int tnmf_hip_events_update(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,
                            void *strength_inout, long long n_events, const void *V, const void *R, double eps,
                            double sparsity, void *stream) {
-    EventGeo g;
-    int S[2];
-    const int rc = events_enter(ctx, geom, mode, &g, S);
+    EventFrame f;
+    const int rc = events_enter(ctx, geom, mode, &f);
     if (rc != TNMF_OK) return rc;
     if (n_events < 0) return TNMF_E_GEOM;
     if (!(eps >= 0) || !(sparsity >= 0)) return TNMF_E_UNSUPPORTED;
-    if (n_events > 0 && g.N > 0 && (!W_eff || !events || !strength_inout || !V || !R)) return TNMF_E_NULL;
+    if (n_events > 0 && f.g.N > 0 && (!W_eff || !events || !strength_inout || !V || !R)) return TNMF_E_NULL;
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
-    return events_update(ctx, g, geom->dtype, mode, S[0], S[1], W_eff, events, strength_inout, n_events, V, R,
+    return events_update(ctx, f, geom->dtype, W_eff, events, strength_inout, n_events, V, R,
                          eps + (sparsity > 0 ? sparsity : 0.), static_cast<hipStream_t>(stream));
 }
 
 int tnmf_hip_events_gain(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,
                          const void *strength, long long n_events, const void *V, const void *R, double *gain, double *mag,
                          void *stream) {
-    EventGeo g;
-    int S[2];
-    const int rc = events_enter(ctx, geom, mode, &g, S);
+    EventFrame f;
+    const int rc = events_enter(ctx, geom, mode, &f);
     if (rc != TNMF_OK) return rc;
     if (n_events < 0) return TNMF_E_GEOM;
     if (n_events > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
-    if (n_events > 0 && g.N > 0 && (!W_eff || !events || !strength || !V || !R || !gain)) return TNMF_E_NULL;
+    if (n_events > 0 && f.g.N > 0 && (!W_eff || !events || !strength || !V || !R || !gain)) return TNMF_E_NULL;
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
-    return events_gain(ctx, g, geom->dtype, mode, S[0], S[1], W_eff, events, strength, n_events, V, R, gain, mag,
+    return events_gain(ctx, f, geom->dtype, W_eff, events, strength, n_events, V, R, gain, mag,
                        static_cast<hipStream_t>(stream));
 }
 
 int tnmf_hip_events_grad_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const int *events, const int *by_plane,
                            const int *plane_start, const void *strength, long long n_events, const void *V, const void *R,
                            void *workspace, void *negpos_eff, void *stream) {
-    EventGeo g;
-    int S[2];
-    const int rc = events_enter(ctx, geom, mode, &g, S);
+    EventFrame f;
+    const int rc = events_enter(ctx, geom, mode, &f);
     if (rc != TNMF_OK) return rc;
     if (n_events < 0) return TNMF_E_GEOM;
     if (n_events > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
     if (!negpos_eff) return TNMF_E_NULL;
-    if (n_events > 0 && g.N > 0 && (!events || !by_plane || !plane_start || !strength || !V || !R || !workspace))
+    if (n_events > 0 && f.g.N > 0 && (!events || !by_plane || !plane_start || !strength || !V || !R || !workspace))
         return TNMF_E_NULL;
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
-    return events_grad_W(ctx, g, geom->dtype, mode, S[0], S[1], events, by_plane, plane_start, strength, n_events, V, R,
+    return events_grad_W(ctx, f, geom->dtype, events, by_plane, plane_start, strength, n_events, V, R,
                          workspace, negpos_eff, static_cast<hipStream_t>(stream));
 }
 
 int tnmf_hip_events_norms(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, double *b,
                           void *stream) {
-    EventGeo g;
-    int S[2];
-    const int rc = events_enter(ctx, geom, mode, &g, S);
+    EventFrame f;
+    const int rc = events_enter(ctx, geom, mode, &f);
     if (rc != TNMF_OK) return rc;
-    if ((long long)S[0] * S[1] > 0x7fffffffLL || g.P > 65535) return TNMF_E_UNSUPPORTED;
+    if ((long long)f.Sy * f.Sx > 0x7fffffffLL || f.g.P > 65535) return TNMF_E_UNSUPPORTED;
     if (!W_eff || !b) return TNMF_E_NULL;
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
-    return events_norms(ctx, g, geom->dtype, mode, S[0], S[1], W_eff, b, static_cast<hipStream_t>(stream));
+    return events_norms(ctx, f, geom->dtype, W_eff, b, static_cast<hipStream_t>(stream));
 }
 
 int tnmf_hip_pursuit_score(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *a, const double *b, void *gain_out,
@@ -1490,47 +1487,44 @@ int tnmf_hip_pursuit_score(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const v
 int tnmf_hip_pursuit_pick(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const long long *idx,
                           long long n_picked, const void *V, const void *R, int *events_out, void *strength_out,
                           double *gain_out, double *mag_out, void *stream) {
-    EventGeo g;
-    int S[2];
-    const int rc = events_enter(ctx, geom, mode, &g, S);
+    EventFrame f;
+    const int rc = events_enter(ctx, geom, mode, &f);
     if (rc != TNMF_OK) return rc;
     if (n_picked < 0) return TNMF_E_GEOM;
-    if (n_picked > 0x7fffffffLL || (long long)S[0] * S[1] > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
-    if (n_picked > 0 && (!idx || !events_out || !strength_out || !gain_out || (g.N > 0 && (!W_eff || !V || !R))))
+    if (n_picked > 0x7fffffffLL || (long long)f.Sy * f.Sx > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
+    if (n_picked > 0 && (!idx || !events_out || !strength_out || !gain_out || (f.g.N > 0 && (!W_eff || !V || !R))))
         return TNMF_E_NULL;
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
-    return pursuit_pick(ctx, g, geom->dtype, mode, S[0], S[1], W_eff, idx, n_picked, V, R, events_out, strength_out,
+    return pursuit_pick(ctx, f, geom->dtype, W_eff, idx, n_picked, V, R, events_out, strength_out,
                         gain_out, mag_out, static_cast<hipStream_t>(stream));
 }
 
 int tnmf_hip_events_landscape(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,
                               const void *strength, long long n_events, const void *V, const void *R, double *a_out,
                               double *b_out, double *mag_out, void *stream) {
-    EventGeo g;
-    int S[2];
-    const int rc = events_enter(ctx, geom, mode, &g, S);
+    EventFrame f;
+    const int rc = events_enter(ctx, geom, mode, &f);
     if (rc != TNMF_OK) return rc;
     if (n_events < 0) return TNMF_E_GEOM;
     if (n_events > 0x7fffffffLL / 9) return TNMF_E_UNSUPPORTED;
-    if (n_events > 0 && g.N > 0 && (!W_eff || !events || !strength || !V || !R || !a_out || !b_out)) return TNMF_E_NULL;
+    if (n_events > 0 && f.g.N > 0 && (!W_eff || !events || !strength || !V || !R || !a_out || !b_out)) return TNMF_E_NULL;
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
-    return events_landscape(ctx, g, geom->ndim, geom->dtype, mode, S[0], S[1], W_eff, events, strength, n_events, V, R,
+    return events_landscape(ctx, f, geom->ndim, geom->dtype, W_eff, events, strength, n_events, V, R,
                             a_out, b_out, mag_out, static_cast<hipStream_t>(stream));
 }
 
 int tnmf_hip_events_alternatives(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff,
                                  const int *events, const void *strength, long long n_events, const void *V, const void *R,
                                  int n_alt, int stride, double *a_out, double *b_out, double *mag_out, void *stream) {
-    EventGeo g;
-    int S[2];
-    const int rc = events_enter(ctx, geom, mode, &g, S);
+    EventFrame f;
+    const int rc = events_enter(ctx, geom, mode, &f);
     if (rc != TNMF_OK) return rc;
     if (n_events < 0 || n_alt < 1 || stride < 1) return TNMF_E_GEOM;
-    if ((long long)n_alt * stride > g.P || g.P % (n_alt * stride) != 0) return TNMF_E_GEOM;
+    if ((long long)n_alt * stride > f.g.P || f.g.P % (n_alt * stride) != 0) return TNMF_E_GEOM;
     if (n_events > 0x7fffffffLL / n_alt) return TNMF_E_UNSUPPORTED;
-    if (n_events > 0 && g.N > 0 && (!W_eff || !events || !strength || !V || !R || !a_out || !b_out)) return TNMF_E_NULL;
+    if (n_events > 0 && f.g.N > 0 && (!W_eff || !events || !strength || !V || !R || !a_out || !b_out)) return TNMF_E_NULL;
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
-    return events_alternatives(ctx, g, geom->dtype, mode, S[0], S[1], W_eff, events, strength, n_events, V, R, n_alt,
+    return events_alternatives(ctx, f, geom->dtype, W_eff, events, strength, n_events, V, R, n_alt,
                                stride, a_out, b_out, mag_out, static_cast<hipStream_t>(stream));
 }
 
@@ -1553,30 +1547,27 @@ int tnmf_hip_events_pairs(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const in
 int tnmf_hip_events_gram(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,
                          long long n_events, const int *row_i, const int *row_j, long long n_pairs, double *val_out,
                          void *stream) {
-    EventGeo g;
-    int S[2];
-    const int rc = events_enter(ctx, geom, mode, &g, S);
+    EventFrame f;
+    const int rc = events_enter(ctx, geom, mode, &f);
     if (rc != TNMF_OK) return rc;
     if (n_events < 0 || n_pairs < 0) return TNMF_E_GEOM;
     if (n_events > 0x7fffffffLL || n_pairs > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
     if (n_pairs > 0 && (!row_i || !row_j || !val_out || (n_events > 0 && (!W_eff || !events)))) return TNMF_E_NULL;
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
-    return events_gram(ctx, g, geom->dtype, mode, S[0], S[1], W_eff, events, n_events, row_i, row_j, n_pairs, val_out,
+    return events_gram(ctx, f, geom->dtype, W_eff, events, n_events, row_i, row_j, n_pairs, val_out,
                        static_cast<hipStream_t>(stream));
 }
 
 int tnmf_hip_events_project(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,
                             long long n_events, const void *V, double *c_out, void *stream) {
-    EventGeo g;
-    int S[2];
-    const int rc = events_enter(ctx, geom, mode, &g, S);
+    EventFrame f;
+    const int rc = events_enter(ctx, geom, mode, &f);
     if (rc != TNMF_OK) return rc;
     if (n_events < 0) return TNMF_E_GEOM;
     if (n_events > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
-    if (n_events > 0 && (!events || !c_out || (g.N > 0 && (!W_eff || !V)))) return TNMF_E_NULL;
+    if (n_events > 0 && (!events || !c_out || (f.g.N > 0 && (!W_eff || !V)))) return TNMF_E_NULL;
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
-    return events_project(ctx, g, geom->dtype, mode, S[0], S[1], W_eff, events, n_events, V, c_out,
-                          static_cast<hipStream_t>(stream));
+    return events_project(ctx, f, geom->dtype, W_eff, events, n_events, V, c_out, static_cast<hipStream_t>(stream));
 }
 
 int tnmf_hip_events_nnls(tnmf_hip_ctx *ctx, long long n_rows, long long nnz, const int *row_start, const int *col,

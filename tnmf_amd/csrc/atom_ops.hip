@@ -332,12 +332,10 @@ int tnmf_hip_ops_expand_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const tn
     fft_invalidate_W(ctx);   // (W_eff: a fixed address with new contents -- its cached spectra are stale)
     const Tables tb = tables_of(ops);
     const int n = d.M * tb.T * d.C * tb.nA;
-    if (geom->dtype == 0)
-        hipLaunchKernelGGL(k_ops_expand<float>, dim3(grid_of(n)), dim3(kBlock), 0, s, tb, d, (const float *)W,
-                           (float *)W_eff);
-    else
-        hipLaunchKernelGGL(k_ops_expand<double>, dim3(grid_of(n)), dim3(kBlock), 0, s, tb, d, (const double *)W,
-                           (double *)W_eff);
+    with_dtype(geom->dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_ops_expand<T>, dim3(grid_of(n)), dim3(kBlock), 0, s, tb, d, (const T *)W, (T *)W_eff);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
@@ -352,12 +350,10 @@ int tnmf_hip_ops_fold_grad_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Tables tb = tables_of(ops);
     const int n = 2 * d.M * d.C * tb.nA;
-    if (geom->dtype == 0)
-        hipLaunchKernelGGL(k_ops_fold<float>, dim3(grid_of(n)), dim3(kBlock), 0, s, tb, d, (const float *)negpos_eff,
-                           (float *)negpos);
-    else
-        hipLaunchKernelGGL(k_ops_fold<double>, dim3(grid_of(n)), dim3(kBlock), 0, s, tb, d, (const double *)negpos_eff,
-                           (double *)negpos);
+    with_dtype(geom->dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_ops_fold<T>, dim3(grid_of(n)), dim3(kBlock), 0, s, tb, d, (const T *)negpos_eff, (T *)negpos);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
@@ -368,16 +364,16 @@ int tnmf_hip_ops_apply_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const tnm
     Dict d;
     CHECK_RC(to_dict(ctx, geom, ops, &d));
     if (!W_inout || !W_eff_out || !negpos_eff) return TNMF_E_NULL;
-    const size_t lds = (size_t)ops->nA * (geom->dtype == 0 ? sizeof(float) : sizeof(double));
+    const size_t lds = (size_t)ops->nA * esize(geom->dtype);
     if (lds > kMaxLdsBytes) return TNMF_E_GEOM;   // (a row larger than the LDS staging)
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     fft_invalidate_W(ctx);
     const Tables tb = tables_of(ops);
-    if (geom->dtype == 0)
-        launch_apply<float>(s, tb, d, (float *)W_inout, (float *)W_eff_out, (const float *)negpos_eff, (float)eps);
-    else
-        launch_apply<double>(s, tb, d, (double *)W_inout, (double *)W_eff_out, (const double *)negpos_eff, eps);
+    with_dtype(geom->dtype, [&](auto zero) {
+        using T = decltype(zero);
+        launch_apply<T>(s, tb, d, (T *)W_inout, (T *)W_eff_out, (const T *)negpos_eff, (T)eps);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }

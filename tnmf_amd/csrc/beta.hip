@@ -331,16 +331,15 @@ void objective_typed(bool vec, double beta, double eps, const void *V, const voi
 int launch_beta_fields(const tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *G,
                        const void *R, void *Q, void *P, size_t n, hipStream_t s) {
     if (n == 0) return TNMF_OK;
-    return dtype == 0 ? fields_typed<float>(ctx, beta, eps, V, G, R, Q, P, n, s)
-                      : fields_typed<double>(ctx, beta, eps, V, G, R, Q, P, n, s);
+    return with_dtype(dtype, [&](auto zero) { return fields_typed<decltype(zero)>(ctx, beta, eps, V, G, R, Q, P, n, s); });
 }
 
 int launch_beta_energy(const tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *G,
                        const void *R, size_t n, double *partials, double *out_dev, hipStream_t s) {
     int grid = grid_of(n, ctx);
     if (grid > kBetaPartials) grid = kBetaPartials;
-    const int rc = dtype == 0 ? energy_typed<float>(beta, eps, V, G, R, n, partials, grid, s)
-                              : energy_typed<double>(beta, eps, V, G, R, n, partials, grid, s);
+    const int rc = with_dtype(
+        dtype, [&](auto zero) { return energy_typed<decltype(zero)>(beta, eps, V, G, R, n, partials, grid, s); });
     if (rc != TNMF_OK) return rc;
     hipLaunchKernelGGL(k_beta_sum, dim3(1), dim3(kBlock), 0, s, partials, grid, out_dev);
     TNMF_LAUNCH_CHECK();
@@ -357,17 +356,14 @@ int launch_sample_objective(int dtype, double beta, double eps, const void *V, c
     const size_t B = objective_blocks(L);
     if (N * B > 0x7fffffffu) return TNMF_E_GEOM;   // (one block index per (sample, block))
     // whole, aligned vectors: 16-byte aligned bases and samples that are a whole number of vectors (kObjChunk is one)
-    const size_t es = dtype == 0 ? 4 : 8;
     const bool vec = ((reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(G) | reinterpret_cast<uintptr_t>(R)) & 15) == 0 &&
-                     (L * es) % 16 == 0;
+                     (L * esize(dtype)) % 16 == 0;
     double *dst = B == 1 ? out : partials;
-    if (dtype == 0) {
-        if (G) objective_typed<float, true>(vec, beta, eps, V, G, R, L, (unsigned)B, (unsigned)(N * B), dst, s);
-        else objective_typed<float, false>(vec, beta, eps, V, G, R, L, (unsigned)B, (unsigned)(N * B), dst, s);
-    } else {
-        if (G) objective_typed<double, true>(vec, beta, eps, V, G, R, L, (unsigned)B, (unsigned)(N * B), dst, s);
-        else objective_typed<double, false>(vec, beta, eps, V, G, R, L, (unsigned)B, (unsigned)(N * B), dst, s);
-    }
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        if (G) objective_typed<T, true>(vec, beta, eps, V, G, R, L, (unsigned)B, (unsigned)(N * B), dst, s);
+        else objective_typed<T, false>(vec, beta, eps, V, G, R, L, (unsigned)B, (unsigned)(N * B), dst, s);
+    });
     TNMF_LAUNCH_CHECK();
     if (B > 1) {
         hipLaunchKernelGGL(k_objective_finish, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, partials, N,

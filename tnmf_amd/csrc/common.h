@@ -117,3 +117,13 @@ static inline const char *tnmf_diag_env(const char *) { return nullptr; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// f(T{}) with T the element type of `dtype` (0: float, 1: double; checked by the entry points); returns what f returns.
+// Every launcher reaches its <float> / <double> kernels through this: `using T = decltype(zero);` in a generic lambda.
+// (The instantiations appear in the object in the order the host code names them: DESIGN.md 4v.)
+template <typename F>
+static inline decltype(auto) with_dtype(int dtype, F &&f) {
+    if (dtype == 0) return f(float{});
+    return f(double{});
+}
+static inline size_t esize(int dtype) { return dtype == 0 ? 4 : 8; }
+

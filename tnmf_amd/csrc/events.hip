@@ -307,10 +307,6 @@ __global__ __launch_bounds__(kEventThreads) void k_events_grad_W_sum(int P, int 
     negpos[((size_t)P + p) * taps + t] = (T)pos;
 }
 
-unsigned grid_for(const tnmf_hip_ctx *ctx, long long blocks) {
-    return (unsigned)std::max<long long>(1, std::min<long long>(blocks, (long long)ctx->num_cu * 64));
-}
-
 }  // namespace
 
 int events_render(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, const void *W, const int *images, long long n_images,
@@ -319,80 +315,67 @@ int events_render(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, const void *W
     int tx_log = 0;
     while ((1 << tx_log) < g.tx) ++tx_log;
     const int nty = cdiv(g.Dy, g.ty), ntx = cdiv(g.Dx, g.tx);
-    const unsigned grid = grid_for(ctx, (long long)g.N * nty * ntx);
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_events_render<float>, dim3(grid), dim3(kEventThreads), 0, s, g, tx_log, nty, ntx,
-                           (const float *)W, (const int4 *)images, (int)n_images, cell_start, (const float *)strength,
-                           (int)n_events, (float *)R);
-    else
-        hipLaunchKernelGGL(k_events_render<double>, dim3(grid), dim3(kEventThreads), 0, s, g, tx_log, nty, ntx,
-                           (const double *)W, (const int4 *)images, (int)n_images, cell_start, (const double *)strength,
-                           (int)n_events, (double *)R);
+    const unsigned grid = events_grid(ctx, (long long)g.N * nty * ntx);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_events_render<T>, dim3(grid), dim3(kEventThreads), 0, s, g, tx_log, nty, ntx, (const T *)W,
+                           (const int4 *)images, (int)n_images, cell_start, (const T *)strength, (int)n_events, (T *)R);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
 
-int events_update(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const void *W,
-                  const int *events, void *strength, long long n_events, const void *V, const void *R, double reg,
-                  hipStream_t s) {
-    if (n_events <= 0 || g.N <= 0) return TNMF_OK;
-    const unsigned grid = grid_for(ctx, (n_events + kWaves - 1) / kWaves);
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_events_update<float>, dim3(grid), dim3(kEventThreads), 0, s, g, mode, Sy, Sx,
-                           (const float *)W, (const int4 *)events, (float *)strength, n_events, (const float *)V,
-                           (const float *)R, reg);
-    else
-        hipLaunchKernelGGL(k_events_update<double>, dim3(grid), dim3(kEventThreads), 0, s, g, mode, Sy, Sx,
-                           (const double *)W, (const int4 *)events, (double *)strength, n_events, (const double *)V,
-                           (const double *)R, reg);
+int events_update(tnmf_hip_ctx *ctx, const EventFrame &f, int dtype, const void *W, const int *events, void *strength,
+                  long long n_events, const void *V, const void *R, double reg, hipStream_t s) {
+    if (n_events <= 0 || f.g.N <= 0) return TNMF_OK;
+    const unsigned grid = events_grid(ctx, (n_events + kWaves - 1) / kWaves);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_events_update<T>, dim3(grid), dim3(kEventThreads), 0, s, f.g, f.mode, f.Sy, f.Sx, (const T *)W,
+                           (const int4 *)events, (T *)strength, n_events, (const T *)V, (const T *)R, reg);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
 
-int events_gain(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const void *W, const int *events,
-                const void *strength, long long n_events, const void *V, const void *R, double *gain, double *mag,
-                hipStream_t s) {
-    if (n_events <= 0 || g.N <= 0) return TNMF_OK;
-    const unsigned grid = grid_for(ctx, (n_events + kWaves - 1) / kWaves);
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_events_gain<float>, dim3(grid), dim3(kEventThreads), 0, s, g, mode, Sy, Sx, (const float *)W,
-                           (const int4 *)events, (const float *)strength, n_events, (const float *)V, (const float *)R,
-                           gain, mag);
-    else
-        hipLaunchKernelGGL(k_events_gain<double>, dim3(grid), dim3(kEventThreads), 0, s, g, mode, Sy, Sx,
-                           (const double *)W, (const int4 *)events, (const double *)strength, n_events,
-                           (const double *)V, (const double *)R, gain, mag);
+int events_gain(tnmf_hip_ctx *ctx, const EventFrame &f, int dtype, const void *W, const int *events, const void *strength,
+                long long n_events, const void *V, const void *R, double *gain, double *mag, hipStream_t s) {
+    if (n_events <= 0 || f.g.N <= 0) return TNMF_OK;
+    const unsigned grid = events_grid(ctx, (n_events + kWaves - 1) / kWaves);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_events_gain<T>, dim3(grid), dim3(kEventThreads), 0, s, f.g, f.mode, f.Sy, f.Sx, (const T *)W,
+                           (const int4 *)events, (const T *)strength, n_events, (const T *)V, (const T *)R, gain, mag);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
 
 long long events_grad_W_slabs(long long n_events, int P) { return n_events / TNMF_EVENTS_SEGMENT + P; }
 
-int events_grad_W(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const int *events,
-                  const int *by_plane, const int *plane_start, const void *strength, long long n_events, const void *V,
-                  const void *R, void *workspace, void *negpos, hipStream_t s) {
+int events_grad_W(tnmf_hip_ctx *ctx, const EventFrame &f, int dtype, const int *events, const int *by_plane,
+                  const int *plane_start, const void *strength, long long n_events, const void *V, const void *R,
+                  void *workspace, void *negpos, hipStream_t s) {
+    const EventGeo &g = f.g;
     const int taps = g.C * g.Ay * g.Ax;
     const long long n_slabs = events_grad_W_slabs(n_events, g.P);
     if (n_events > 0 && g.N > 0) {
-        if (dtype == 0)
-            hipLaunchKernelGGL(k_events_grad_W<float>, dim3((unsigned)n_slabs), dim3(kEventThreads), 0, s, g, mode, Sy, Sx,
-                               (const int4 *)events, by_plane, plane_start, (const float *)strength, (int)n_events,
-                               (const float *)V, (const float *)R, (double *)workspace);
-        else
-            hipLaunchKernelGGL(k_events_grad_W<double>, dim3((unsigned)n_slabs), dim3(kEventThreads), 0, s, g, mode, Sy,
-                               Sx, (const int4 *)events, by_plane, plane_start, (const double *)strength, (int)n_events,
-                               (const double *)V, (const double *)R, (double *)workspace);
+        with_dtype(dtype, [&](auto zero) {
+            using T = decltype(zero);
+            hipLaunchKernelGGL(k_events_grad_W<T>, dim3((unsigned)n_slabs), dim3(kEventThreads), 0, s, g, f.mode, f.Sy, f.Sx,
+                               (const int4 *)events, by_plane, plane_start, (const T *)strength, (int)n_events,
+                               (const T *)V, (const T *)R, (double *)workspace);
+        });
         TNMF_LAUNCH_CHECK();
     }
     // (without events or samples no slab exists: K = 0 makes every run empty, whatever plane_start holds)
     const int K = g.N > 0 ? (int)n_events : 0;
     const dim3 grid((unsigned)((long long)cdiv(taps, kEventThreads) * g.P));
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_events_grad_W_sum<float>, grid, dim3(kEventThreads), 0, s, g.P, taps, plane_start, K, n_slabs,
-                           (const double *)workspace, (float *)negpos);
-    else
-        hipLaunchKernelGGL(k_events_grad_W_sum<double>, grid, dim3(kEventThreads), 0, s, g.P, taps, plane_start, K,
-                           n_slabs, (const double *)workspace, (double *)negpos);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_events_grad_W_sum<T>, grid, dim3(kEventThreads), 0, s, g.P, taps, plane_start, K, n_slabs,
+                           (const double *)workspace, (T *)negpos);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }

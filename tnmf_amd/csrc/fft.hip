@@ -305,12 +305,11 @@ int scaled_W(tnmf_hip_ctx *ctx, const Geo &g, const Lay &l, int dtype, const voi
     const int planes = g.M * g.C, n = planes * g.Ay * g.Ax;
     char *wt = at(ctx, l.Wt);
     const size_t half = (size_t)n * (l.csz / 2);
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_fft_prep_W<float>, dim3(cdiv(n, 256)), dim3(256), 0, s, (const float *)W, (float *)wt,
-                           (float *)(wt + half), planes, g.Ay, g.Ax, scale);
-    else
-        hipLaunchKernelGGL(k_fft_prep_W<double>, dim3(cdiv(n, 256)), dim3(256), 0, s, (const double *)W, (double *)wt,
-                           (double *)(wt + half), planes, g.Ay, g.Ax, scale);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_fft_prep_W<T>, dim3(cdiv(n, 256)), dim3(256), 0, s, (const T *)W, (T *)wt, (T *)(wt + half),
+                           planes, g.Ay, g.Ax, scale);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
@@ -322,12 +321,11 @@ int spectra_W(tnmf_hip_ctx *ctx, const Geo &g, const Lay &l, int dtype, const vo
     const double scale = 1.0 / ((double)l.Ly * l.Lx);
     char *wt = at(ctx, l.Wt);
     const size_t half = (size_t)n * (l.csz / 2);
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_fft_prep_W<float>, dim3(cdiv(n, 256)), dim3(256), 0, s, (const float *)W, (float *)wt,
-                           (float *)(wt + half), planes, g.Ay, g.Ax, scale);
-    else
-        hipLaunchKernelGGL(k_fft_prep_W<double>, dim3(cdiv(n, 256)), dim3(256), 0, s, (const double *)W, (double *)wt,
-                           (double *)(wt + half), planes, g.Ay, g.Ax, scale);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_fft_prep_W<T>, dim3(cdiv(n, 256)), dim3(256), 0, s, (const T *)W, (T *)wt, (T *)(wt + half),
+                           planes, g.Ay, g.Ax, scale);
+    });
     TNMF_LAUNCH_CHECK();
     if (plain) CHECK(forward_planes(g, l, dtype, wt, planes, g.Ay, g.Ax, at(ctx, l.TW), at(ctx, l.SW), s));
     if (flipped) CHECK(forward_planes(g, l, dtype, wt + half, planes, g.Ay, g.Ax, at(ctx, l.TW), at(ctx, l.SWf), s));
@@ -335,8 +333,6 @@ int spectra_W(tnmf_hip_ctx *ctx, const Geo &g, const Lay &l, int dtype, const vo
 }
 
 // ---- binding and per-sample validity ---------------------------------------------------------------------------------
-
-inline size_t esz_of(int dtype) { return dtype == 0 ? 4 : 8; }
 
 bool same_shape(const Geo &a, const Geo &b) {
     return a.M == b.M && a.C == b.C && a.Dy == b.Dy && a.Dx == b.Dx && a.Ay == b.Ay && a.Ax == b.Ax && a.Hs == b.Hs;
@@ -366,7 +362,7 @@ struct Slot {
 Slot locate(FftState &f, const Geo &g, int dtype, const void *H, const void *V) {
     Slot sl = {0, false, false};
     if (!f.cache_enabled || !f.bound || dtype != f.dtype || !same_shape(f.geo, g) || g.N <= 0) return sl;
-    const size_t es = esz_of(dtype);
+    const size_t es = esize(dtype);
     const size_t hb = (size_t)g.M * g.Hy * g.Hs * es, vb = (size_t)g.C * g.Dy * g.Dx * es;
     long n0 = -1;
     if (H) {
@@ -854,14 +850,12 @@ int fft_grad_W(tnmf_hip_ctx *ctx, const Geo &g, int dtype, const void *V, const 
         {
             char *out = at(ctx, l.Gs);
             const dim3 grid((unsigned)((count + 63) / 64), 2);
-            if (dtype == 0)
-                hipLaunchKernelGGL(k_fft_sum_groups<float>, grid, dim3(64), 0, s, (const cplx<float> *)at(ctx, l.Gn),
-                                   (const cplx<float> *)at(ctx, l.Gp), (cplx<float> *)out, (cplx<float> *)(out + sbytes),
-                                   count, ngroups, scale);
-            else
-                hipLaunchKernelGGL(k_fft_sum_groups<double>, grid, dim3(64), 0, s, (const cplx<double> *)at(ctx, l.Gn),
-                                   (const cplx<double> *)at(ctx, l.Gp), (cplx<double> *)out,
-                                   (cplx<double> *)(out + sbytes), count, ngroups, scale);
+            with_dtype(dtype, [&](auto zero) {
+                using T = decltype(zero);
+                hipLaunchKernelGGL(k_fft_sum_groups<T>, grid, dim3(64), 0, s, (const cplx<T> *)at(ctx, l.Gn),
+                                   (const cplx<T> *)at(ctx, l.Gp), (cplx<T> *)out, (cplx<T> *)(out + sbytes), count,
+                                   ngroups, scale);
+            });
             TNMF_LAUNCH_CHECK();
         }
         FftArgs b = base_args(g, l);
@@ -884,17 +878,13 @@ int fft_grad_W(tnmf_hip_ctx *ctx, const Geo &g, int dtype, const void *V, const 
     CHECK(l.rowf(kFftRowsInv, dtype, &d, s));
     const int per = g.M * g.C * g.Ay * g.Ax;
     const char *wo = at(ctx, l.Wo);
-    if (dtype == 0) {
-        hipLaunchKernelGGL(k_fft_flip_out<float>, dim3(cdiv(per, 256)), dim3(256), 0, s, (const float *)wo,
-                           (float *)neg, g.M * g.C, g.Ay, g.Ax, nonneg ? 1 : 0);
-        hipLaunchKernelGGL(k_fft_flip_out<float>, dim3(cdiv(per, 256)), dim3(256), 0, s, (const float *)wo + per,
-                           (float *)pos, g.M * g.C, g.Ay, g.Ax, nonneg ? 1 : 0);
-    } else {
-        hipLaunchKernelGGL(k_fft_flip_out<double>, dim3(cdiv(per, 256)), dim3(256), 0, s, (const double *)wo,
-                           (double *)neg, g.M * g.C, g.Ay, g.Ax, nonneg ? 1 : 0);
-        hipLaunchKernelGGL(k_fft_flip_out<double>, dim3(cdiv(per, 256)), dim3(256), 0, s, (const double *)wo + per,
-                           (double *)pos, g.M * g.C, g.Ay, g.Ax, nonneg ? 1 : 0);
-    }
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_fft_flip_out<T>, dim3(cdiv(per, 256)), dim3(256), 0, s, (const T *)wo, (T *)neg, g.M * g.C,
+                           g.Ay, g.Ax, nonneg ? 1 : 0);
+        hipLaunchKernelGGL(k_fft_flip_out<T>, dim3(cdiv(per, 256)), dim3(256), 0, s, (const T *)wo + per, (T *)pos,
+                           g.M * g.C, g.Ay, g.Ax, nonneg ? 1 : 0);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }

@@ -132,19 +132,15 @@ int spectral_contract_R(const Geo &g, int dtype, const void *SH, const void *SW,
 #define SPEC_R(T_, CG_)                                                                                              \
     hipLaunchKernelGGL((k_spec_contract_R<T_, CG_>), grid, dim3(kSpecThreads), 0, s, (const cplx<T_> *)SH,           \
                        (const cplx<T_> *)SW, (cplx<T_> *)SR, g.N, g.M, g.C, plane, KX, KXP, gx, gy, gz)
-#define SPEC_R_T(T_)                 \
-    switch (cg) {                    \
-        case 1: SPEC_R(T_, 1); break; \
-        case 2: SPEC_R(T_, 2); break; \
-        case 3: SPEC_R(T_, 3); break; \
-        default: SPEC_R(T_, 4); break; \
-    }
-    if (dtype == 0) {
-        SPEC_R_T(float)
-    } else {
-        SPEC_R_T(double)
-    }
-#undef SPEC_R_T
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        switch (cg) {
+            case 1: SPEC_R(T, 1); break;
+            case 2: SPEC_R(T, 2); break;
+            case 3: SPEC_R(T, 3); break;
+            default: SPEC_R(T, 4); break;
+        }
+    });
 #undef SPEC_R
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
@@ -162,19 +158,15 @@ int spectral_grad_W(const Geo &g, int dtype, const void *SH, const void *SV, con
     hipLaunchKernelGGL((k_spec_grad_W<T_, CG_>), grid, dim3(kSpecThreads), 0, s, (const cplx<T_> *)SH,               \
                        (const cplx<T_> *)SV, (const cplx<T_> *)SR, (cplx<T_> *)Gn, (cplx<T_> *)Gp, g.N, g.M, g.C,     \
                        plane, ngroups, nper, KX, KXP, gx, gy, gz)
-#define SPEC_G_T(T_)                 \
-    switch (cg) {                    \
-        case 1: SPEC_G(T_, 1); break; \
-        case 2: SPEC_G(T_, 2); break; \
-        case 3: SPEC_G(T_, 3); break; \
-        default: SPEC_G(T_, 4); break; \
-    }
-    if (dtype == 0) {
-        SPEC_G_T(float)
-    } else {
-        SPEC_G_T(double)
-    }
-#undef SPEC_G_T
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        switch (cg) {
+            case 1: SPEC_G(T, 1); break;
+            case 2: SPEC_G(T, 2); break;
+            case 3: SPEC_G(T, 3); break;
+            default: SPEC_G(T, 4); break;
+        }
+    });
 #undef SPEC_G
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;

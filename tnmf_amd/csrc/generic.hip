@@ -868,13 +868,14 @@ int launch_corr_H(const Geo &g, const void *V, const void *R, const void *H, dou
 // ------------------------------------------------------------------------------------------------------------
 int generic_reconstruct(tnmf_hip_ctx *, const Geo &g, int dtype, const void *W, const void *H, void *R,
                         hipStream_t s) {
-    return dtype == 0 ? launch_reconstruct<float>(g, W, H, R, s) : launch_reconstruct<double>(g, W, H, R, s);
+    return with_dtype(dtype, [&](auto zero) { return launch_reconstruct<decltype(zero)>(g, W, H, R, s); });
 }
 
 int generic_corr_W(tnmf_hip_ctx *, const Geo &g, int dtype, const void *V, const void *R, const void *W,
                    void *H_inout, void *neg, void *pos, bool fused, double reg, hipStream_t s, const void *extra) {
-    return dtype == 0 ? launch_corr_W<float>(g, V, R, W, H_inout, neg, pos, fused, reg, s, extra)
-                      : launch_corr_W<double>(g, V, R, W, H_inout, neg, pos, fused, reg, s, extra);
+    return with_dtype(dtype, [&](auto zero) {
+        return launch_corr_W<decltype(zero)>(g, V, R, W, H_inout, neg, pos, fused, reg, s, extra);
+    });
 }
 
 int generic_corr_H_chunks(const tnmf_hip_ctx *ctx, const Geo &g) {
@@ -889,19 +890,17 @@ int generic_corr_H_chunks(const tnmf_hip_ctx *ctx, const Geo &g) {
 
 int generic_corr_H(tnmf_hip_ctx *, const Geo &g, int dtype, const void *V, const void *R, const void *H,
                    double *partials, int P, hipStream_t s) {
-    return dtype == 0 ? launch_corr_H<float>(g, V, R, H, partials, P, s)
-                      : launch_corr_H<double>(g, V, R, H, partials, P, s);
+    return with_dtype(dtype, [&](auto zero) { return launch_corr_H<decltype(zero)>(g, V, R, H, partials, P, s); });
 }
 
 int finalize_corr_H(const Geo &g, int dtype, const double *partials, int P, void *neg, void *pos, hipStream_t s) {
     const int MC = g.M * g.C, nA = g.Ay * g.Ax;
     const int blocks = cdiv(MC * nA, kFinOut);
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_corr_H_finalize<float>, dim3(blocks), dim3(kFinOut * kFinSlices), 0, s, MC, nA, P,
-                           partials, (float *)neg, (float *)pos);
-    else
-        hipLaunchKernelGGL(k_corr_H_finalize<double>, dim3(blocks), dim3(kFinOut * kFinSlices), 0, s, MC, nA, P,
-                           partials, (double *)neg, (double *)pos);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_corr_H_finalize<T>, dim3(blocks), dim3(kFinOut * kFinSlices), 0, s, MC, nA, P, partials,
+                           (T *)neg, (T *)pos);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
@@ -910,12 +909,10 @@ int launch_mu_update(const tnmf_hip_ctx *ctx, int dtype, void *arr, const void *
                      hipStream_t s) {
     if (n == 0) return TNMF_OK;
     const int grid = grid_for(n, ctx);
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_mu_update<float>, dim3(grid), dim3(kBlock), 0, s, (float *)arr, (const float *)neg,
-                           (float *)pos, (float)reg, n);
-    else
-        hipLaunchKernelGGL(k_mu_update<double>, dim3(grid), dim3(kBlock), 0, s, (double *)arr, (const double *)neg,
-                           (double *)pos, reg, n);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_mu_update<T>, dim3(grid), dim3(kBlock), 0, s, (T *)arr, (const T *)neg, (T *)pos, (T)reg, n);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
@@ -924,10 +921,10 @@ int launch_axpby(const tnmf_hip_ctx *ctx, int dtype, void *acc, const void *g, d
                  hipStream_t s) {
     if (n == 0) return TNMF_OK;
     const int grid = grid_for(n, ctx);
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_axpby<float>, dim3(grid), dim3(kBlock), 0, s, (float *)acc, (const float *)g, (float)a, (float)b, n);
-    else
-        hipLaunchKernelGGL(k_axpby<double>, dim3(grid), dim3(kBlock), 0, s, (double *)acc, (const double *)g, a, b, n);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_axpby<T>, dim3(grid), dim3(kBlock), 0, s, (T *)acc, (const T *)g, (T)a, (T)b, n);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
@@ -936,11 +933,10 @@ int launch_sum_parts(const tnmf_hip_ctx *ctx, int dtype, const void *parts, int 
                      hipStream_t s) {
     if (n == 0) return TNMF_OK;
     const int grid = grid_for(n, ctx);
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_sum_parts<float>, dim3(grid), dim3(kBlock), 0, s, (const float *)parts, n_parts, n, (float *)out);
-    else
-        hipLaunchKernelGGL(k_sum_parts<double>, dim3(grid), dim3(kBlock), 0, s, (const double *)parts, n_parts, n,
-                           (double *)out);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_sum_parts<T>, dim3(grid), dim3(kBlock), 0, s, (const T *)parts, n_parts, n, (T *)out);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
@@ -948,21 +944,15 @@ int launch_sum_parts(const tnmf_hip_ctx *ctx, int dtype, const void *parts, int 
 int launch_apply_normalize_W(const Geo &g, int dtype, void *W, const void *neg, void *pos, double eps, bool apply,
                              hipStream_t s) {
     const int nA = g.Ay * g.Ax, rows = g.M * g.C;
-    if (dtype == 0) {
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
         if (apply)
-            hipLaunchKernelGGL((k_apply_normalize_W<float, true>), dim3(rows), dim3(kBlock), 0, s, nA, (float *)W,
-                               (const float *)neg, (float *)pos, (float)eps);
+            hipLaunchKernelGGL((k_apply_normalize_W<T, true>), dim3(rows), dim3(kBlock), 0, s, nA, (T *)W, (const T *)neg,
+                               (T *)pos, (T)eps);
         else
-            hipLaunchKernelGGL((k_apply_normalize_W<float, false>), dim3(rows), dim3(kBlock), 0, s, nA, (float *)W,
-                               (const float *)nullptr, (float *)nullptr, 0.f);
-    } else {
-        if (apply)
-            hipLaunchKernelGGL((k_apply_normalize_W<double, true>), dim3(rows), dim3(kBlock), 0, s, nA, (double *)W,
-                               (const double *)neg, (double *)pos, eps);
-        else
-            hipLaunchKernelGGL((k_apply_normalize_W<double, false>), dim3(rows), dim3(kBlock), 0, s, nA, (double *)W,
-                               (const double *)nullptr, (double *)nullptr, 0.0);
-    }
+            hipLaunchKernelGGL((k_apply_normalize_W<T, false>), dim3(rows), dim3(kBlock), 0, s, nA, (T *)W,
+                               (const T *)nullptr, (T *)nullptr, T(0));
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
@@ -971,12 +961,10 @@ int launch_half_sqdiff(const tnmf_hip_ctx *ctx, int dtype, const void *V, const 
                        double *out_dev, hipStream_t s) {
     int grid = grid_for(n, ctx);
     if (grid > kEnergyPartials) grid = kEnergyPartials;
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_sqdiff_partial<float>, dim3(grid), dim3(kBlock), 0, s, (const float *)V,
-                           (const float *)R, n, partials);
-    else
-        hipLaunchKernelGGL(k_sqdiff_partial<double>, dim3(grid), dim3(kBlock), 0, s, (const double *)V,
-                           (const double *)R, n, partials);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_sqdiff_partial<T>, dim3(grid), dim3(kBlock), 0, s, (const T *)V, (const T *)R, n, partials);
+    });
     TNMF_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(kBlock), 0, s, partials, grid, 0.5, out_dev);
     TNMF_LAUNCH_CHECK();
@@ -991,12 +979,11 @@ int launch_convolve_axis(const tnmf_hip_ctx *ctx, int dtype, const void *in, voi
     const size_t total = rows * (size_t)len * inner;
     if (total == 0) return TNMF_OK;
     const int grid = grid_for(total, ctx);
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_convolve_axis<float>, dim3(grid), dim3(kBlock), 0, s, (const float *)in, (float *)out,
-                           rows, len, inner, taps, ntaps);
-    else
-        hipLaunchKernelGGL(k_convolve_axis<double>, dim3(grid), dim3(kBlock), 0, s, (const double *)in,
-                           (double *)out, rows, len, inner, taps, ntaps);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_convolve_axis<T>, dim3(grid), dim3(kBlock), 0, s, (const T *)in, (T *)out, rows, len, inner,
+                           taps, ntaps);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
@@ -1084,15 +1071,19 @@ int launch_pad_fold(const tnmf_hip_ctx *ctx, const Geo &g, int dtype, int mode, 
     const size_t total = rows * (fold ? (size_t)Sy * Sx : (size_t)g.Hy * g.Hx);
     if (total == 0) return TNMF_OK;
     const int grid = grid_for(total, ctx);
-#define LAUNCH_PF(K_, T_)                                                                                     \
-    hipLaunchKernelGGL(K_<T_>, dim3(grid), dim3(kBlock), 0, s, rows, Sy, Sx, g.Ay, g.Ax, g.Hy, g.Hx, mode,    \
-                       (const T_ *)in, (T_ *)out)
-    if (fold) {
-        if (dtype == 0) LAUNCH_PF(k_fold_H, float); else LAUNCH_PF(k_fold_H, double);
-    } else {
-        if (dtype == 0) LAUNCH_PF(k_pad_H, float); else LAUNCH_PF(k_pad_H, double);
-    }
-#undef LAUNCH_PF
+    // (fold outside: both precisions of k_fold_H come before k_pad_H in the object, as they always have)
+    if (fold)
+        with_dtype(dtype, [&](auto zero) {
+            using T = decltype(zero);
+            hipLaunchKernelGGL(k_fold_H<T>, dim3(grid), dim3(kBlock), 0, s, rows, Sy, Sx, g.Ay, g.Ax, g.Hy, g.Hx, mode,
+                               (const T *)in, (T *)out);
+        });
+    else
+        with_dtype(dtype, [&](auto zero) {
+            using T = decltype(zero);
+            hipLaunchKernelGGL(k_pad_H<T>, dim3(grid), dim3(kBlock), 0, s, rows, Sy, Sx, g.Ay, g.Ax, g.Hy, g.Hx, mode,
+                               (const T *)in, (T *)out);
+        });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
@@ -1128,9 +1119,9 @@ static int schedule_small_max(const Geo &g, const Tile &tR, size_t *lds_small) {
 }
 
 static size_t schedule_lds_any(const Geo &g, int dtype, const Tile &tR, const Tile &tW, const Tile &tH, int *small_max) {
-    size_t lds = dtype == 0 ? schedule_lds<float>(g, tR, tW, tH) : schedule_lds<double>(g, tR, tW, tH);
+    size_t lds = with_dtype(dtype, [&](auto zero) { return schedule_lds<decltype(zero)>(g, tR, tW, tH); });
     size_t ls = 0;
-    *small_max = dtype == 0 ? schedule_small_max<float>(g, tR, &ls) : schedule_small_max<double>(g, tR, &ls);
+    *small_max = with_dtype(dtype, [&](auto zero) { return schedule_small_max<decltype(zero)>(g, tR, &ls); });
     if (*small_max > 0 && ls > lds) lds = ls;
     return lds;
 }
@@ -1148,8 +1139,9 @@ bool generic_schedule_fits(const tnmf_hip_ctx *, const Geo &g, int dtype) {
 // kernel's real register / LDS footprint), not an assumption about "one workgroup of <= 64 KB per CU".  0: not even one.
 static int schedule_grid(const tnmf_hip_ctx *ctx, int dtype, size_t lds) {
     int per_cu = 0;
-    const hipError_t e = dtype == 0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_schedule<float>, kBlock, lds)
-                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_schedule<double>, kBlock, lds);
+    const hipError_t e = with_dtype(dtype, [&](auto zero) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_schedule<decltype(zero)>, kBlock, lds);
+    });
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return 0;
@@ -1193,7 +1185,7 @@ int generic_run_schedule(tnmf_hip_ctx *ctx, const Geo &g, int dtype, const void 
     const int grid = schedule_grid(ctx, dtype, lds);
     if (grid < 1) return TNMF_E_UNSUPPORTED;   // (nothing launched, nothing written: the caller walks the list per operation)
     TNMF_HIP_TRY(hipMemsetAsync(counter, 0, 64 * sizeof(unsigned), s));
-    const void *fn = dtype == 0 ? (const void *)k_schedule<float> : (const void *)k_schedule<double>;
+    const void *fn = with_dtype(dtype, [](auto zero) { return (const void *)k_schedule<decltype(zero)>; });
     void *params[] = {&a};
     if (ctx->persistent == 2) {
         // cooperative launch: the runtime refuses a grid it cannot make co-resident instead of starting it
@@ -1212,12 +1204,11 @@ int generic_run_schedule(tnmf_hip_ctx *ctx, const Geo &g, int dtype, const void 
 int launch_finalize_blend_apply(const Geo &g, int dtype, const double *partials, int P, void *acc, double a, double b,
                                 bool apply, void *W, double eps, hipStream_t s) {
     const int MC = g.M * g.C, nA = g.Ay * g.Ax;
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_finalize_blend_apply<float>, dim3(MC), dim3(kBlock), 0, s, MC, nA, P, partials, (float *)acc,
-                           (float)a, (float)b, apply ? 1 : 0, (float *)W, (float)eps);
-    else
-        hipLaunchKernelGGL(k_finalize_blend_apply<double>, dim3(MC), dim3(kBlock), 0, s, MC, nA, P, partials, (double *)acc,
-                           a, b, apply ? 1 : 0, (double *)W, eps);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_finalize_blend_apply<T>, dim3(MC), dim3(kBlock), 0, s, MC, nA, P, partials, (T *)acc, (T)a,
+                           (T)b, apply ? 1 : 0, (T *)W, (T)eps);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }

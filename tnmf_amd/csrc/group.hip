@@ -167,12 +167,10 @@ int tnmf_hip_group_expand_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int gr
     hipStream_t s = static_cast<hipStream_t>(stream);
     fft_invalidate_W(ctx);   // (W_eff: a fixed address with new contents -- its cached spectra are stale)
     const int n = d.M * grp.T * d.C * d.Ay * d.Ax;
-    if (geom->dtype == 0)
-        hipLaunchKernelGGL(k_group_expand<float>, dim3(grid_of(n)), dim3(kBlock), 0, s, grp, d, (const float *)W,
-                           (float *)W_eff);
-    else
-        hipLaunchKernelGGL(k_group_expand<double>, dim3(grid_of(n)), dim3(kBlock), 0, s, grp, d, (const double *)W,
-                           (double *)W_eff);
+    with_dtype(geom->dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_group_expand<T>, dim3(grid_of(n)), dim3(kBlock), 0, s, grp, d, (const T *)W, (T *)W_eff);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
@@ -187,12 +185,11 @@ int tnmf_hip_group_fold_grad_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int n = 2 * d.M * d.C * d.Ay * d.Ax;
-    if (geom->dtype == 0)
-        hipLaunchKernelGGL(k_group_fold<float>, dim3(grid_of(n)), dim3(kBlock), 0, s, grp, d,
-                           (const float *)negpos_eff, (float *)negpos);
-    else
-        hipLaunchKernelGGL(k_group_fold<double>, dim3(grid_of(n)), dim3(kBlock), 0, s, grp, d,
-                           (const double *)negpos_eff, (double *)negpos);
+    with_dtype(geom->dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_group_fold<T>, dim3(grid_of(n)), dim3(kBlock), 0, s, grp, d, (const T *)negpos_eff,
+                           (T *)negpos);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
@@ -208,12 +205,11 @@ int tnmf_hip_group_apply_W(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int gro
     hipStream_t s = static_cast<hipStream_t>(stream);
     fft_invalidate_W(ctx);
     const int rows = d.M * d.C;
-    if (geom->dtype == 0)
-        hipLaunchKernelGGL(k_group_apply<float>, dim3(rows), dim3(kBlock), 0, s, grp, d, (float *)W_inout,
-                           (float *)W_eff_out, (const float *)negpos_eff, (float)eps);
-    else
-        hipLaunchKernelGGL(k_group_apply<double>, dim3(rows), dim3(kBlock), 0, s, grp, d, (double *)W_inout,
-                           (double *)W_eff_out, (const double *)negpos_eff, eps);
+    with_dtype(geom->dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_group_apply<T>, dim3(rows), dim3(kBlock), 0, s, grp, d, (T *)W_inout, (T *)W_eff_out,
+                           (const T *)negpos_eff, (T)eps);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }

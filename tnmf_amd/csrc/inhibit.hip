@@ -350,8 +350,9 @@ int launch_inhibition(const tnmf_hip_ctx *, int dtype, int N, int M, int Hy, int
                       hipStream_t s) {
     if (ly < 1 || lx < 1 || ly > kMaxTaps || lx > kMaxTaps || !(ly & 1) || !(lx & 1)) return TNMF_E_UNSUPPORTED;
     if (N <= 0) return TNMF_OK;
-    return dtype == 0 ? launch_inhibition_t<float>(N, M, Hy, ld, H, E, ky_host, ly, kx_host, lx, inh, xc, s)
-                      : launch_inhibition_t<double>(N, M, Hy, ld, H, E, ky_host, ly, kx_host, lx, inh, xc, s);
+    return with_dtype(dtype, [&](auto zero) {
+        return launch_inhibition_t<decltype(zero)>(N, M, Hy, ld, H, E, ky_host, ly, kx_host, lx, inh, xc, s);
+    });
 }
 
 int launch_mu_update_extra(const tnmf_hip_ctx *ctx, int dtype, void *H, const void *neg, const void *pos, const void *E,
@@ -359,12 +360,11 @@ int launch_mu_update_extra(const tnmf_hip_ctx *ctx, int dtype, void *H, const vo
     const size_t total = rows * (size_t)Hx;
     if (total == 0) return TNMF_OK;
     const int grid = grid_cap(total, ctx);
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_mu_update_extra<float>, dim3(grid), dim3(kThreads), 0, s, (float *)H, (const float *)neg,
-                           (const float *)pos, (const float *)E, rows, Hx, ld, (float)reg);
-    else
-        hipLaunchKernelGGL(k_mu_update_extra<double>, dim3(grid), dim3(kThreads), 0, s, (double *)H, (const double *)neg,
-                           (const double *)pos, (const double *)E, rows, Hx, ld, reg);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_mu_update_extra<T>, dim3(grid), dim3(kThreads), 0, s, (T *)H, (const T *)neg, (const T *)pos,
+                           (const T *)E, rows, Hx, ld, (T)reg);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
@@ -374,12 +374,11 @@ int launch_fold_update(const tnmf_hip_ctx *ctx, const Geo &g, int dtype, int mod
     const size_t rows = (size_t)g.N * g.M, total = rows * (size_t)Sy * Sx;
     if (total == 0) return TNMF_OK;
     const int grid = grid_cap(total, ctx);
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_fold_update<float>, dim3(grid), dim3(kThreads), 0, s, rows, Sy, Sx, g.Ay, g.Ax, g.Hy, g.Hx, mode,
-                           (float *)H, (const float *)negp, (const float *)posp, (const float *)E, (float)reg);
-    else
-        hipLaunchKernelGGL(k_fold_update<double>, dim3(grid), dim3(kThreads), 0, s, rows, Sy, Sx, g.Ay, g.Ax, g.Hy, g.Hx,
-                           mode, (double *)H, (const double *)negp, (const double *)posp, (const double *)E, reg);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_fold_update<T>, dim3(grid), dim3(kThreads), 0, s, rows, Sy, Sx, g.Ay, g.Ax, g.Hy, g.Hx, mode,
+                           (T *)H, (const T *)negp, (const T *)posp, (const T *)E, (T)reg);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }

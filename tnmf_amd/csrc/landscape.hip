@@ -175,9 +175,10 @@ __global__ __launch_bounds__(kEventThreads) void k_events_landscape(EventGeo g, 
 
 }  // namespace
 
-int events_landscape(tnmf_hip_ctx *ctx, const EventGeo &g, int ndim, int dtype, int mode, int Sy, int Sx, const void *W,
-                     const int *events, const void *strength, long long n_events, const void *V, const void *R, double *a,
-                     double *b, double *mag, hipStream_t s) {
+int events_landscape(tnmf_hip_ctx *ctx, const EventFrame &f, int ndim, int dtype, const void *W, const int *events,
+                     const void *strength, long long n_events, const void *V, const void *R, double *a, double *b,
+                     double *mag, hipStream_t s) {
+    const EventGeo &g = f.g;
     if (n_events <= 0 || g.N <= 0) return TNMF_OK;
     const int ry = ndim == 2 ? 1 : 0;
     const long long cells = (long long)g.C * (g.Ay + 2 * ry) * (g.Ax + 2);
@@ -188,16 +189,13 @@ int events_landscape(tnmf_hip_ctx *ctx, const EventGeo &g, int ndim, int dtype, 
 #endif
     const int patch = stage && cells <= kPatchMax ? (int)cells : 0;
     const size_t lds = (size_t)kWaves * patch * sizeof(double);
-    const unsigned grid = (unsigned)std::max<long long>(
-        1, std::min<long long>((n_events + kWaves - 1) / kWaves, (long long)ctx->num_cu * TNMF_LANDSCAPE_BLOCKS_PER_CU));
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_events_landscape<float>, dim3(grid), dim3(kEventThreads), lds, s, g, mode, Sy, Sx, ry, patch,
-                           (const float *)W, (const int4 *)events, (const float *)strength, n_events, (const float *)V,
-                           (const float *)R, a, b, mag);
-    else
-        hipLaunchKernelGGL(k_events_landscape<double>, dim3(grid), dim3(kEventThreads), lds, s, g, mode, Sy, Sx, ry, patch,
-                           (const double *)W, (const int4 *)events, (const double *)strength, n_events, (const double *)V,
-                           (const double *)R, a, b, mag);
+    const unsigned grid = events_grid(ctx, (n_events + kWaves - 1) / kWaves, TNMF_LANDSCAPE_BLOCKS_PER_CU);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_events_landscape<T>, dim3(grid), dim3(kEventThreads), lds, s, g, f.mode, f.Sy, f.Sx, ry, patch,
+                           (const T *)W, (const int4 *)events, (const T *)strength, n_events, (const T *)V, (const T *)R, a,
+                           b, mag);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }

@@ -279,10 +279,7 @@ int peaks_find(tnmf_hip_ctx *ctx, const PeakGeo &g, int dtype, const void *H, do
                void *val, size_t capacity, unsigned long long *count, hipStream_t s) {
     TNMF_HIP_TRY(hipMemsetAsync(count, 0, sizeof(unsigned long long), s));
     if (g.planes <= 0) return TNMF_OK;
-    if (dtype == 0)
-        launch<float>(ctx, g, H, threshold, idx, val, capacity, count, s);
-    else
-        launch<double>(ctx, g, H, threshold, idx, val, capacity, count, s);
+    with_dtype(dtype, [&](auto zero) { launch<decltype(zero)>(ctx, g, H, threshold, idx, val, capacity, count, s); });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }

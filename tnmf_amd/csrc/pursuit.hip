@@ -168,22 +168,17 @@ __global__ __launch_bounds__(kEventThreads) void k_pursuit_pick(EventGeo g, int 
     }
 }
 
-unsigned grid_for(const tnmf_hip_ctx *ctx, long long blocks, int per_cu) {
-    return (unsigned)std::max<long long>(1, std::min<long long>(blocks, (long long)ctx->num_cu * per_cu));
-}
-
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
-int events_norms(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const void *W, double *b,
-                 hipStream_t s) {
-    const int entries = Sy * Sx;
-    const dim3 grid(grid_for(ctx, cdiv(entries, kEventThreads), 8), (unsigned)g.P);
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_events_norms<float>, grid, dim3(kEventThreads), 0, s, g, mode, Sy, Sx, (const float *)W, b);
-    else
-        hipLaunchKernelGGL(k_events_norms<double>, grid, dim3(kEventThreads), 0, s, g, mode, Sy, Sx, (const double *)W, b);
+int events_norms(tnmf_hip_ctx *ctx, const EventFrame &f, int dtype, const void *W, double *b, hipStream_t s) {
+    const int entries = f.Sy * f.Sx;
+    const dim3 grid(events_grid(ctx, cdiv(entries, kEventThreads), 8), (unsigned)f.g.P);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_events_norms<T>, grid, dim3(kEventThreads), 0, s, f.g, f.mode, f.Sy, f.Sx, (const T *)W, b);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
@@ -202,7 +197,7 @@ static int pursuit_score_t(tnmf_hip_ctx *ctx, long long planes, int P, int Sy, i
             rows = planes / P, brows = 1, Sx = Hs = (int)per_sample;
         }
         const int cpr = cdiv(Sx, kV);
-        const unsigned grid = grid_for(ctx, (rows * cpr + kEventThreads - 1) / kEventThreads, 8);
+        const unsigned grid = events_grid(ctx, (rows * cpr + kEventThreads - 1) / kEventThreads, 8);
         const bool aligned = aligned16(a) && aligned16(gain) && Hs % kV == 0;
         if (aligned)
             hipLaunchKernelGGL((k_pursuit_score<T, true>), dim3(grid), dim3(kEventThreads), 0, s, rows, brows, Sx, Hs, cpr,
@@ -212,7 +207,7 @@ static int pursuit_score_t(tnmf_hip_ctx *ctx, long long planes, int P, int Sy, i
                                a, b, gain);
         TNMF_LAUNCH_CHECK();
         if (n_taken > 0) {
-            const unsigned tgrid = grid_for(ctx, (n_taken + kEventThreads - 1) / kEventThreads, 8);
+            const unsigned tgrid = events_grid(ctx, (n_taken + kEventThreads - 1) / kEventThreads, 8);
             // (entries = rows * Sx in either view, and a flat index splits into row and column of either alike)
             hipLaunchKernelGGL(k_pursuit_taken<T>, dim3(tgrid), dim3(kEventThreads), 0, s, entries, Sx, Hs, taken, n_taken,
                                gain);
@@ -224,24 +219,22 @@ static int pursuit_score_t(tnmf_hip_ctx *ctx, long long planes, int P, int Sy, i
 
 int pursuit_score(tnmf_hip_ctx *ctx, int dtype, long long planes, int P, int Sy, int Sx, int Hs, const void *a,
                   const double *b, void *gain, const long long *taken, long long n_taken, hipStream_t s) {
-    return dtype == 0 ? pursuit_score_t<float>(ctx, planes, P, Sy, Sx, Hs, (const float *)a, b, (float *)gain, taken,
-                                               n_taken, s)
-                      : pursuit_score_t<double>(ctx, planes, P, Sy, Sx, Hs, (const double *)a, b, (double *)gain, taken,
-                                                n_taken, s);
+    return with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        return pursuit_score_t<T>(ctx, planes, P, Sy, Sx, Hs, (const T *)a, b, (T *)gain, taken, n_taken, s);
+    });
 }
 
-int pursuit_pick(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const void *W,
-                 const long long *idx, long long n_picked, const void *V, const void *R, int *events, void *strength,
-                 double *gain, double *mag, hipStream_t s) {
+int pursuit_pick(tnmf_hip_ctx *ctx, const EventFrame &f, int dtype, const void *W, const long long *idx,
+                 long long n_picked, const void *V, const void *R, int *events, void *strength, double *gain, double *mag,
+                 hipStream_t s) {
     if (n_picked <= 0) return TNMF_OK;
-    const unsigned grid = grid_for(ctx, (n_picked + kWaves - 1) / kWaves, 64);
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_pursuit_pick<float>, dim3(grid), dim3(kEventThreads), 0, s, g, mode, Sy, Sx, (const float *)W,
-                           idx, n_picked, (const float *)V, (const float *)R, (int4 *)events, (float *)strength, gain, mag);
-    else
-        hipLaunchKernelGGL(k_pursuit_pick<double>, dim3(grid), dim3(kEventThreads), 0, s, g, mode, Sy, Sx,
-                           (const double *)W, idx, n_picked, (const double *)V, (const double *)R, (int4 *)events,
-                           (double *)strength, gain, mag);
+    const unsigned grid = events_grid(ctx, (n_picked + kWaves - 1) / kWaves, 64);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_pursuit_pick<T>, dim3(grid), dim3(kEventThreads), 0, s, f.g, f.mode, f.Sy, f.Sx, (const T *)W,
+                           idx, n_picked, (const T *)V, (const T *)R, (int4 *)events, (T *)strength, gain, mag);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }

@@ -12,12 +12,12 @@ int events_pairs(tnmf_hip_ctx *ctx, const EventGeo &g, const int *images, long l
 
 // val[p] = <phi_i, phi_j> for the pair (row_i[p], row_j[p]), in double; 0 for a row outside the contract and for rows of two
 // samples.  Every element is written.
-int events_gram(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const void *W, const int *events,
-                long long n_events, const int *row_i, const int *row_j, long long n_pairs, double *val, hipStream_t s);
+int events_gram(tnmf_hip_ctx *ctx, const EventFrame &f, int dtype, const void *W, const int *events, long long n_events,
+                const int *row_i, const int *row_j, long long n_pairs, double *val, hipStream_t s);
 
 // c[e] = <phi_e, V>, in double; 0 for a row outside the contract.  Every element is written.
-int events_project(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const void *W,
-                   const int *events, long long n_events, const void *V, double *c, hipStream_t s);
+int events_project(tnmf_hip_ctx *ctx, const EventFrame &f, int dtype, const void *W, const int *events, long long n_events,
+                   const void *V, double *c, hipStream_t s);
 
 // min 1/2 h'Gh - c'h over h >= 0 on a CSR matrix, from the start h projected; synchronises the stream at every check.
 // workspace: events_nnls_workspace(K) doubles on the device; iterations, kkt_out, converged, history, n_history on the host.

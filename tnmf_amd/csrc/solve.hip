@@ -289,10 +289,6 @@ __global__ __launch_bounds__(kEventThreads) void k_nnls_reduce(int K, const doub
     }
 }
 
-unsigned grid_for(const tnmf_hip_ctx *ctx, long long blocks) {
-    return (unsigned)std::max<long long>(1, std::min<long long>(blocks, (long long)ctx->num_cu * 64));
-}
-
 }  // namespace
 
 int events_pairs(tnmf_hip_ctx *ctx, const EventGeo &g, const int *images, long long n_images, const int *cell_start,
@@ -300,37 +296,35 @@ int events_pairs(tnmf_hip_ctx *ctx, const EventGeo &g, const int *images, long l
                  hipStream_t s) {
     TNMF_HIP_TRY(hipMemsetAsync(count, 0, sizeof(unsigned long long), s));
     if (n_images <= 0 || n_events <= 0 || g.N <= 0) return TNMF_OK;
-    const unsigned grid = grid_for(ctx, (n_images + kWaves - 1) / kWaves);
+    const unsigned grid = events_grid(ctx, (n_images + kWaves - 1) / kWaves);
     hipLaunchKernelGGL(k_events_pairs, dim3(grid), dim3(kEventThreads), 0, s, g, (const int4 *)images, (int)n_images,
                        cell_start, (const int4 *)events, (int)n_events, pairs, (unsigned long long)capacity, count);
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
 
-int events_gram(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const void *W, const int *events,
-                long long n_events, const int *row_i, const int *row_j, long long n_pairs, double *val, hipStream_t s) {
+int events_gram(tnmf_hip_ctx *ctx, const EventFrame &f, int dtype, const void *W, const int *events, long long n_events,
+                const int *row_i, const int *row_j, long long n_pairs, double *val, hipStream_t s) {
     if (n_pairs <= 0) return TNMF_OK;
-    const unsigned grid = grid_for(ctx, (n_pairs + kWaves - 1) / kWaves);
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_events_gram<float>, dim3(grid), dim3(kEventThreads), 0, s, g, mode, Sy, Sx, (const float *)W,
+    const unsigned grid = events_grid(ctx, (n_pairs + kWaves - 1) / kWaves);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_events_gram<T>, dim3(grid), dim3(kEventThreads), 0, s, f.g, f.mode, f.Sy, f.Sx, (const T *)W,
                            (const int4 *)events, (int)n_events, row_i, row_j, n_pairs, val);
-    else
-        hipLaunchKernelGGL(k_events_gram<double>, dim3(grid), dim3(kEventThreads), 0, s, g, mode, Sy, Sx, (const double *)W,
-                           (const int4 *)events, (int)n_events, row_i, row_j, n_pairs, val);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
 
-int events_project(tnmf_hip_ctx *ctx, const EventGeo &g, int dtype, int mode, int Sy, int Sx, const void *W,
-                   const int *events, long long n_events, const void *V, double *c, hipStream_t s) {
+int events_project(tnmf_hip_ctx *ctx, const EventFrame &f, int dtype, const void *W, const int *events, long long n_events,
+                   const void *V, double *c, hipStream_t s) {
     if (n_events <= 0) return TNMF_OK;
-    const unsigned grid = grid_for(ctx, (n_events + kWaves - 1) / kWaves);
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_events_project<float>, dim3(grid), dim3(kEventThreads), 0, s, g, mode, Sy, Sx,
-                           (const float *)W, (const int4 *)events, n_events, (const float *)V, c);
-    else
-        hipLaunchKernelGGL(k_events_project<double>, dim3(grid), dim3(kEventThreads), 0, s, g, mode, Sy, Sx,
-                           (const double *)W, (const int4 *)events, n_events, (const double *)V, c);
+    const unsigned grid = events_grid(ctx, (n_events + kWaves - 1) / kWaves);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_events_project<T>, dim3(grid), dim3(kEventThreads), 0, s, f.g, f.mode, f.Sy, f.Sx,
+                           (const T *)W, (const int4 *)events, n_events, (const T *)V, c);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }

@@ -255,12 +255,10 @@ int vol_reconstruct(const Vol &v, int dtype, const void *W, const void *H, void 
     if (v.N == 0) return TNMF_OK;
     const int tiles = cdiv(v.D[0] * v.D[1] * v.D[2], kVolBlock);
     const dim3 grid((unsigned)(tiles * v.N * v.C));
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_vol_reconstruct<float>, grid, dim3(kVolBlock), 0, s, v, tiles, (const float *)W,
-                           (const float *)H, (float *)R);
-    else
-        hipLaunchKernelGGL(k_vol_reconstruct<double>, grid, dim3(kVolBlock), 0, s, v, tiles, (const double *)W,
-                           (const double *)H, (double *)R);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_vol_reconstruct<T>, grid, dim3(kVolBlock), 0, s, v, tiles, (const T *)W, (const T *)H, (T *)R);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
@@ -271,17 +269,15 @@ int vol_corr_W(const Vol &v, int dtype, const void *V, const void *R, const void
     if (v.N == 0) return TNMF_OK;
     const int tiles = cdiv(v.H[0] * v.H[1] * v.H[2], kVolBlock);
     const dim3 grid((unsigned)(tiles * v.N * v.M));
-#define VOL_CW(T_, F_)                                                                                              \
-    hipLaunchKernelGGL((k_vol_corr_W<T_, F_>), grid, dim3(kVolBlock), 0, s, v, tiles, (const T_ *)V, (const T_ *)R,   \
-                       (const T_ *)W, (T_ *)Hio, (T_ *)neg, (T_ *)pos, (T_)reg)
-    if (dtype == 0) {
-        if (fused) VOL_CW(float, true);
-        else VOL_CW(float, false);
-    } else {
-        if (fused) VOL_CW(double, true);
-        else VOL_CW(double, false);
-    }
-#undef VOL_CW
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        if (fused)
+            hipLaunchKernelGGL((k_vol_corr_W<T, true>), grid, dim3(kVolBlock), 0, s, v, tiles, (const T *)V, (const T *)R,
+                               (const T *)W, (T *)Hio, (T *)neg, (T *)pos, (T)reg);
+        else
+            hipLaunchKernelGGL((k_vol_corr_W<T, false>), grid, dim3(kVolBlock), 0, s, v, tiles, (const T *)V, (const T *)R,
+                               (const T *)W, (T *)Hio, (T *)neg, (T *)pos, (T)reg);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
@@ -302,17 +298,13 @@ int vol_corr_H(const Vol &v, int dtype, const void *V, const void *R, const void
     if (entries * P > 0x7fffffffL) return TNMF_E_GEOM;
     const dim3 grid((unsigned)(entries * P));   // (an empty slice: every sum is zero)
     const int n = v.M * v.C * v.A[0] * v.A[1] * v.A[2];
-    if (dtype == 0) {
-        hipLaunchKernelGGL(k_vol_corr_H<float>, grid, dim3(kVolBlock), 0, s, v, P, (const float *)V, (const float *)R,
-                           (const float *)H, partials);
-        hipLaunchKernelGGL(k_vol_corr_H_finalize<float>, dim3(cdiv(n, kVolBlock)), dim3(kVolBlock), 0, s, n, P, partials,
-                           (float *)neg, (float *)pos);
-    } else {
-        hipLaunchKernelGGL(k_vol_corr_H<double>, grid, dim3(kVolBlock), 0, s, v, P, (const double *)V, (const double *)R,
-                           (const double *)H, partials);
-        hipLaunchKernelGGL(k_vol_corr_H_finalize<double>, dim3(cdiv(n, kVolBlock)), dim3(kVolBlock), 0, s, n, P, partials,
-                           (double *)neg, (double *)pos);
-    }
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_vol_corr_H<T>, grid, dim3(kVolBlock), 0, s, v, P, (const T *)V, (const T *)R, (const T *)H,
+                           partials);
+        hipLaunchKernelGGL(k_vol_corr_H_finalize<T>, dim3(cdiv(n, kVolBlock)), dim3(kVolBlock), 0, s, n, P, partials,
+                           (T *)neg, (T *)pos);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
@@ -334,20 +326,18 @@ int vol_pad_fold(const tnmf_hip_ctx *ctx, const Vol &v, int dtype, int mode, boo
     const size_t total = planes * (fold ? (size_t)q.S[0] * q.S[1] * q.S[2] : (size_t)q.P[0] * q.P[1] * q.P[2]);
     if (total == 0) return TNMF_OK;
     if (mode == TNMF_MODE_VALID) {   // identity
-        TNMF_HIP_TRY(hipMemcpyAsync(out, in, total * (dtype == 0 ? 4 : 8), hipMemcpyDeviceToDevice, s));
+        TNMF_HIP_TRY(hipMemcpyAsync(out, in, total * esize(dtype), hipMemcpyDeviceToDevice, s));
         return TNMF_OK;
     }
     size_t blocks = (total + kVolBlock - 1) / kVolBlock;
     const size_t cap = (size_t)ctx->num_cu * 32;
     if (blocks > cap) blocks = cap;
     const dim3 grid((unsigned)blocks);
-    if (dtype == 0) {
-        if (fold) hipLaunchKernelGGL(k_vol_fold<float>, grid, dim3(kVolBlock), 0, s, planes, q, mode, (const float *)in, (float *)out);
-        else hipLaunchKernelGGL(k_vol_pad<float>, grid, dim3(kVolBlock), 0, s, planes, q, mode, (const float *)in, (float *)out);
-    } else {
-        if (fold) hipLaunchKernelGGL(k_vol_fold<double>, grid, dim3(kVolBlock), 0, s, planes, q, mode, (const double *)in, (double *)out);
-        else hipLaunchKernelGGL(k_vol_pad<double>, grid, dim3(kVolBlock), 0, s, planes, q, mode, (const double *)in, (double *)out);
-    }
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        if (fold) hipLaunchKernelGGL(k_vol_fold<T>, grid, dim3(kVolBlock), 0, s, planes, q, mode, (const T *)in, (T *)out);
+        else hipLaunchKernelGGL(k_vol_pad<T>, grid, dim3(kVolBlock), 0, s, planes, q, mode, (const T *)in, (T *)out);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
@@ -359,12 +349,11 @@ int vol_lateral(const tnmf_hip_ctx *ctx, int dtype, size_t N, int M, size_t vox,
     size_t blocks = (total + kVolBlock - 1) / kVolBlock;
     const size_t cap = (size_t)ctx->num_cu * 32;
     if (blocks > cap) blocks = cap;
-    if (dtype == 0)
-        hipLaunchKernelGGL(k_vol_lateral<float>, dim3((unsigned)blocks), dim3(kVolBlock), 0, s, N, M, vox, (float *)G,
-                           (const float *)H, (float)inh, (float)xc);
-    else
-        hipLaunchKernelGGL(k_vol_lateral<double>, dim3((unsigned)blocks), dim3(kVolBlock), 0, s, N, M, vox, (double *)G,
-                           (const double *)H, inh, xc);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_vol_lateral<T>, dim3((unsigned)blocks), dim3(kVolBlock), 0, s, N, M, vox, (T *)G,
+                           (const T *)H, (T)inh, (T)xc);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
