@@ -383,6 +383,28 @@ int tnmf_hip_ctx_set_objective_tap(tnmf_hip_ctx *ctx, double *per_sample_dev);
 int tnmf_hip_sample_objective(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, double beta, double eps, const void *V,
                               const void *G_or_null, const void *W, const void *H, double *per_sample_dev, void *stream);
 
+/* ---- atom terms: what each atom explains (ABI 8, additive: the version stays 8) ------------------------------------------
+ * With R_m the contribution of atom m in all its orientations -- the planes m * group + t, t < group, of H and W -- and
+ * d = V - R:   a[n, m] = sum G R_m[n] d[n],   b[n, m] = sum G R_m[n]^2   (G = 1 without weights), so that
+ *   1/2 ||V[n] - (R[n] - R_m[n])||^2 - 1/2 ||V[n] - R[n]||^2 = a[n, m] + b[n, m] / 2     (the weighted norms with G)
+ * in the unit of tnmf_hip_events_gain; 1 + a / b is the optimal rescaling of the atom alone.  One pass over H with the
+ * arithmetic of a reconstruct: r_m[c, x] = sum_{t < group} sum_a Hpad[n, m group + t, x + a] W[m group + t, c, A-1-a] in
+ * the element type (the blocks' planes summed before r is squared), r (G d) and G r^2 accumulated in double, each
+ * workgroup's sums combined in a fixed order (partial sums per (sample, tile, atom), then their ordered sum): no
+ * floating-point atomics, the same bits from run to run.  Entries of weight <= 0 add exactly 0, whatever V holds there. */
+
+/* a, b of every atom: ab[(n*(M/group) + m)*2 + {0,1}] (double, device), for geom->M planes in blocks of `group`
+ * (the T orientations of one atom; group = 1 without transforms).  H: padded activations [N, M, *(D+A-1)], row stride
+ * honoured.  W: the M planes (W, or W_eff).  G_or_null: weights of V's shape and dtype.  R_or_null: reconstruct(W, H);
+ * NULL: computed into the ctx scratch by the ctx's kernel family.  Every element of ab is written.  Asynchronous on the
+ * stream.  The partial sums and a re-ordered copy of W live in a work buffer of the context that the first call allocates
+ * (tnmf_hip_ctx_reserve does not size it).
+ * TNMF_E_GEOM: group < 1 or M % group != 0.  TNMF_E_UNSUPPORTED: ndim == 3, or an atom whose tile of H (16 + A_y - 1
+ * rows of 64 + 4 ceil((A_x + 1) / 4) elements; one shift axis: one row of 1024 + 4 ceil((A + 1) / 4)) exceeds 60 KiB.
+ * A refused call writes nothing. */
+int tnmf_hip_atom_terms(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int group, const void *V, const void *G_or_null,
+                        const void *R_or_null, const void *W, const void *H, double *ab, void *stream);
+
 /* ---- transform groups: rotation and mirror invariance (ABI 8, additive: the version stays 8) -------------------------
  * A dictionary W[M,C,*A] stands for M * T effective atoms W_eff[m*T + t] = T_t(W[m]), every T_t a permutation of the
  * atom's pixels.  The groups, with t in the order below (numpy, a = W[m, c]):

@@ -30,6 +30,7 @@ from typing import Callable, Iterable, Iterator, List, Optional, Tuple, Union
 import numpy as np
 
 from . import transforms as _transforms
+from .atoms_host import atom_terms_numpy
 from .backends._Backend import Backend, sliceNone
 # (the host side of the events; the names stay importable from this module)
 from .events_host import (event_boxes, event_images, events_alternatives_numpy, events_fit_numpy,  # noqa: F401
@@ -227,6 +228,7 @@ class TransformInvariantNMF:
         self._use_schedules = bool(use_fused_updates)   # mini-batch epochs as one backend call where the backend can
         self._iteration_acc = None
         self._weighted = False   # the current fit has weights (set by every fit)
+        self._weights = None
 
         self._W = None
         self._W_eff = None   # with transforms: the M * T effective atoms, expanded from W after every change of W
@@ -1004,6 +1006,51 @@ class TransformInvariantNMF:
         out = np.asarray(hook(self._V, self._W_dict, self._H, beta=self._beta, eps=self.eps), dtype=np.float64)
         return out if self._shuffle_idx is None else out[np.argsort(self._shuffle_idx)]
 
+    def atom_terms(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(a, b), float64 ``[N, n_atoms]``: with ``R_m`` the contribution of atom m (in all its orientations, as
+        ``R_partial(m)``) and ``d = V - R``, ``a[n, m] = <R_m[n], d[n]>`` and ``b[n, m] = ||R_m[n]||^2`` -- after a weighted
+        fit ``sum G R_m d`` and ``sum G R_m^2``.  Without atom m the objective of sample n rises by ``a + b / 2``
+        (``atom_gains``); ``1 + a / b`` is the factor that rescales the atom's activations in that sample best, a
+        diagnostic after a fit under ``sparsity_H``.  Samples in the order of ``H`` (with a process group: this rank's
+        samples, and the call is not collective).  On a backend with ``atom_terms`` one pass over the activations where they
+        live; any other backend's are scored on the host.  The Frobenius objective only; ``W``, ``H`` and ``V`` are not
+        touched."""
+        if self._H is None:
+            raise RuntimeError('the atom gains of a model need a fitted model: call fit first')
+        if self._beta != 2.:
+            raise NotImplementedError('atom_gains covers the Frobenius objective (beta_loss 2), with or without weights')
+        if len(self.atom_shape) == 3:
+            raise NotImplementedError('atom gains: 1 or 2 shift axes only')
+        hook = getattr(self._backend, 'atom_terms', None)
+        if hook is not None:
+            a, b = hook(self._V, self._W_dict, self._H, self.n_transforms)
+        else:
+            G = self._weights
+            if G is not None and len(G) != int(self._H.shape[0]):
+                n0 = int(getattr(self._backend, 'shard', (0, 0))[0])
+                G = G[n0:n0 + int(self._H.shape[0])]
+            a, b = atom_terms_numpy(self._backend.to_ndarray(self._W_dict), self._backend.to_ndarray(self._H),
+                                    getattr(self._backend, '_reconstruction_mode', 'valid'), self._local_V(), G,
+                                    self.n_transforms)
+        a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+        if self._shuffle_idx is not None:
+            order = np.argsort(self._shuffle_idx)
+            a, b = a[order], b[order]
+        return a, b
+
+    def atom_gains(self, per_sample: bool = False) -> np.ndarray:
+        """What each atom explains: the objective of the model without atom m (in all its orientations) minus that of the
+        model, ``1/2 ||V - (R - R_m)||^2 - 1/2 ||V - R||^2 = a + b / 2`` with the terms of ``atom_terms`` -- in the unit of
+        ``detection_gains``, so an atom and a detection compare.  ``[n_atoms]`` float64, summed over the samples, or with
+        ``per_sample=True`` ``[N, n_atoms]`` in the order of ``H``.  Not collective: with a process group each rank reports
+        its own samples and the sum over the ranks is the caller's, as for ``detection_errors``.  The Frobenius objective,
+        with or without weights."""
+        if not isinstance(per_sample, (bool, np.bool_)):
+            raise ValueError(f'per_sample must be a bool, not {per_sample!r}')
+        a, b = self.atom_terms()
+        gain = a + 0.5 * b
+        return gain if per_sample else gain.sum(axis=0)
+
     # -- stopping on the objective ---------------------------------------------------------------------------------
     @staticmethod
     def _convergence_args(objective_every, tol) -> Tuple[Optional[int], Optional[float]]:
@@ -1158,6 +1205,8 @@ class TransformInvariantNMF:
         self._iteration_acc = None    # (sized and typed for the W of ONE fit: a refit may change dtype or device)
         self._objective_buf = None    # (one value per local sample of ONE fit)
         self._weighted = weights is not None
+        # (the host copy, kept only for atom_terms on a backend without the hook)
+        self._weights = weights if getattr(self._backend, 'atom_terms', None) is None else None
         kw = {} if weights is None else {'weights': weights}
         if self._transforms is not None:
             kw['transforms'] = self._transforms

@@ -772,6 +772,27 @@ class HIP_Backend(Backend):
             self._stream()), 'tnmf_hip_sample_objective'))
         return out.cpu().numpy()
 
+    def atom_terms(self, V, W: torch.Tensor, H: torch.Tensor, group: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+        """(a, b), float64 ``[n_local_samples, n_planes / group]`` on the host: what each block of ``group`` planes of W
+        (an atom in all its orientations) explains of the resident samples -- ``a = sum G R_m d``, ``b = sum G R_m^2``
+        with the bound weights G (include/tnmf_hip.h, "atom terms") -> tnmf_hip_atom_terms: one pass over H, and only the
+        two sums per (sample, atom) cross to the host.  The modes other than 'valid' are the 'valid' pass over the padded
+        activations."""
+        if len(self.atom_shape) == 3:
+            raise NotImplementedError('atom gains: 1 or 2 shift axes only')
+        self._check_W(W)
+        self._foreign_H()
+        self._check_H(H, W.shape[0])
+        assert H.shape[0] == self.n_local_samples
+        H = self._pad(H)
+        ab = torch.empty((H.shape[0], W.shape[0] // max(int(group), 1), 2), dtype=torch.float64, device=self._device)
+        self._call_H(H, False, lambda Hc, ld: (self._lib.tnmf_hip_atom_terms(
+            self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)), int(group), _ptr(self._V_dev),
+            None if self._G_dev is None else _ptr(self._G_dev), None, _ptr(W), _ptr(Hc), _ptr(ab), self._stream()),
+            'tnmf_hip_atom_terms'))
+        out = ab.cpu().numpy()
+        return np.ascontiguousarray(out[..., 0]), np.ascontiguousarray(out[..., 1])
+
     # -- detections -----------------------------------------------------------------------------------------------------
     # The peaks of H are found and compacted on the device (include/tnmf_hip.h, "detections"): only the list of
     # (index, value) pairs crosses to the host, never H.

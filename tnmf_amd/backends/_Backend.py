@@ -31,6 +31,10 @@ takes an ``AtomOperators`` (tnmf_amd/transforms.py) wherever those hooks take a 
 objective_out=buf)`` -- passed only on the iterations that record; the step's slice selects the part written, with each
 sample's objective at the (W, H) passed in -- and ``read_objective(buf) -> float``, the only call that waits: the sum in
 sample order, over all ranks.  ``sample_objective(V, W, H, beta, eps)`` -> one float64 per local sample, host side.
+``atom_terms(V, W, H, group) -> (a, b)`` (float64 ``[n_local, n_planes / group]``, host): what each block of ``group``
+planes of W -- an atom in all its orientations -- explains of the local samples under the Frobenius objective, with the
+weights when they are bound (include/tnmf_hip.h, "atom terms"); without it ``atom_terms`` / ``atom_gains`` run
+``atom_terms_numpy`` (tnmf_amd/atoms_host.py) on the host.
 A backend that declares ``supports_peaks`` offers ``find_peaks(H, threshold, radius, group) -> (idx, val)``: the ascending
 flat C-order indices (int64, host) in H's shape [n, P, *S] and the values of the detections of its native H
 (include/tnmf_hip.h, "detections"); without it ``detections()`` searches ``to_ndarray(H)`` on the host.
