@@ -113,6 +113,24 @@ __device__ __forceinline__ void load_rows_merge(cplx<T> *x, const cplx<T> *src, 
     }
 }
 
+// One entry of the row spectra the forward row kernel writes.  Float32 stores carry the non-temporal hint: a launch writes
+// its spectra once and another kernel reads them, at config 3 2.4 GB later, so nothing is gained by keeping the lines --
+// the one hint that moves a two-array copy in this kernel's access shape (tools/probes/rows_copy_probe.hip: 1.03-1.06 ->
+// 0.89-0.90 ms for the 4.9 GB of config 3) takes the long launch on H from 0.99 to 0.91 ms, same-box A/B in
+// profiles/rows_fwd_stream_ab.md.  TNMF_ROWS_FWD_NT=0: the A/B flavour of the library (Makefile: VARIANT) with plain stores.
+#ifndef TNMF_ROWS_FWD_NT
+#define TNMF_ROWS_FWD_NT 1
+#endif
+template <typename T>
+__device__ __forceinline__ void store_spectrum(cplx<T> *p, cplx<T> v) {
+    if constexpr (sizeof(T) == 4 && TNMF_ROWS_FWD_NT != 0) {
+        typedef float f2_t __attribute__((ext_vector_type(2)));
+        __builtin_nontemporal_store(f2_t{v.x, v.y}, reinterpret_cast<f2_t *>(p));
+    } else {
+        *p = v;
+    }
+}
+
 // kFftRowsFwd: src0 real [planes][rows][ld_src] (cols valid) -> dst0 row spectra [planes][rows][KXP]
 // Thread mapping: for the real data a thread owns column x = tid (+ NT, ...) for all 2*NB rows -- those tile elements
 // are consecutive floats, so all addresses are a per-thread base plus an immediate; for the spectra it owns frequency
@@ -177,8 +195,8 @@ __global__ __launch_bounds__(NT) void k_fft_rows_fwd(FftArgs a) {
                 const int ya = y0 + 2 * p;
                 cplx<T> A, B;
                 split_pair(x[pk + p], x[plk + p], A, B);
-                if (ya < a.rows) dst[(long)ya * a.KXP + k] = A;
-                if (ya + 1 < a.rows) dst[(long)(ya + 1) * a.KXP + k] = B;
+                if (ya < a.rows) store_spectrum(dst + (long)ya * a.KXP + k, A);
+                if (ya + 1 < a.rows) store_spectrum(dst + (long)(ya + 1) * a.KXP + k, B);
             }
         }
     }
