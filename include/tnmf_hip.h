@@ -405,6 +405,27 @@ int tnmf_hip_sample_objective(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, doub
 int tnmf_hip_atom_terms(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int group, const void *V, const void *G_or_null,
                         const void *R_or_null, const void *W, const void *H, double *ab, void *stream);
 
+/* ---- atom Gram: how atoms overlap (ABI 8, additive: the version stays 8) ------------------------------------------------
+ * With R_m and d as under "atom terms":   B[n, m, m'] = sum G R_m[n] R_m'[n]   (G = 1 without weights): diag(B) is b, and
+ * with per-atom scale factors s (R(s) = sum s_m R_m) the objective of sample n is the exact quadratic
+ *   E(s) = E(1) - a^T (s - 1) + 1/2 (s - 1)^T B (s - 1);      without the atoms of a set S (s_S = 0): + sum_S a + 1/2 sum_SS B.
+ * One pass over H: r_m as for the atom terms, one channel at a time, parked in LDS per pixel tile for up to 32 (float) or
+ * 16 (double) atoms; the sums over the tile's pixels on the matrix cores (v_mfma_f64_16x16x4_f64), operands G r_m (the
+ * product in double) and r_m' converted to double, accumulated in double over a strip of 16 tiles per workgroup; with more
+ * atoms every pair of atom blocks is a workgroup of its own (512 threads in two halves with 32 rows, else 256).  Partial
+ * sums per (sample, strip, block pair), then their sum in strip order: no floating-point atomics, the same bits from run
+ * to run; B[n, m, m'] and B[n, m', m] are the same sum.
+ * Entries of weight <= 0 add exactly 0, whatever V holds there. */
+
+/* a[n*(M/group) + m] and B[(n*(M/group) + m)*(M/group) + m'] (double, device), B symmetric and written in full, in the
+ * order of H's atoms; per sample.  Operands, `group`, G_or_null, R_or_null, the row stride of H and the work buffer as for
+ * tnmf_hip_atom_terms.  Every element of a and B is written.  Asynchronous on the stream.
+ * TNMF_E_GEOM: group < 1 or M % group != 0.  TNMF_E_UNSUPPORTED: ndim == 3, or an atom whose tile of H (as for
+ * tnmf_hip_atom_terms) does not fit the 160 KiB of LDS next to the parked rows: 16 rows of 1040 elements, the tile's
+ * weights and 512 bytes.  A refused call writes nothing. */
+int tnmf_hip_atom_gram(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int group, const void *V, const void *G_or_null,
+                       const void *R_or_null, const void *W, const void *H, double *a, double *B, void *stream);
+
 /* ---- transform groups: rotation and mirror invariance (ABI 8, additive: the version stays 8) -------------------------
  * A dictionary W[M,C,*A] stands for M * T effective atoms W_eff[m*T + t] = T_t(W[m]), every T_t a permutation of the
  * atom's pixels.  The groups, with t in the order below (numpy, a = W[m, c]):

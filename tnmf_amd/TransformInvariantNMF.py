@@ -30,7 +30,8 @@ from typing import Callable, Iterable, Iterator, List, Optional, Tuple, Union
 import numpy as np
 
 from . import transforms as _transforms
-from .atoms_host import atom_terms_numpy
+from .atoms_host import (atom_gram_numpy, atom_terms_numpy, gram_drop, gram_elimination, gram_scales,
+                         gram_set_gain)
 from .backends._Backend import Backend, sliceNone
 # (the host side of the events; the names stay importable from this module)
 from .events_host import (event_boxes, event_images, events_alternatives_numpy, events_fit_numpy,  # noqa: F401
@@ -1051,6 +1052,129 @@ class TransformInvariantNMF:
         gain = a + 0.5 * b
         return gain if per_sample else gain.sum(axis=0)
 
+    # -- how atoms overlap: a and the Gram matrix B of the atoms' contributions ------------------------------------------
+    # With per-atom scale factors s (R(s) = sum s_m R_m) the objective is the exact quadratic
+    #   E(s) = E(1) - a^T (s - 1) + 1/2 (s - 1)^T B (s - 1),        B[m, m'] = sum G R_m R_m'  (diag(B) = b of atom_terms)
+    # so after ONE pass over H everything below is host algebra on an [n_atoms, n_atoms] matrix.
+    def _atom_refusals(self) -> None:
+        """What ``atom_terms`` refuses, with its messages."""
+        if self._H is None:
+            raise RuntimeError('the atom gains of a model need a fitted model: call fit first')
+        if self._beta != 2.:
+            raise NotImplementedError('atom_gains covers the Frobenius objective (beta_loss 2), with or without weights')
+        if len(self.atom_shape) == 3:
+            raise NotImplementedError('atom gains: 1 or 2 shift axes only')
+
+    def _atom_gram(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(a [N, n_atoms], B [N, n_atoms, n_atoms]), float64, samples in the order of ``H``; refuses what ``atom_terms``
+        refuses."""
+        self._atom_refusals()
+        hook = getattr(self._backend, 'atom_gram', None)
+        if hook is not None:
+            a, B = hook(self._V, self._W_dict, self._H, self.n_transforms)
+        else:
+            G = self._weights
+            if G is not None and len(G) != int(self._H.shape[0]):
+                n0 = int(getattr(self._backend, 'shard', (0, 0))[0])
+                G = G[n0:n0 + int(self._H.shape[0])]
+            a, B = atom_gram_numpy(self._backend.to_ndarray(self._W_dict), self._backend.to_ndarray(self._H),
+                                   getattr(self._backend, '_reconstruction_mode', 'valid'), self._local_V(), G,
+                                   self.n_transforms)
+        a, B = np.asarray(a, dtype=np.float64), np.asarray(B, dtype=np.float64)
+        if self._shuffle_idx is not None:
+            order = np.argsort(self._shuffle_idx)
+            a, B = a[order], B[order]
+        return a, B
+
+    def atom_gram(self, per_sample: bool = False) -> np.ndarray:
+        """``B[m, m'] = <R_m, R_m'>`` (after a weighted fit ``sum G R_m R_m'``) with ``R_m`` the contribution of atom m in
+        all its orientations: float64 ``[n_atoms, n_atoms]`` summed over the samples, or with ``per_sample=True``
+        ``[N, n_atoms, n_atoms]`` in the order of ``H``.  Symmetric; its diagonal is ``b`` of ``atom_terms``.  On a backend
+        with ``atom_gram`` one pass over the activations where they live.  Not collective: with a process group each rank
+        reports its own samples.  The Frobenius objective, with or without weights; ``W``, ``H``, ``V`` are not touched."""
+        if not isinstance(per_sample, (bool, np.bool_)):
+            raise ValueError(f'per_sample must be a bool, not {per_sample!r}')
+        B = self._atom_gram()[1]
+        return B if per_sample else B.sum(axis=0)
+
+    def atom_overlaps(self) -> np.ndarray:
+        """``B[m, m'] / sqrt(B[m, m] B[m', m'])``, float64 ``[n_atoms, n_atoms]``: the cosine between two atoms'
+        contributions to R, 1 for duplicates -- duplicates up to a shift included, since H absorbs the shift -- and 0 where
+        an atom is dead (contributes nothing)."""
+        B = self._atom_gram()[1].sum(axis=0)
+        norm = np.sqrt(np.diag(B))
+        live = norm > 0
+        out = np.zeros_like(B)
+        out[np.ix_(live, live)] = B[np.ix_(live, live)] / np.outer(norm[live], norm[live])
+        out[live, live] = 1.
+        return out
+
+    def _atom_indices(self, atoms) -> np.ndarray:
+        try:
+            items = list(atoms)
+        except TypeError:
+            raise ValueError(f'atoms must be a sequence of distinct ints in [0, {self.n_atoms}), not {atoms!r}') from None
+        for m in items:
+            if isinstance(m, (bool, np.bool_)) or not isinstance(m, numbers.Integral) or not 0 <= m < self.n_atoms:
+                raise ValueError(f'atoms must be distinct ints in [0, {self.n_atoms}), not {m!r}')
+        if len(set(int(m) for m in items)) != len(items):
+            raise ValueError(f'atoms must be distinct: {items!r}')
+        return np.asarray(items, dtype=np.int64)
+
+    def atom_set_gain(self, atoms) -> float:
+        """What the atoms in ``atoms`` explain together: the exact rise of the objective without them (their activations
+        set to zero, everything else held), ``sum_S a + 1/2 sum_SS B``.  A single atom gives ``atom_gains()[m]``.
+        ``atoms``: distinct ints in ``[0, n_atoms)``."""
+        idx = self._atom_indices(atoms)
+        a, B = self._atom_gram()
+        return gram_set_gain(a.sum(axis=0), B.sum(axis=0), idx)
+
+    def atom_scales(self, nonnegative: bool = True) -> np.ndarray:
+        """The per-atom scale factors ``s`` of the activations, ``[n_atoms]`` float64, that fit V best with everything else
+        held: the minimiser of ``E(s)``, ``B s = a + B 1``, over ``s >= 0`` unless ``nonnegative=False`` (an active-set
+        solve on the host) -- after a fit under ``sparsity_H``, the shrinkage undone for all atoms at once.  Dead atoms get
+        scale 1; a singular block, such as two exact duplicates, its minimum-norm solution."""
+        if not isinstance(nonnegative, (bool, np.bool_)):
+            raise ValueError(f'nonnegative must be a bool, not {nonnegative!r}')
+        a, B = self._atom_gram()
+        return gram_scales(a.sum(axis=0), B.sum(axis=0), bool(nonnegative))
+
+    def rescale_atoms(self, scales=None) -> float:
+        """Multiply the activations of atom m (all its orientations) by ``scales[m]`` in place -- ``None``:
+        ``atom_scales()`` -- and return the predicted drop of the objective, ``a^T (s - 1) - 1/2 (s - 1)^T B (s - 1)``
+        (exact for the Frobenius objective up to rounding).  Leaves the factors in ``atom_scales_``.  ``scales``:
+        ``[n_atoms]`` finite numbers >= 0.  With a process group ``scales`` must be given: the (a, B) of this call are this
+        rank's, and a global ``s`` is the caller's all-reduce of ``atom_terms`` / ``atom_gram``."""
+        if scales is not None:
+            s = np.asarray(scales, dtype=np.float64)
+            if s.shape != (self.n_atoms,) or not np.all(np.isfinite(s)) or np.any(s < 0):
+                raise ValueError(f'scales must be {self.n_atoms} finite numbers >= 0, not {scales!r}')
+        self._atom_refusals()
+        if scales is None and int(getattr(self._backend, '_world', 1)) > 1:   # (before the pass over H)
+            raise NotImplementedError('rescale_atoms with a process group needs the scales: reduce atom_terms and '
+                                      'atom_gram over the ranks and pass the global scales')
+        a, B = self._atom_gram()
+        a, B = a.sum(axis=0), B.sum(axis=0)
+        if scales is None:
+            s = gram_scales(a, B, True)
+        drop = gram_drop(a, B, s)
+        T = self.n_transforms
+        for m in np.flatnonzero(s != 1.):
+            self._H[:, m * T:(m + 1) * T] *= float(s[m])   # (in place: an array library's own operation, which its caches see)
+        self.atom_scales_ = s
+        return drop
+
+    def atom_elimination(self, rescale: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """Backward elimination of atoms on ``(a, B)`` alone -> ``(order, rise)``: ``order[k]`` is the atom whose removal
+        raises the objective least given ``order[:k]`` already removed, ``rise[k]`` the cumulative rise of the objective
+        over the model as it stands once ``order[:k + 1]`` are gone.  ``rescale=True``: the remaining atoms are rescaled
+        optimally (``s >= 0``) at every step, so ``rise`` may begin below zero.  One pass over H, then host algebra; the
+        model is not touched."""
+        if not isinstance(rescale, (bool, np.bool_)):
+            raise ValueError(f'rescale must be a bool, not {rescale!r}')
+        a, B = self._atom_gram()
+        return gram_elimination(a.sum(axis=0), B.sum(axis=0), bool(rescale))
+
     # -- stopping on the objective ---------------------------------------------------------------------------------
     @staticmethod
     def _convergence_args(objective_every, tol) -> Tuple[Optional[int], Optional[float]]:
@@ -1205,8 +1329,9 @@ class TransformInvariantNMF:
         self._iteration_acc = None    # (sized and typed for the W of ONE fit: a refit may change dtype or device)
         self._objective_buf = None    # (one value per local sample of ONE fit)
         self._weighted = weights is not None
-        # (the host copy, kept only for atom_terms on a backend without the hook)
-        self._weights = weights if getattr(self._backend, 'atom_terms', None) is None else None
+        # (the host copy, kept only for atom_terms / atom_gram on a backend without the hooks)
+        hooks = [getattr(self._backend, name, None) for name in ('atom_terms', 'atom_gram')]
+        self._weights = weights if None in hooks else None
         kw = {} if weights is None else {'weights': weights}
         if self._transforms is not None:
             kw['transforms'] = self._transforms

@@ -1,7 +1,8 @@
 """
-What each atom explains, on the host: the NumPy fallback of ``atom_terms`` for a backend without the hook
-(tnmf_amd/backends/_Backend.py) -- the semantics of tnmf_hip_atom_terms (include/tnmf_hip.h, "atom terms") in float64.
-Not on the hip path.
+What each atom explains and how atoms overlap, on the host: the NumPy fallbacks of ``atom_terms`` and ``atom_gram`` for a
+backend without the hooks (tnmf_amd/backends/_Backend.py) -- the semantics of tnmf_hip_atom_terms and tnmf_hip_atom_gram
+(include/tnmf_hip.h, "atom terms", "atom Gram") in float64; not on the hip path -- and the algebra on ``(a, B)`` that every
+backend's front end runs on the host: joint scale factors, set gains, backward elimination.
 """
 import itertools
 from typing import Optional, Tuple
@@ -31,6 +32,13 @@ def atom_terms_numpy(W: np.ndarray, H: np.ndarray, mode: str, V: np.ndarray, G: 
     activations ``H[N, P, *S]`` (in the shift shape of ``mode``) add to the reconstruction R of the samples ``V[N, C, *D]``
     and ``d = V - R``: ``a = sum G R_m d`` and ``b = sum G R_m^2`` (``G``: weights of V's shape, None for 1; entries of
     weight 0 add exactly 0 whatever V holds there).  ``a + b / 2`` is what the objective rises by without the atom."""
+    parts, gd, g = _parts_and_residual(W, H, mode, V, G, group)
+    axes = tuple(range(2, parts.ndim))
+    return np.sum(parts * gd[:, None], axis=axes), np.sum(g[:, None] * parts * parts, axis=axes)
+
+
+def _parts_and_residual(W, H, mode, V, G, group):
+    """(R_m ``[N, P / group, C, *D]``, G d with exact zeros where the weight is <= 0, G clipped at 0), float64."""
     W, H = np.asarray(W, dtype=np.float64), np.asarray(H, dtype=np.float64)
     A, D = tuple(W.shape[2:]), tuple(V.shape[2:])
     P = W.shape[0]
@@ -49,5 +57,111 @@ def atom_terms_numpy(W: np.ndarray, H: np.ndarray, mode: str, V: np.ndarray, G: 
     with np.errstate(invalid='ignore'):
         gd = np.where(g > 0, g * (np.asarray(V, dtype=np.float64) - parts.sum(axis=1)), 0.)
     g = np.where(g > 0, g, 0.)
-    axes = tuple(range(2, parts.ndim))
-    return np.sum(parts * gd[:, None], axis=axes), np.sum(g[:, None] * parts * parts, axis=axes)
+    return parts, gd, g
+
+
+def atom_gram_numpy(W: np.ndarray, H: np.ndarray, mode: str, V: np.ndarray, G: Optional[np.ndarray] = None,
+                    group: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+    """(a, B), float64 ``[N, Mo]`` and ``[N, Mo, Mo]`` with ``Mo = P / group``: ``a`` of ``atom_terms_numpy`` and
+    ``B[n, m, m'] = sum G R_m R_m'``, symmetric, whose diagonal is ``b`` (same operands, same treatment of weights)."""
+    parts, gd, g = _parts_and_residual(W, H, mode, V, G, group)
+    N, Mo = parts.shape[:2]
+    flat = parts.reshape(N, Mo, -1)
+    B = np.einsum('nmx,nkx->nmk', flat * g.reshape(N, 1, -1), flat)
+    B = 0.5 * (B + B.transpose(0, 2, 1))
+    b = np.sum(g[:, None] * parts * parts, axis=tuple(range(2, parts.ndim)))
+    B[:, np.arange(Mo), np.arange(Mo)] = b
+    return np.sum(parts * gd[:, None], axis=tuple(range(2, parts.ndim))), B
+
+
+# -- the algebra on (a, B): E(s) = E(1) - a^T (s - 1) + 1/2 (s - 1)^T B (s - 1) for per-atom scale factors s ------------------
+def gram_drop(a: np.ndarray, B: np.ndarray, s: np.ndarray) -> float:
+    """E(1) - E(s): what the objective falls by under the scale factors s."""
+    e = np.asarray(s, dtype=np.float64) - 1.
+    return float(a @ e - 0.5 * e @ B @ e)
+
+
+def _min_norm(B, c, idx):
+    z = np.zeros(len(c))
+    if len(idx):
+        z[idx] = np.linalg.lstsq(B[np.ix_(idx, idx)], c[idx], rcond=None)[0]   # (minimum norm where the block is singular)
+    return z
+
+
+def gram_scales(a: np.ndarray, B: np.ndarray, nonnegative: bool = True, fixed_zero=()) -> np.ndarray:
+    """The scale factors s that minimise E(s): ``B s = a + B 1``, over ``s >= 0`` when ``nonnegative`` (an active-set
+    solve: Lawson and Hanson's NNLS on the normal equations), with ``s[fixed_zero] = 0`` held.  Atoms with ``B[m, m] == 0``
+    are dead: they change nothing and keep scale 1.  A singular block gets its minimum-norm solution."""
+    a, B = np.asarray(a, dtype=np.float64), np.asarray(B, dtype=np.float64)
+    M = len(a)
+    s = np.ones(M)
+    out = np.zeros(M, dtype=bool)
+    out[list(fixed_zero)] = True
+    s[out] = 0.
+    live = np.flatnonzero((np.diag(B) > 0) & ~out)
+    if len(live) == 0:
+        return s
+    # minimise 1/2 z^T Bl z - c^T z over the live ones; the held ones, at 0, drop out of B s and stay in c = a + B 1
+    Bl, c = B[np.ix_(live, live)], (a + B @ np.ones(M))[live]
+    every = np.arange(len(live))
+    z = _min_norm(Bl, c, every)
+    tol = 64 * np.finfo(np.float64).eps * len(live) * max(float(np.max(np.abs(c))), float(np.max(np.abs(Bl @ np.abs(z)))))
+    if nonnegative and np.any(z < 0):
+        z = np.zeros(len(live))
+        passive = np.zeros(len(live), dtype=bool)
+        for _ in range(3 * len(live) + 3):
+            w = c - Bl @ z
+            cand = ~passive & (w > tol)
+            if not np.any(cand):
+                break
+            passive[np.argmax(np.where(cand, w, -np.inf))] = True
+            while True:
+                t = _min_norm(Bl, c, np.flatnonzero(passive))
+                bad = passive & (t <= 0)
+                if not np.any(bad):
+                    z = t
+                    break
+                alpha = np.min(z[bad] / (z[bad] - t[bad]))
+                z = z + alpha * (t - z)
+                passive &= z > tol / max(float(np.max(np.diag(Bl))), 1e-300)
+                z[~passive] = 0.
+        # atoms at 0 whose gradient vanishes too (duplicates of a passive one) share its load: the minimum-norm solution
+        w = c - Bl @ z
+        tied = np.flatnonzero(passive | (np.abs(w) <= tol))
+        t = _min_norm(Bl, c, tied)
+        if np.all(t >= 0) and 0.5 * t @ Bl @ t - c @ t <= 0.5 * z @ Bl @ z - c @ z + tol:
+            z = t
+    s[live] = z
+    return s
+
+
+def gram_set_gain(a: np.ndarray, B: np.ndarray, atoms) -> float:
+    """E(s) - E(1) with ``s[atoms] = 0``: what the objective rises by without the atoms."""
+    idx = np.asarray(list(atoms), dtype=np.int64)
+    return float(a[idx].sum() + 0.5 * B[np.ix_(idx, idx)].sum())
+
+
+def gram_elimination(a: np.ndarray, B: np.ndarray, rescale: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    """Backward elimination on (a, B) alone -> (order [M] int64, rise [M] float64): each time the atom whose removal
+    raises the objective least given those already removed; ``rise[k]`` is the cumulative rise over the model as it stands
+    (all scales 1) after ``order[:k + 1]`` are gone.  ``rescale``: the remaining atoms are rescaled optimally (s >= 0) at
+    every step, and the rise is measured against the model as it stands all the same (it may start negative)."""
+    a, B = np.asarray(a, dtype=np.float64), np.asarray(B, dtype=np.float64)
+    M = len(a)
+    gone, order, rise = [], [], []
+    for _ in range(M):
+        best = None
+        for m in range(M):
+            if m in gone:
+                continue
+            trial = gone + [m]
+            if rescale:
+                val = -gram_drop(a, B, gram_scales(a, B, True, trial))
+            else:
+                val = gram_set_gain(a, B, trial)
+            if best is None or val < best[0]:
+                best = (val, m)
+        gone.append(best[1])
+        order.append(best[1])
+        rise.append(best[0])
+    return np.asarray(order, dtype=np.int64), np.asarray(rise, dtype=np.float64)

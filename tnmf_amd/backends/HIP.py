@@ -793,6 +793,27 @@ class HIP_Backend(Backend):
         out = ab.cpu().numpy()
         return np.ascontiguousarray(out[..., 0]), np.ascontiguousarray(out[..., 1])
 
+    def atom_gram(self, V, W: torch.Tensor, H: torch.Tensor, group: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+        """(a, B), float64 ``[n_local_samples, Mo]`` and ``[n_local_samples, Mo, Mo]`` (``Mo = n_planes / group``) on the
+        host: ``a`` of ``atom_terms`` and ``B[n, m, m'] = sum G R_m R_m'`` with the bound weights G (include/tnmf_hip.h,
+        "atom Gram") -> tnmf_hip_atom_gram: one pass over H, the contraction over the pixels on the matrix cores, and only
+        the sums cross to the host.  The modes other than 'valid' are the 'valid' pass over the padded activations."""
+        if len(self.atom_shape) == 3:
+            raise NotImplementedError('atom gains: 1 or 2 shift axes only')
+        self._check_W(W)
+        self._foreign_H()
+        self._check_H(H, W.shape[0])
+        assert H.shape[0] == self.n_local_samples
+        H = self._pad(H)
+        Mo = W.shape[0] // max(int(group), 1)
+        a = torch.empty((H.shape[0], Mo), dtype=torch.float64, device=self._device)
+        B = torch.empty((H.shape[0], Mo, Mo), dtype=torch.float64, device=self._device)
+        self._call_H(H, False, lambda Hc, ld: (self._lib.tnmf_hip_atom_gram(
+            self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)), int(group), _ptr(self._V_dev),
+            None if self._G_dev is None else _ptr(self._G_dev), None, _ptr(W), _ptr(Hc), _ptr(a), _ptr(B), self._stream()),
+            'tnmf_hip_atom_gram'))
+        return a.cpu().numpy(), B.cpu().numpy()
+
     # -- detections -----------------------------------------------------------------------------------------------------
     # The peaks of H are found and compacted on the device (include/tnmf_hip.h, "detections"): only the list of
     # (index, value) pairs crosses to the host, never H.

@@ -35,6 +35,10 @@ sample order, over all ranks.  ``sample_objective(V, W, H, beta, eps)`` -> one f
 planes of W -- an atom in all its orientations -- explains of the local samples under the Frobenius objective, with the
 weights when they are bound (include/tnmf_hip.h, "atom terms"); without it ``atom_terms`` / ``atom_gains`` run
 ``atom_terms_numpy`` (tnmf_amd/atoms_host.py) on the host.
+``atom_gram(V, W, H, group) -> (a, B)`` (float64 ``[n_local, Mo]`` and ``[n_local, Mo, Mo]``, ``Mo = n_planes / group``,
+host): ``a`` as above and ``B[n, m, m'] = sum G R_m R_m'``, symmetric, in the order of H's atoms (include/tnmf_hip.h, "atom
+Gram"); without it ``atom_gram`` and what builds on it (``atom_overlaps``, ``atom_set_gain``, ``atom_scales``,
+``rescale_atoms``, ``atom_elimination``) run ``atom_gram_numpy`` (tnmf_amd/atoms_host.py) on the host.
 A backend that declares ``supports_peaks`` offers ``find_peaks(H, threshold, radius, group) -> (idx, val)``: the ascending
 flat C-order indices (int64, host) in H's shape [n, P, *S] and the values of the detections of its native H
 (include/tnmf_hip.h, "detections"); without it ``detections()`` searches ``to_ndarray(H)`` on the host.

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "atom_gram.h"
 #include "atoms.h"
 #include "beta.h"
 #include "events.h"
@@ -899,6 +900,30 @@ int tnmf_hip_atom_terms(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int group,
     }
     return launch_atom_terms(ctx, g, dtype, group, V, G_or_null, R, W, H, static_cast<double *>(ctx->ob),
                              static_cast<char *>(ctx->ob) + p_bytes, ab, s);
+}
+
+int tnmf_hip_atom_gram(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int group, const void *V, const void *G_or_null,
+                       const void *R_or_null, const void *W, const void *H, double *a, double *B, void *stream) {
+    if (!ctx || !geom) return TNMF_E_NULL;
+    if (is_vol(geom)) return TNMF_E_UNSUPPORTED;
+    ENTER(ctx, geom);
+    if (group < 1 || g.M % group != 0) return TNMF_E_GEOM;
+    if (g.N == 0) return TNMF_OK;
+    if (!V || !W || !H || !a || !B) return TNMF_E_NULL;
+    CHECK(atom_gram_check(g, dtype, group));
+    // work buffer: [partial sums per (sample, strip, pair of atom blocks) | the taps of the flipped dictionary]
+    const size_t p_bytes = atom_gram_partial_bytes(g, dtype, group);
+    CHECK(ensure_buffer(&ctx->ob, &ctx->ob_bytes, p_bytes + atom_terms_taps_bytes(g, dtype), false));
+    const void *R = R_or_null;
+    if (!R) {
+        const Scratch sc = plan_scratch(ctx, g, dtype);
+        CHECK(ensure_scratch(ctx, sc.total));
+        void *Rs = ws_at(ctx, sc.r_off);
+        CHECK(do_reconstruct(ctx, g, dtype, W, H, Rs, s));
+        R = Rs;
+    }
+    return launch_atom_gram(ctx, g, dtype, group, V, G_or_null, R, W, H, static_cast<double *>(ctx->ob),
+                            static_cast<char *>(ctx->ob) + p_bytes, a, B, s);
 }
 
 int tnmf_hip_beta_fields(tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *R, void *Q,
