@@ -23,12 +23,12 @@ import enum
 import itertools
 import logging
 import math
-import numbers
 import warnings
 from typing import Callable, Iterable, Iterator, List, Optional, Tuple, Union
 
 import numpy as np
 
+from . import _args
 from . import transforms as _transforms
 from .atoms_host import (atom_gram_numpy, atom_terms_numpy, gram_drop, gram_elimination, gram_scales,
                          gram_set_gain)
@@ -93,7 +93,7 @@ def beta_loss_value(beta_loss) -> float:
         if beta_loss not in _BETA_NAMES:
             raise ValueError(f'beta_loss must be one of {sorted(_BETA_NAMES)} or a finite float, not {beta_loss!r}')
         return _BETA_NAMES[beta_loss]
-    if isinstance(beta_loss, (bool, np.bool_)) or not isinstance(beta_loss, (int, float, np.integer, np.floating)):
+    if _args.is_bool(beta_loss) or not isinstance(beta_loss, (int, float, np.integer, np.floating)):
         raise ValueError(f'beta_loss must be one of {sorted(_BETA_NAMES)} or a finite float, not {beta_loss!r}')
     beta = float(beta_loss)
     if not np.isfinite(beta):
@@ -341,28 +341,24 @@ class TransformInvariantNMF:
         other backend's ``H`` is searched on the host."""
         if self._H is None:
             raise RuntimeError('detections() needs a fitted model: call fit first')
-        if (isinstance(threshold, (bool, np.bool_)) or not isinstance(threshold, numbers.Real)
-                or not math.isfinite(threshold) or threshold < 0):
-            raise ValueError(f'threshold must be a finite number >= 0, not {threshold!r}')
+        _args.finite_number('threshold', threshold, '>= 0')
         k = len(self.atom_shape)
         if min_distance is None:
             radius = self._inhibition_range
-        elif isinstance(min_distance, numbers.Integral) and not isinstance(min_distance, (bool, np.bool_)):
+        elif _args.is_int(min_distance):
             radius = (min_distance,) * k
         elif isinstance(min_distance, (tuple, list)) and len(min_distance) == k:
             radius = tuple(min_distance)
         else:
             raise ValueError(f'min_distance must be None, an int or {k} ints, not {min_distance!r}')
-        if any(isinstance(r, (bool, np.bool_)) or not isinstance(r, numbers.Integral) or r < 0 for r in radius):
+        if any(not _args.is_int(r) or r < 0 for r in radius):
             raise ValueError(f'min_distance must be >= 0 on every axis, not {min_distance!r}')
         radius = tuple(int(r) for r in radius)
         if not isinstance(suppress, str) or suppress not in self._SUPPRESS:
             raise ValueError(f'suppress must be one of {self._SUPPRESS}, not {suppress!r}')
         if suppress == 'transforms' and self._transforms is None:
             raise ValueError("suppress='transforms' needs a model with transforms")
-        if max_per_sample is not None and (isinstance(max_per_sample, (bool, np.bool_))
-                                           or not isinstance(max_per_sample, numbers.Integral) or max_per_sample < 0):
-            raise ValueError(f'max_per_sample must be None or an int >= 0, not {max_per_sample!r}')
+        _args.int_at_least('max_per_sample', max_per_sample, 0, none_ok=True)
         shape = tuple(int(x) for x in self._H.shape)   # [local samples, M * T, *shift]
         T = self.n_transforms
         group = {'atom': 1, 'transforms': T, 'all': shape[1]}[suppress]
@@ -388,12 +384,27 @@ class TransformInvariantNMF:
             sample, val, at = sample[keep], val[keep], tuple(a[keep] for a in at)
         sample = sample + int(getattr(self._backend, 'shard', (0, 0))[0])
         shift = np.stack([a.astype(np.int64) for a in at[2:]], axis=1).reshape(len(val), k)
-        mode = getattr(self._backend, '_reconstruction_mode', 'valid')
-        offset = np.array([a - 1 if mode == 'valid' else 0 for a in self.atom_shape], dtype=np.int64)
         return Detections(sample=sample, atom=(at[1] // T).astype(np.int64), transform=(at[1] % T).astype(np.int64),
-                          shift=shift, origin=shift - offset, strength=val)
+                          shift=shift, origin=shift - self._origin_offset(), strength=val)
 
     # -- detections rendered and refitted -------------------------------------------------------------------------------
+    @property
+    def _mode(self) -> str:
+        """The backend's reconstruction mode ('valid' for a backend that does not say)."""
+        return getattr(self._backend, '_reconstruction_mode', 'valid')
+
+    def _origin_offset(self) -> np.ndarray:
+        """[k]: ``shift - origin`` of a detection, ``atom_shape - 1`` in 'valid' mode and 0 in the others."""
+        return np.array([a - 1 if self._mode == 'valid' else 0 for a in self.atom_shape], dtype=np.int64)
+
+    def _plain_frobenius_only(self, who: str) -> bool:
+        """The refusal the list operations share: ``who`` works on the plain Frobenius objective.  Returns whether the
+        model is fitted and not a volume -- the two ``_events_of`` refuses next, with messages of its own."""
+        served = self._H is not None and len(self.atom_shape) != 3
+        if served and (self._beta != 2. or self._weighted):
+            raise NotImplementedError(f'{who} covers the plain Frobenius objective (beta_loss 2, no weights)')
+        return served
+
     def _events_of(self, det, distinct: bool):
         """The events of ``det`` in the backend's terms -- (internal local sample, plane of the effective dictionary, shift,
         strength in the model's element type) -- after the checks: the inverse of what ``detections()`` applies to the
@@ -439,6 +450,40 @@ class TransformInvariantNMF:
         n0, n = int(getattr(self._backend, 'shard', (0, 0))[0]), int(self._H.shape[0])
         return self._V if len(self._V) == n else self._V[n0:n0 + n]
 
+    def _rows_to_detections(self, sample, plane, shift, strength) -> Detections:
+        """The inverse of ``_events_of``: rows in the backend's terms as the ``Detections`` the caller sees."""
+        sample = np.asarray(sample, dtype=np.int64)
+        if self._shuffle_idx is not None:   # (internal sample a[i] is shown at place i)
+            place = np.empty(int(self._H.shape[0]), dtype=np.int64)
+            place[np.argsort(self._shuffle_idx)] = np.arange(int(self._H.shape[0]))
+            sample = place[sample]
+        sample = sample + int(getattr(self._backend, 'shard', (0, 0))[0])
+        plane = np.asarray(plane, dtype=np.int64)
+        shift = np.asarray(shift, dtype=np.int64).reshape(len(sample), len(self.atom_shape))
+        T = self.n_transforms
+        return Detections(sample=sample, atom=plane // T, transform=plane % T, shift=shift,
+                          origin=shift - self._origin_offset(), strength=np.asarray(strength))
+
+    def _with_strengths(self, det, shift, strength) -> Detections:
+        """The rows of ``det`` (any object with its columns; ``shift`` is theirs, checked) with new strengths."""
+        as_rows = lambda x: np.asarray(x).astype(np.int64).reshape(len(strength))   # noqa: E731
+        return Detections(sample=as_rows(det.sample), atom=as_rows(det.atom), transform=as_rows(det.transform),
+                          shift=shift, origin=shift - self._origin_offset(), strength=strength)
+
+    def _host_problem(self, W=None):
+        """(dictionary on the host, sample shape, local samples, mode): what every function of events_host.py takes first.
+        ``W``: the effective dictionary unless given."""
+        return (self._backend.to_ndarray(self._W_dict if W is None else W), self._V.shape[2:], int(self._H.shape[0]),
+                self._mode)
+
+    def _on_events(self, hook_name: str, fallback: Callable, rows, *more, **kw):
+        """The backend's hook ``hook_name`` on the rows of ``_events_of``, or on a backend without it the function
+        ``fallback`` of events_host.py, which takes the host problem, the rows, this rank's samples and the same rest."""
+        hook = getattr(self._backend, hook_name, None)
+        if hook is not None:
+            return hook(self._V, self._W_dict, *rows, *more, **kw)
+        return fallback(*self._host_problem(), *rows, self._local_V(), *more, **kw)
+
     def reconstruct_detections(self, det) -> np.ndarray:
         """What the detections ``det`` (a ``Detections``, or any object with its sample, atom, transform, shift and
         strength) explain: the reconstruction of the activations that hold the strengths at the detections and zero
@@ -448,8 +493,7 @@ class TransformInvariantNMF:
         hook = getattr(self._backend, 'render_events', None)
         if hook is not None:
             return self._backend.to_ndarray(hook(self._W_dict, sample, plane, shift, strength))
-        return events_numpy(self._backend.to_ndarray(self._W_dict), self._V.shape[2:], int(self._H.shape[0]),
-                            getattr(self._backend, '_reconstruction_mode', 'valid'), sample, plane, shift, strength)
+        return events_numpy(*self._host_problem(), sample, plane, shift, strength)
 
     def refit_detections(self, det, n_iterations: int = 50, sparsity_H: float = 0.) -> Detections:
         """The detections with their strengths refitted: ``n_iterations`` multiplicative updates of the strengths alone, on
@@ -457,29 +501,18 @@ class TransformInvariantNMF:
         inhibition on activations that are zero off the support.  It removes the shrinkage the strengths carry from a fit
         under ``sparsity_H`` or inhibition (and from the sub-threshold activations ``detections()`` dropped).  The rows must
         be distinct; a strength of 0 stays 0.  The plain Frobenius objective only."""
-        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
-            raise NotImplementedError('refit_detections covers the plain Frobenius objective (beta_loss 2, no weights)')
-        if (isinstance(n_iterations, (bool, np.bool_)) or not isinstance(n_iterations, numbers.Integral)
-                or n_iterations < 0):
-            raise ValueError(f'n_iterations must be an int >= 0, not {n_iterations!r}')
-        if (isinstance(sparsity_H, (bool, np.bool_)) or not isinstance(sparsity_H, numbers.Real)
-                or not math.isfinite(sparsity_H) or sparsity_H < 0):
-            raise ValueError(f'sparsity_H must be a finite number >= 0, not {sparsity_H!r}')
+        self._plain_frobenius_only('refit_detections')
+        _args.int_at_least('n_iterations', n_iterations, 0)
+        _args.finite_number('sparsity_H', sparsity_H, '>= 0')
         sample, plane, shift, strength = self._events_of(det, distinct=True)
         hook = getattr(self._backend, 'refit_events', None)
         if hook is not None:
             new = self._backend.to_ndarray(hook(self._V, self._W_dict, sample, plane, shift, strength, int(n_iterations),
                                                 sparsity=float(sparsity_H), eps=self.eps))
         else:
-            new = events_numpy(self._backend.to_ndarray(self._W_dict), self._V.shape[2:], int(self._H.shape[0]),
-                               getattr(self._backend, '_reconstruction_mode', 'valid'), sample, plane, shift, strength,
-                               V=self._local_V(), n_iterations=int(n_iterations), sparsity=float(sparsity_H),
-                               eps=self.eps)
-        mode = getattr(self._backend, '_reconstruction_mode', 'valid')
-        offset = np.array([a - 1 if mode == 'valid' else 0 for a in self.atom_shape], dtype=np.int64)
-        as_rows = lambda x: np.asarray(x).astype(np.int64).reshape(len(new))   # noqa: E731
-        return Detections(sample=as_rows(det.sample), atom=as_rows(det.atom), transform=as_rows(det.transform),
-                          shift=shift, origin=shift - offset, strength=new)
+            new = events_numpy(*self._host_problem(), sample, plane, shift, strength, V=self._local_V(),
+                               n_iterations=int(n_iterations), sparsity=float(sparsity_H), eps=self.eps)
+        return self._with_strengths(det, shift, new)
 
     def solve_detections(self, det, tol: float = 1e-8, max_iterations: int = 10000) -> Detections:
         """The detections with the strengths that MINIMISE the objective on the fixed support ``det`` and the fixed
@@ -495,8 +528,7 @@ class TransformInvariantNMF:
         ``solve_converged_`` -- a run that ends unconverged returns its last iterate and says so there.  The rows must be
         distinct; the plain Frobenius objective only.  On a backend with ``solve_events`` everything runs on the device.
         With a process group every rank solves its own samples: the call is not collective."""
-        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
-            raise NotImplementedError('solve_detections covers the plain Frobenius objective (beta_loss 2, no weights)')
+        self._plain_frobenius_only('solve_detections')
         self._check_solve_args(tol, max_iterations)
         sample, plane, shift, strength = self._events_of(det, distinct=True)
         hook = getattr(self._backend, 'solve_events', None)
@@ -504,18 +536,12 @@ class TransformInvariantNMF:
             new, info = hook(self._V, self._W_dict, sample, plane, shift, strength, float(tol), int(max_iterations))
             new = np.asarray(self._backend.to_ndarray(new), dtype=np.float64)
         else:
-            G, c = events_gram_numpy(self._backend.to_ndarray(self._W_dict), self._V.shape[2:], int(self._H.shape[0]),
-                                     getattr(self._backend, '_reconstruction_mode', 'valid'), sample, plane, shift,
-                                     V=self._local_V(), sparse=True)
+            G, c = events_gram_numpy(*self._host_problem(), sample, plane, shift, V=self._local_V(), sparse=True)
             new, info = events_solve_numpy(G, c, strength, float(tol), int(max_iterations))
         self.solve_history_ = np.asarray(info['history'], dtype=np.float64).reshape(-1, 2)
         self.solve_n_iter_ = int(info['iterations'])
         self.solve_converged_ = bool(info['converged'])
-        mode = getattr(self._backend, '_reconstruction_mode', 'valid')
-        offset = np.array([a - 1 if mode == 'valid' else 0 for a in self.atom_shape], dtype=np.int64)
-        as_rows = lambda x: np.asarray(x).astype(np.int64).reshape(len(new))   # noqa: E731
-        return Detections(sample=as_rows(det.sample), atom=as_rows(det.atom), transform=as_rows(det.transform),
-                          shift=shift, origin=shift - offset, strength=new.astype(self._V.dtype))
+        return self._with_strengths(det, shift, new.astype(self._V.dtype))
 
     def detection_errors(self, det, noise: Optional[float] = None, max_component: int = 2048) -> Tuple[np.ndarray, np.ndarray]:
         """(stderr [K], vif [K]) in float64: how well the strengths of ``det`` are determined.  Meant for the output of
@@ -538,14 +564,9 @@ class TransformInvariantNMF:
         ``H``, ``W`` and ``det`` are not touched.  On a backend with ``event_errors`` everything runs on the device.  With a
         process group every rank uses its own samples and the call is not collective: a sigma shared by the ranks is the
         caller's to pass in as ``noise``."""
-        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
-            raise NotImplementedError('detection_errors covers the plain Frobenius objective (beta_loss 2, no weights)')
-        if noise is not None and (isinstance(noise, (bool, np.bool_)) or not isinstance(noise, numbers.Real)
-                                  or not math.isfinite(noise) or not noise > 0):
-            raise ValueError(f'noise must be None or a finite number > 0, not {noise!r}')
-        if (isinstance(max_component, (bool, np.bool_)) or not isinstance(max_component, numbers.Integral)
-                or max_component < 1):
-            raise ValueError(f'max_component must be an int >= 1, not {max_component!r}')
+        self._plain_frobenius_only('detection_errors')
+        _args.finite_number('noise', noise, '> 0', none_ok=True)
+        _args.int_at_least('max_component', max_component, 1)
         sample, plane, shift, strength = self._events_of(det, distinct=True)
         hook = getattr(self._backend, 'event_errors', None)
         if hook is not None:
@@ -554,9 +575,7 @@ class TransformInvariantNMF:
             row_size = np.asarray(self._backend.to_ndarray(info['row_size']))
         else:
             V = np.asarray(self._local_V(), dtype=np.float64)
-            G, c = events_gram_numpy(self._backend.to_ndarray(self._W_dict), self._V.shape[2:], int(self._H.shape[0]),
-                                     getattr(self._backend, '_reconstruction_mode', 'valid'), sample, plane, shift,
-                                     V=V, sparse=True)
+            G, c = events_gram_numpy(*self._host_problem(), sample, plane, shift, V=V, sparse=True)
             h = strength.astype(np.float64)
             d, info = events_inverse_diag_numpy(G, h > 0, int(max_component))
             row_of = np.repeat(np.arange(len(h)), np.diff(G[0]))
@@ -583,11 +602,8 @@ class TransformInvariantNMF:
 
     @staticmethod
     def _check_solve_args(tol, max_iterations) -> None:
-        if isinstance(tol, (bool, np.bool_)) or not isinstance(tol, numbers.Real) or not math.isfinite(tol) or not tol > 0:
-            raise ValueError(f'tol must be a finite number > 0, not {tol!r}')
-        if (isinstance(max_iterations, (bool, np.bool_)) or not isinstance(max_iterations, numbers.Integral)
-                or max_iterations < 0):
-            raise ValueError(f'max_iterations must be an int >= 0, not {max_iterations!r}')
+        _args.finite_number('tol', tol, '> 0')
+        _args.int_at_least('max_iterations', max_iterations, 0)
 
     def _list_strengths(self, who: str, strengths, n_iterations, sparsity_H, tol, max_iterations):
         """det -> det with the strengths of a round of ``who``: ``refit_detections`` ('mu') or ``solve_detections``
@@ -596,9 +612,7 @@ class TransformInvariantNMF:
             return lambda det: self.refit_detections(det, n_iterations, sparsity_H)
         if strengths != 'solve':
             raise ValueError(f"strengths must be 'mu' or 'solve', not {strengths!r}")
-        if (isinstance(sparsity_H, (bool, np.bool_)) or not isinstance(sparsity_H, numbers.Real)
-                or not math.isfinite(sparsity_H) or sparsity_H < 0):
-            raise ValueError(f'sparsity_H must be a finite number >= 0, not {sparsity_H!r}')
+        _args.finite_number('sparsity_H', sparsity_H, '>= 0')
         if sparsity_H != 0:
             raise ValueError(f"{who}: strengths='solve' minimises the objective without a sparsity term: sparsity_H must "
                              f'be 0, not {sparsity_H!r}')
@@ -613,15 +627,9 @@ class TransformInvariantNMF:
         the units of the objective for every atom.  Duplicate rows are scored each against the whole list.  On a backend
         with ``event_gains`` the list is rendered and scored on the device and only the K gains are copied.  The plain
         Frobenius objective only."""
-        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
-            raise NotImplementedError('detection_gains covers the plain Frobenius objective (beta_loss 2, no weights)')
-        sample, plane, shift, strength = self._events_of(det, distinct=False)
-        hook = getattr(self._backend, 'event_gains', None)
-        if hook is not None:
-            return np.asarray(hook(self._V, self._W_dict, sample, plane, shift, strength), dtype=np.float64)
-        return events_gain_numpy(self._backend.to_ndarray(self._W_dict), self._V.shape[2:], int(self._H.shape[0]),
-                                 getattr(self._backend, '_reconstruction_mode', 'valid'), sample, plane, shift, strength,
-                                 self._local_V())
+        self._plain_frobenius_only('detection_gains')
+        rows = self._events_of(det, distinct=False)
+        return np.asarray(self._on_events('event_gains', events_gain_numpy, rows), dtype=np.float64)
 
     def prune_detections(self, det, min_gain: float, n_iterations: int = 50, sparsity_H: float = 0.,
                          max_rounds: int = 100, strengths: str = 'mu', tol: float = 1e-8,
@@ -637,15 +645,9 @@ class TransformInvariantNMF:
         them.  The rows must be distinct; the plain Frobenius objective only.  With ``strengths='solve'`` the strengths of
         every round are ``solve_detections(tol=, max_iterations=)``' -- the gains are then those of the true minimiser;
         ``n_iterations`` is unused and ``sparsity_H`` must be 0."""
-        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
-            raise NotImplementedError('prune_detections covers the plain Frobenius objective (beta_loss 2, no weights)')
-        if (isinstance(min_gain, (bool, np.bool_)) or not isinstance(min_gain, numbers.Real)
-                or not math.isfinite(min_gain)):
-            raise ValueError(f'min_gain must be a finite number, not {min_gain!r}')
-        if (isinstance(max_rounds, (bool, np.bool_)) or not isinstance(max_rounds, numbers.Integral)
-                or max_rounds < 0):
-            raise ValueError(f'max_rounds must be an int >= 0, not {max_rounds!r}')
-        mode = getattr(self._backend, '_reconstruction_mode', 'valid')
+        self._plain_frobenius_only('prune_detections')
+        _args.finite_number('min_gain', min_gain)
+        _args.int_at_least('max_rounds', max_rounds, 0)
         fitted = self._list_strengths('prune_detections', strengths, n_iterations, sparsity_H, tol, max_iterations)
         rounds = 0
         while True:
@@ -654,7 +656,7 @@ class TransformInvariantNMF:
             if rounds >= max_rounds:
                 break
             lo, hi = event_boxes(det.shift, self.atom_shape, self._V.shape[2:], tuple(int(x) for x in self._H.shape[2:]),
-                                 mode)
+                                 self._mode)
             keep = np.ones(len(det), dtype=bool)
             candidates = np.flatnonzero(gains < min_gain)
             dropped = {}   # per sample: the boxes dropped in this round
@@ -700,19 +702,14 @@ class TransformInvariantNMF:
         With ``strengths='solve'`` the list's strengths after every round, and at the end, are
         ``solve_detections(tol=, max_iterations=)``' -- orthogonal matching pursuit; ``refit_iterations`` and
         ``n_iterations`` are unused and ``sparsity_H`` must be 0."""
-        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
-            raise NotImplementedError('pursue_detections covers the plain Frobenius objective (beta_loss 2, no weights)')
-        if (isinstance(min_gain, (bool, np.bool_)) or not isinstance(min_gain, numbers.Real)
-                or not math.isfinite(min_gain) or not min_gain > 0):
-            raise ValueError(f'min_gain must be a finite number > 0, not {min_gain!r}')
-        for name, value in (('max_rounds', max_rounds), ('refit_iterations', refit_iterations),
-                            ('n_iterations', n_iterations)) + ((('max_events', max_events),) if max_events is not None
-                                                               else ()):
-            if isinstance(value, (bool, np.bool_)) or not isinstance(value, numbers.Integral) or value < 0:
-                raise ValueError(f'{name} must be an int >= 0, not {value!r}')
-        if (isinstance(sparsity_H, (bool, np.bool_)) or not isinstance(sparsity_H, numbers.Real)
-                or not math.isfinite(sparsity_H) or sparsity_H < 0):
-            raise ValueError(f'sparsity_H must be a finite number >= 0, not {sparsity_H!r}')
+        self._plain_frobenius_only('pursue_detections')
+        _args.finite_number('min_gain', min_gain, '> 0')
+        _args.int_at_least('max_rounds', max_rounds, 0)
+        _args.int_at_least('refit_iterations', refit_iterations, 0)
+        _args.int_at_least('n_iterations', n_iterations, 0)
+        if max_events is not None:   # (None is no limit; the message does not offer it)
+            _args.int_at_least('max_events', max_events, 0)
+        _args.finite_number('sparsity_H', sparsity_H, '>= 0')
         fitted = self._list_strengths('pursue_detections', strengths, n_iterations, sparsity_H, tol, max_iterations)
         solve = (float(tol), int(max_iterations)) if strengths == 'solve' else None
         k = len(self.atom_shape)
@@ -720,49 +717,22 @@ class TransformInvariantNMF:
             start = Detections(sample=np.zeros(0, dtype=np.int64), atom=np.zeros(0, dtype=np.int64),
                                transform=np.zeros(0, dtype=np.int64), shift=np.zeros((0, k), dtype=np.int64),
                                origin=np.zeros((0, k), dtype=np.int64), strength=np.zeros(0))
-        sample, plane, shift, strength = self._events_of(start, distinct=True)
-        mode = getattr(self._backend, '_reconstruction_mode', 'valid')
+        rows = self._events_of(start, distinct=True)
         max_events = None if max_events is None else int(max_events)
-        hook = getattr(self._backend, 'pursue_events', None)
         more = {} if solve is None else {'solve': solve}   # (a hook without the keyword keeps serving strengths='mu')
-        if hook is not None:
-            sample, plane, shift, strength, history = hook(
-                self._V, self._W_dict, sample, plane, shift, strength, float(min_gain), max_events=max_events,
-                max_rounds=int(max_rounds), refit_iterations=int(refit_iterations), eps=self.eps, **more)
-        else:
-            sample, plane, shift, strength, history = pursuit_numpy(
-                self._backend.to_ndarray(self._W_dict), self._V.shape[2:], int(self._H.shape[0]), mode, sample, plane, shift,
-                strength, self._local_V(), float(min_gain), max_events=max_events, max_rounds=int(max_rounds),
-                refit_iterations=int(refit_iterations), eps=self.eps, **more)
-        self.pursuit_history_ = history
-        sample = np.asarray(sample, dtype=np.int64)
-        if self._shuffle_idx is not None:   # (the inverse of _events_of: internal sample a[i] is shown at place i)
-            place = np.empty(int(self._H.shape[0]), dtype=np.int64)
-            place[np.argsort(self._shuffle_idx)] = np.arange(int(self._H.shape[0]))
-            sample = place[sample]
-        sample = sample + int(getattr(self._backend, 'shard', (0, 0))[0])
-        plane, shift = np.asarray(plane, dtype=np.int64), np.asarray(shift, dtype=np.int64).reshape(len(sample), k)
-        offset = np.array([a - 1 if mode == 'valid' else 0 for a in self.atom_shape], dtype=np.int64)
-        T = self.n_transforms
-        det = Detections(sample=sample, atom=plane // T, transform=plane % T, shift=shift, origin=shift - offset,
-                         strength=np.asarray(strength))
-        det = fitted(det)
+        *rows, self.pursuit_history_ = self._on_events(
+            'pursue_events', pursuit_numpy, rows, float(min_gain), max_events=max_events, max_rounds=int(max_rounds),
+            refit_iterations=int(refit_iterations), eps=self.eps, **more)
+        det = fitted(self._rows_to_detections(*rows))
         return det, self.detection_gains(det)
 
     # -- detections moved: the landscape of the neighbouring shifts ----------------------------------------------------
     def _landscape(self, det, distinct: bool, who: str):
         """(a, b) ``[K, 3^k]`` float64 of the rows of ``det``, after the refusals and checks ``who`` shares with
         ``detection_gains``, and the rows in the backend's terms."""
-        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
-            raise NotImplementedError(f'{who} covers the plain Frobenius objective (beta_loss 2, no weights)')
-        rows = sample, plane, shift, strength = self._events_of(det, distinct=distinct)
-        hook = getattr(self._backend, 'event_landscape', None)
-        if hook is not None:
-            a, b = hook(self._V, self._W_dict, sample, plane, shift, strength)
-        else:
-            a, b = events_landscape_numpy(
-                self._backend.to_ndarray(self._W_dict), self._V.shape[2:], int(self._H.shape[0]),
-                getattr(self._backend, '_reconstruction_mode', 'valid'), sample, plane, shift, strength, self._local_V())
+        self._plain_frobenius_only(who)
+        rows = self._events_of(det, distinct=distinct)
+        a, b = self._on_events('event_landscape', events_landscape_numpy, rows)
         return np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64), rows
 
     def detection_landscape(self, det) -> Tuple[np.ndarray, np.ndarray]:
@@ -823,16 +793,9 @@ class TransformInvariantNMF:
         a process group every rank moves the rows of its own samples: the call is not collective.  With
         ``strengths='solve'`` the strengths of every round are ``solve_detections(tol=, max_iterations=)``';
         ``n_iterations`` is unused and ``sparsity_H`` must be 0."""
-        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
-            raise NotImplementedError('relocate_detections covers the plain Frobenius objective (beta_loss 2, no weights)')
-        if (isinstance(min_improvement, (bool, np.bool_)) or not isinstance(min_improvement, numbers.Real)
-                or not math.isfinite(min_improvement) or min_improvement < 0):
-            raise ValueError(f'min_improvement must be a finite number >= 0, not {min_improvement!r}')
-        if (isinstance(max_rounds, (bool, np.bool_)) or not isinstance(max_rounds, numbers.Integral)
-                or max_rounds < 0):
-            raise ValueError(f'max_rounds must be an int >= 0, not {max_rounds!r}')
-        mode = getattr(self._backend, '_reconstruction_mode', 'valid')
-        offset = np.array([a - 1 if mode == 'valid' else 0 for a in self.atom_shape], dtype=np.int64)
+        self._plain_frobenius_only('relocate_detections')
+        _args.finite_number('min_improvement', min_improvement, '>= 0')
+        _args.int_at_least('max_rounds', max_rounds, 0)
         fitted = self._list_strengths('relocate_detections', strengths, n_iterations, sparsity_H, tol, max_iterations)
         history, rounds = [], 0
         while True:
@@ -842,13 +805,13 @@ class TransformInvariantNMF:
             a, b, (sample, plane, shift, strength) = self._landscape(det, True, 'relocate_detections')
             hopped, target, h, n_candidates, total = relocation_hops(
                 sample, plane, shift, strength, a, b, self.atom_shape, self._V.shape[2:],
-                tuple(int(x) for x in self._H.shape[2:]), mode, float(min_improvement))
+                tuple(int(x) for x in self._H.shape[2:]), self._mode, float(min_improvement))
             history.append((n_candidates, len(hopped), total))
             if not len(hopped):
                 break
             shift, strength = np.array(det.shift, dtype=np.int64).reshape(len(det), -1), np.array(det.strength)
             shift[hopped], strength[hopped] = target, h.astype(strength.dtype)
-            det = dataclasses.replace(det, shift=shift, origin=shift - offset, strength=strength)
+            det = dataclasses.replace(det, shift=shift, origin=shift - self._origin_offset(), strength=strength)
             rounds += 1
         self.relocation_history_ = np.array(history, dtype=np.float64).reshape(len(history), 3)
         return det, self.detection_gains(det)
@@ -868,18 +831,10 @@ class TransformInvariantNMF:
     def _alternatives(self, det, over, distinct: bool, who: str):
         """(a, b) ``[K, n_alt]`` float64 of the rows of ``det``, after the refusals and checks ``who`` shares with
         ``detection_gains``, (n_alt, stride), and the rows in the backend's terms."""
-        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
-            raise NotImplementedError(f'{who} covers the plain Frobenius objective (beta_loss 2, no weights)')
-        rows = sample, plane, shift, strength = self._events_of(det, distinct=distinct)
+        self._plain_frobenius_only(who)
+        rows = self._events_of(det, distinct=distinct)
         n_alt, stride = self._alternative_set(over)
-        hook = getattr(self._backend, 'event_alternatives', None)
-        if hook is not None:
-            a, b = hook(self._V, self._W_dict, sample, plane, shift, strength, n_alt, stride)
-        else:
-            a, b = events_alternatives_numpy(
-                self._backend.to_ndarray(self._W_dict), self._V.shape[2:], int(self._H.shape[0]),
-                getattr(self._backend, '_reconstruction_mode', 'valid'), sample, plane, shift, strength, self._local_V(),
-                n_alt, stride)
+        a, b = self._on_events('event_alternatives', events_alternatives_numpy, rows, n_alt, stride)
         return np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64), (n_alt, stride), rows
 
     def detection_alternatives(self, det, over: str = 'transforms') -> Tuple[np.ndarray, np.ndarray]:
@@ -918,17 +873,10 @@ class TransformInvariantNMF:
         a process group every rank relabels the rows of its own samples: the call is not collective.  With
         ``strengths='solve'`` the strengths of every round are ``solve_detections(tol=, max_iterations=)``';
         ``n_iterations`` is unused and ``sparsity_H`` must be 0."""
-        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
-            raise NotImplementedError('relabel_detections covers the plain Frobenius objective (beta_loss 2, no weights)')
-        if self._H is not None and len(self.atom_shape) != 3:
-            self._alternative_set(over)
-        if (isinstance(min_improvement, (bool, np.bool_)) or not isinstance(min_improvement, numbers.Real)
-                or not math.isfinite(min_improvement) or min_improvement < 0):
-            raise ValueError(f'min_improvement must be a finite number >= 0, not {min_improvement!r}')
-        if (isinstance(max_rounds, (bool, np.bool_)) or not isinstance(max_rounds, numbers.Integral)
-                or max_rounds < 0):
-            raise ValueError(f'max_rounds must be an int >= 0, not {max_rounds!r}')
-        mode = getattr(self._backend, '_reconstruction_mode', 'valid')
+        if self._plain_frobenius_only('relabel_detections'):
+            self._alternative_set(over)   # (checked before the numbers; an unfitted model or a volume is refused first)
+        _args.finite_number('min_improvement', min_improvement, '>= 0')
+        _args.int_at_least('max_rounds', max_rounds, 0)
         T = self.n_transforms
         fitted = self._list_strengths('relabel_detections', strengths, n_iterations, sparsity_H, tol, max_iterations)
         history, rounds = [], 0
@@ -940,7 +888,7 @@ class TransformInvariantNMF:
                                                                                          'relabel_detections')
             hopped, target, h, n_candidates, total = relabel_hops(
                 sample, plane, shift, strength, a, b, n_alt, stride, self.atom_shape, self._V.shape[2:],
-                tuple(int(x) for x in self._H.shape[2:]), mode, float(min_improvement))
+                tuple(int(x) for x in self._H.shape[2:]), self._mode, float(min_improvement))
             history.append((n_candidates, len(hopped), total))
             if not len(hopped):
                 break
@@ -963,40 +911,30 @@ class TransformInvariantNMF:
         ``reconstruct_detections`` of the returned rows.  ``update_W=False`` is ``refit_detections``.  The rows must be
         distinct; the plain Frobenius objective only.  With a process group the call is collective: every rank calls with
         the detections of its own samples (possibly none) and the same ``n_iterations``."""
-        for name, flag in (('update_H', update_H), ('update_W', update_W)):
-            if not isinstance(flag, (bool, np.bool_)):
-                raise ValueError(f'{name} must be a bool, not {flag!r}')
+        _args.boolean('update_H', update_H)
+        _args.boolean('update_W', update_W)
         if not update_H and not update_W:
             raise ValueError('fit_detections: update_H and update_W are both off')
         if not update_W:
             return self.refit_detections(det, n_iterations, sparsity_H)
-        if self._H is not None and len(self.atom_shape) != 3 and (self._beta != 2. or self._weighted):
-            raise NotImplementedError('fit_detections covers the plain Frobenius objective (beta_loss 2, no weights)')
-        if (isinstance(n_iterations, (bool, np.bool_)) or not isinstance(n_iterations, numbers.Integral)
-                or n_iterations < 0):
-            raise ValueError(f'n_iterations must be an int >= 0, not {n_iterations!r}')
-        if (isinstance(sparsity_H, (bool, np.bool_)) or not isinstance(sparsity_H, numbers.Real)
-                or not math.isfinite(sparsity_H) or sparsity_H < 0):
-            raise ValueError(f'sparsity_H must be a finite number >= 0, not {sparsity_H!r}')
+        self._plain_frobenius_only('fit_detections')
+        _args.int_at_least('n_iterations', n_iterations, 0)
+        _args.finite_number('sparsity_H', sparsity_H, '>= 0')
         sample, plane, shift, strength = self._events_of(det, distinct=True)
-        mode = getattr(self._backend, '_reconstruction_mode', 'valid')
         hook = getattr(self._backend, 'fit_events', None)
         if hook is not None:
             new = self._backend.to_ndarray(hook(self._V, self._W, self._W_eff, self._transforms, sample, plane, shift,
                                                 strength, int(n_iterations), update_H=bool(update_H), update_W=True,
                                                 sparsity=float(sparsity_H), eps=self.eps))
         else:
+            W, *where = self._host_problem(self._W)
             W, new = events_fit_numpy(
-                self._backend.to_ndarray(self._W), self._transforms, self._V.shape[2:], int(self._H.shape[0]), mode, sample,
-                plane, shift, strength, self._local_V(), int(n_iterations), update_H=bool(update_H), update_W=True,
-                sparsity=float(sparsity_H), eps=self.eps,
+                W, self._transforms, *where, sample, plane, shift, strength, self._local_V(), int(n_iterations),
+                update_H=bool(update_H), update_W=True, sparsity=float(sparsity_H), eps=self.eps,
                 normalize=lambda arr: self._backend.normalize(arr, axis=self._axes_W_normalization))
             self._W[...] = W
             self._expand_W()
-        offset = np.array([a - 1 if mode == 'valid' else 0 for a in self.atom_shape], dtype=np.int64)
-        as_rows = lambda x: np.asarray(x).astype(np.int64).reshape(len(new))   # noqa: E731
-        return Detections(sample=as_rows(det.sample), atom=as_rows(det.atom), transform=as_rows(det.transform),
-                          shift=shift, origin=shift - offset, strength=new)
+        return self._with_strengths(det, shift, new)
 
     def sample_objective(self) -> np.ndarray:
         """[N] float64: each sample's share of ``objective()``, in the order of ``V`` (with a process group: this rank's
@@ -1016,12 +954,7 @@ class TransformInvariantNMF:
         samples, and the call is not collective).  On a backend with ``atom_terms`` one pass over the activations where they
         live; any other backend's are scored on the host.  The Frobenius objective only; ``W``, ``H`` and ``V`` are not
         touched."""
-        if self._H is None:
-            raise RuntimeError('the atom gains of a model need a fitted model: call fit first')
-        if self._beta != 2.:
-            raise NotImplementedError('atom_gains covers the Frobenius objective (beta_loss 2), with or without weights')
-        if len(self.atom_shape) == 3:
-            raise NotImplementedError('atom gains: 1 or 2 shift axes only')
+        self._atom_refusals()
         hook = getattr(self._backend, 'atom_terms', None)
         if hook is not None:
             a, b = hook(self._V, self._W_dict, self._H, self.n_transforms)
@@ -1031,8 +964,7 @@ class TransformInvariantNMF:
                 n0 = int(getattr(self._backend, 'shard', (0, 0))[0])
                 G = G[n0:n0 + int(self._H.shape[0])]
             a, b = atom_terms_numpy(self._backend.to_ndarray(self._W_dict), self._backend.to_ndarray(self._H),
-                                    getattr(self._backend, '_reconstruction_mode', 'valid'), self._local_V(), G,
-                                    self.n_transforms)
+                                    self._mode, self._local_V(), G, self.n_transforms)
         a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
         if self._shuffle_idx is not None:
             order = np.argsort(self._shuffle_idx)
@@ -1046,8 +978,7 @@ class TransformInvariantNMF:
         ``per_sample=True`` ``[N, n_atoms]`` in the order of ``H``.  Not collective: with a process group each rank reports
         its own samples and the sum over the ranks is the caller's, as for ``detection_errors``.  The Frobenius objective,
         with or without weights."""
-        if not isinstance(per_sample, (bool, np.bool_)):
-            raise ValueError(f'per_sample must be a bool, not {per_sample!r}')
+        _args.boolean('per_sample', per_sample)
         a, b = self.atom_terms()
         gain = a + 0.5 * b
         return gain if per_sample else gain.sum(axis=0)
@@ -1078,8 +1009,7 @@ class TransformInvariantNMF:
                 n0 = int(getattr(self._backend, 'shard', (0, 0))[0])
                 G = G[n0:n0 + int(self._H.shape[0])]
             a, B = atom_gram_numpy(self._backend.to_ndarray(self._W_dict), self._backend.to_ndarray(self._H),
-                                   getattr(self._backend, '_reconstruction_mode', 'valid'), self._local_V(), G,
-                                   self.n_transforms)
+                                   self._mode, self._local_V(), G, self.n_transforms)
         a, B = np.asarray(a, dtype=np.float64), np.asarray(B, dtype=np.float64)
         if self._shuffle_idx is not None:
             order = np.argsort(self._shuffle_idx)
@@ -1092,8 +1022,7 @@ class TransformInvariantNMF:
         ``[N, n_atoms, n_atoms]`` in the order of ``H``.  Symmetric; its diagonal is ``b`` of ``atom_terms``.  On a backend
         with ``atom_gram`` one pass over the activations where they live.  Not collective: with a process group each rank
         reports its own samples.  The Frobenius objective, with or without weights; ``W``, ``H``, ``V`` are not touched."""
-        if not isinstance(per_sample, (bool, np.bool_)):
-            raise ValueError(f'per_sample must be a bool, not {per_sample!r}')
+        _args.boolean('per_sample', per_sample)
         B = self._atom_gram()[1]
         return B if per_sample else B.sum(axis=0)
 
@@ -1115,7 +1044,7 @@ class TransformInvariantNMF:
         except TypeError:
             raise ValueError(f'atoms must be a sequence of distinct ints in [0, {self.n_atoms}), not {atoms!r}') from None
         for m in items:
-            if isinstance(m, (bool, np.bool_)) or not isinstance(m, numbers.Integral) or not 0 <= m < self.n_atoms:
+            if not _args.is_int(m) or not 0 <= m < self.n_atoms:
                 raise ValueError(f'atoms must be distinct ints in [0, {self.n_atoms}), not {m!r}')
         if len(set(int(m) for m in items)) != len(items):
             raise ValueError(f'atoms must be distinct: {items!r}')
@@ -1134,8 +1063,7 @@ class TransformInvariantNMF:
         held: the minimiser of ``E(s)``, ``B s = a + B 1``, over ``s >= 0`` unless ``nonnegative=False`` (an active-set
         solve on the host) -- after a fit under ``sparsity_H``, the shrinkage undone for all atoms at once.  Dead atoms get
         scale 1; a singular block, such as two exact duplicates, its minimum-norm solution."""
-        if not isinstance(nonnegative, (bool, np.bool_)):
-            raise ValueError(f'nonnegative must be a bool, not {nonnegative!r}')
+        _args.boolean('nonnegative', nonnegative)
         a, B = self._atom_gram()
         return gram_scales(a.sum(axis=0), B.sum(axis=0), bool(nonnegative))
 
@@ -1170,8 +1098,7 @@ class TransformInvariantNMF:
         over the model as it stands once ``order[:k + 1]`` are gone.  ``rescale=True``: the remaining atoms are rescaled
         optimally (``s >= 0``) at every step, so ``rise`` may begin below zero.  One pass over H, then host algebra; the
         model is not touched."""
-        if not isinstance(rescale, (bool, np.bool_)):
-            raise ValueError(f'rescale must be a bool, not {rescale!r}')
+        _args.boolean('rescale', rescale)
         a, B = self._atom_gram()
         return gram_elimination(a.sum(axis=0), B.sum(axis=0), bool(rescale))
 
@@ -1179,20 +1106,15 @@ class TransformInvariantNMF:
     @staticmethod
     def _convergence_args(objective_every, tol) -> Tuple[Optional[int], Optional[float]]:
         """(objective_every, tol) checked; ``tol`` alone records every 10 iterations (scikit-learn's cadence)."""
+        # (a number is converted before its range is checked: the message shows the plain float or int)
         if tol is not None:
-            if isinstance(tol, (bool, np.bool_)) or not isinstance(tol, numbers.Real):
-                raise ValueError(f'tol must be a finite number >= 0, not {tol!r}')
-            tol = float(tol)
-            if not math.isfinite(tol) or tol < 0:
-                raise ValueError(f'tol must be a finite number >= 0, not {tol!r}')
+            tol = float(tol) if _args.is_real(tol) else tol
+            _args.finite_number('tol', tol, '>= 0')
             if objective_every is None:
                 objective_every = 10
         if objective_every is not None:
-            if isinstance(objective_every, (bool, np.bool_)) or not isinstance(objective_every, numbers.Integral):
-                raise ValueError(f'objective_every must be an int >= 1, not {objective_every!r}')
-            objective_every = int(objective_every)
-            if objective_every < 1:
-                raise ValueError(f'objective_every must be an int >= 1, not {objective_every!r}')
+            objective_every = int(objective_every) if _args.is_int(objective_every) else objective_every
+            _args.int_at_least('objective_every', objective_every, 1)
         return objective_every, tol
 
     def _begin_history(self) -> None:

@@ -939,6 +939,34 @@ class HIP_Backend(Backend):
                                  dim=1).to(torch.int32).contiguous()
         return images, cell_start, events
 
+    def _events_call(self, name: str, W: torch.Tensor, *args, mode: bool = True) -> None:
+        """tnmf_hip_<name>(ctx, the geometry of this rank's samples and the planes of ``W``, the mode when the entry point
+        takes one, *args, stream) under the timeline span ``name``."""
+        with self._timed(name):
+            head = (self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0]))) + ((self._mode,) if mode else ())
+            _lib.check(getattr(self._lib, 'tnmf_hip_' + name)(*head, *args, self._stream()), 'tnmf_hip_' + name)
+
+    def _unweighted_only(self, who: str) -> None:
+        if self._G_dev is not None:
+            raise NotImplementedError(f'{who} is unweighted')
+
+    def _prepared_events(self, who: Optional[str], n_planes: int, sample, plane, shift, strength,
+                         render: Optional[torch.Tensor] = None):
+        """What a hook on a list begins with -- the refusal of a weighted fit in the name of ``who`` (None: the hook
+        reads no samples), _check_events, event_list -> (images, cell_start, events, strength on the device, R), R the render
+        of the list with the dictionary ``render`` (None without one)."""
+        if who is not None:
+            self._unweighted_only(who)
+        sample, plane, shift, strength = self._check_events(n_planes, sample, plane, shift, strength)
+        images, cell_start, events = self.event_list(sample, plane, shift)
+        R = None if render is None else self.render_event_list(render, images, cell_start, strength)
+        return images, cell_start, events, strength, R
+
+    def _new_ab_mag(self, shape, with_magnitude: bool):
+        """(a, b, mag): float64 outputs of ``shape`` on the device, mag None unless asked for."""
+        a, b = (torch.empty(shape, dtype=torch.float64, device=self._device) for _ in range(2))
+        return a, b, torch.empty(shape, dtype=torch.float64, device=self._device) if with_magnitude else None
+
     def render_event_list(self, W: torch.Tensor, images: torch.Tensor, cell_start: torch.Tensor, strength: torch.Tensor,
                           R: Optional[torch.Tensor] = None) -> torch.Tensor:
         """R[n_local, C, *D] of the image list (event_list) and the strengths -> tnmf_hip_events_render (into R when
@@ -949,11 +977,8 @@ class HIP_Backend(Backend):
         if R is None:
             R = torch.empty(shape, dtype=self._torch_dtype, device=self._device)
         assert R.is_contiguous() and tuple(R.shape) == shape and R.dtype == self._torch_dtype
-        with self._timed('events_render'):
-            _lib.check(self._lib.tnmf_hip_events_render(
-                self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0])), _ptr(W), _ptr(images),
-                images.shape[0], _ptr(cell_start), _ptr(strength), strength.numel(), _ptr(R), self._stream()),
-                'tnmf_hip_events_render')
+        self._events_call('events_render', W, _ptr(W), _ptr(images), images.shape[0], _ptr(cell_start), _ptr(strength),
+                          strength.numel(), _ptr(R), mode=False)
         return R
 
     def update_event_list(self, W: torch.Tensor, events: torch.Tensor, strength: torch.Tensor, R: torch.Tensor,
@@ -961,29 +986,22 @@ class HIP_Backend(Backend):
         """One multiplicative update of the strengths in place, R being their render -> tnmf_hip_events_update."""
         self._check_W(W)
         assert strength.is_contiguous() and strength.dtype == self._torch_dtype and events.shape[0] == strength.numel()
-        with self._timed('events_update'):
-            _lib.check(self._lib.tnmf_hip_events_update(
-                self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0])), self._mode, _ptr(W), _ptr(events),
-                _ptr(strength), strength.numel(), _ptr(self._V_dev), _ptr(R), float(eps), float(sparsity),
-                self._stream()), 'tnmf_hip_events_update')
+        self._events_call('events_update', W, _ptr(W), _ptr(events), _ptr(strength), strength.numel(), _ptr(self._V_dev),
+                          _ptr(R), float(eps), float(sparsity))
 
     def render_events(self, W: torch.Tensor, sample, plane, shift, strength) -> torch.Tensor:
         """R[n_local, C, *D]: what the events (local sample, plane of W, shift in H of this mode, strength) reconstruct --
         the reconstruction of the activations that hold the strengths at the events and zero elsewhere, without those
         activations.  Duplicate events add up."""
-        sample, plane, shift, strength = self._check_events(W.shape[0], sample, plane, shift, strength)
-        images, cell_start, _ = self.event_list(sample, plane, shift)
-        return self.render_event_list(W, images, cell_start, strength)
+        return self._prepared_events(None, W.shape[0], sample, plane, shift, strength, render=W)[-1]
 
     def refit_events(self, V, W: torch.Tensor, sample, plane, shift, strength, n_iterations: int, sparsity: float = 0.,
                      eps: float = 1e-9) -> torch.Tensor:
         """[K] strengths after ``n_iterations`` multiplicative updates on the fixed support, W fixed, against the resident
         samples (`V` is the array given to initialize(), as for the other hooks): per step one render and one update.
         The plain Frobenius objective; the events must be distinct in (sample, plane, shift)."""
-        if self._G_dev is not None:
-            raise NotImplementedError('refit_events is unweighted')
-        sample, plane, shift, strength = self._check_events(W.shape[0], sample, plane, shift, strength)
-        images, cell_start, events = self.event_list(sample, plane, shift)
+        images, cell_start, events, strength, _ = self._prepared_events('refit_events', W.shape[0], sample, plane, shift,
+                                                                        strength)
         strength = strength.clone()
         R = torch.empty_like(self._V_dev)
         for _ in range(int(n_iterations)):
@@ -1000,22 +1018,15 @@ class HIP_Backend(Backend):
         K = strength.numel()
         gain = torch.empty(K, dtype=torch.float64, device=self._device)
         mag = torch.empty(K, dtype=torch.float64, device=self._device) if with_magnitude else None
-        with self._timed('events_gain'):
-            _lib.check(self._lib.tnmf_hip_events_gain(
-                self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0])), self._mode, _ptr(W), _ptr(events),
-                _ptr(strength), K, _ptr(self._V_dev), _ptr(R), _ptr(gain), _ptr(mag), self._stream()),
-                'tnmf_hip_events_gain')
+        self._events_call('events_gain', W, _ptr(W), _ptr(events), _ptr(strength), K, _ptr(self._V_dev), _ptr(R), _ptr(gain),
+                          _ptr(mag))
         return (gain, mag) if with_magnitude else gain
 
     def event_gains(self, V, W: torch.Tensor, sample, plane, shift, strength) -> np.ndarray:
         """[K] float64 on the host: per event the Frobenius energy of the list without it minus that of the list, against
         the resident samples (`V` is the array given to initialize(), as for the other hooks): one render of the list and
         one gather per event; only the K doubles are copied.  Duplicate events are scored each against the whole list."""
-        if self._G_dev is not None:
-            raise NotImplementedError('event_gains is unweighted')
-        sample, plane, shift, strength = self._check_events(W.shape[0], sample, plane, shift, strength)
-        images, cell_start, events = self.event_list(sample, plane, shift)
-        R = self.render_event_list(W, images, cell_start, strength)
+        _, _, events, strength, R = self._prepared_events('event_gains', W.shape[0], sample, plane, shift, strength, render=W)
         return self.gain_event_list(W, events, strength, R).cpu().numpy()
 
     def landscape_event_list(self, W: torch.Tensor, events: torch.Tensor, strength: torch.Tensor, R: torch.Tensor,
@@ -1026,15 +1037,10 @@ class HIP_Backend(Backend):
         self._check_W(W)
         assert strength.is_contiguous() and strength.dtype == self._torch_dtype and events.shape[0] == strength.numel()
         assert R.is_contiguous() and R.dtype == self._torch_dtype and tuple(R.shape) == tuple(self._V_dev.shape)
-        K, nb = strength.numel(), 3 ** len(self.atom_shape)
-        a = torch.empty((K, nb), dtype=torch.float64, device=self._device)
-        b = torch.empty((K, nb), dtype=torch.float64, device=self._device)
-        mag = torch.empty((K, nb), dtype=torch.float64, device=self._device) if with_magnitude else None
-        with self._timed('events_landscape'):
-            _lib.check(self._lib.tnmf_hip_events_landscape(
-                self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0])), self._mode, _ptr(W), _ptr(events),
-                _ptr(strength), K, _ptr(self._V_dev), _ptr(R), _ptr(a), _ptr(b), _ptr(mag), self._stream()),
-                'tnmf_hip_events_landscape')
+        K = strength.numel()
+        a, b, mag = self._new_ab_mag((K, 3 ** len(self.atom_shape)), with_magnitude)
+        self._events_call('events_landscape', W, _ptr(W), _ptr(events), _ptr(strength), K, _ptr(self._V_dev), _ptr(R),
+                          _ptr(a), _ptr(b), _ptr(mag))
         return (a, b, mag) if with_magnitude else (a, b)
 
     def event_landscape(self, V, W: torch.Tensor, sample, plane, shift, strength):
@@ -1042,11 +1048,8 @@ class HIP_Backend(Backend):
         with the residual of the list without the event, and its norm, against the resident samples (`V` is the array given
         to initialize(), as for the other hooks): one render of the list and one kernel; only the 2 * K * 3^k doubles are
         copied.  Duplicate events put back only themselves."""
-        if self._G_dev is not None:
-            raise NotImplementedError('event_landscape is unweighted')
-        sample, plane, shift, strength = self._check_events(W.shape[0], sample, plane, shift, strength)
-        images, cell_start, events = self.event_list(sample, plane, shift)
-        R = self.render_event_list(W, images, cell_start, strength)
+        _, _, events, strength, R = self._prepared_events('event_landscape', W.shape[0], sample, plane, shift, strength,
+                                                          render=W)
         a, b = self.landscape_event_list(W, events, strength, R)
         return a.cpu().numpy(), b.cpu().numpy()
 
@@ -1060,15 +1063,9 @@ class HIP_Backend(Backend):
         assert strength.is_contiguous() and strength.dtype == self._torch_dtype and events.shape[0] == strength.numel()
         assert R.is_contiguous() and R.dtype == self._torch_dtype and tuple(R.shape) == tuple(self._V_dev.shape)
         K, n_alt, stride = strength.numel(), int(n_alt), int(stride)
-        shape = (K, max(n_alt, 0))
-        a = torch.empty(shape, dtype=torch.float64, device=self._device)
-        b = torch.empty(shape, dtype=torch.float64, device=self._device)
-        mag = torch.empty(shape, dtype=torch.float64, device=self._device) if with_magnitude else None
-        with self._timed('events_alternatives'):
-            _lib.check(self._lib.tnmf_hip_events_alternatives(
-                self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0])), self._mode, _ptr(W), _ptr(events),
-                _ptr(strength), K, _ptr(self._V_dev), _ptr(R), n_alt, stride, _ptr(a), _ptr(b), _ptr(mag),
-                self._stream()), 'tnmf_hip_events_alternatives')
+        a, b, mag = self._new_ab_mag((K, max(n_alt, 0)), with_magnitude)
+        self._events_call('events_alternatives', W, _ptr(W), _ptr(events), _ptr(strength), K, _ptr(self._V_dev), _ptr(R),
+                          n_alt, stride, _ptr(a), _ptr(b), _ptr(mag))
         return (a, b, mag) if with_magnitude else (a, b)
 
     def event_alternatives(self, V, W: torch.Tensor, sample, plane, shift, strength, n_alt: int, stride: int):
@@ -1076,11 +1073,8 @@ class HIP_Backend(Backend):
         at the event's shift with the residual of the list without the event, and its norm, against the resident samples
         (`V` is the array given to initialize(), as for the other hooks): one render of the list and one kernel; only the
         2 * K * n_alt doubles are copied.  Duplicate events put back only themselves."""
-        if self._G_dev is not None:
-            raise NotImplementedError('event_alternatives is unweighted')
-        sample, plane, shift, strength = self._check_events(W.shape[0], sample, plane, shift, strength)
-        images, cell_start, events = self.event_list(sample, plane, shift)
-        R = self.render_event_list(W, images, cell_start, strength)
+        _, _, events, strength, R = self._prepared_events('event_alternatives', W.shape[0], sample, plane, shift, strength,
+                                                          render=W)
         a, b = self.alternatives_event_list(W, events, strength, R, n_alt, stride)
         return a.cpu().numpy(), b.cpu().numpy()
 
@@ -1096,16 +1090,13 @@ class HIP_Backend(Backend):
         kernels alone ('events_pairs', 'events_gram') and the torch work on the lists under 'events_gram_lists'."""
         self._check_W(W)
         K = int(events.shape[0])
-        g = self._geom(self.n_local_samples, W.shape[0])
         every = torch.arange(K, dtype=torch.int64, device=self._device)
         count = torch.zeros(1, dtype=torch.int64, device=self._device)
         cap = max(4096, 16 * int(images.shape[0])) if capacity is None else int(capacity)
         for _ in range(2):   # a guess, and once more with the count when it did not fit
             keys = torch.empty(cap, dtype=torch.int64, device=self._device)
-            with self._timed('events_pairs'):
-                _lib.check(self._lib.tnmf_hip_events_pairs(self._ctx, ctypes.byref(g), _ptr(images), images.shape[0],
-                                                           _ptr(cell_start), _ptr(events), K, _ptr(keys), cap, _ptr(count),
-                                                           self._stream()), 'tnmf_hip_events_pairs')
+            self._events_call('events_pairs', W, _ptr(images), images.shape[0], _ptr(cell_start), _ptr(events), K, _ptr(keys),
+                              cap, _ptr(count), mode=False)
             total = int(count.item())
             if total <= cap:
                 break
@@ -1118,10 +1109,7 @@ class HIP_Backend(Backend):
             rj = upper - ri * K
             ri32, rj32 = ri.to(torch.int32).contiguous(), rj.to(torch.int32).contiguous()
             val = torch.empty(upper.numel(), dtype=torch.float64, device=self._device)
-        with self._timed('events_gram'):
-            _lib.check(self._lib.tnmf_hip_events_gram(self._ctx, ctypes.byref(g), self._mode, _ptr(W), _ptr(events), K,
-                                                      _ptr(ri32), _ptr(rj32), upper.numel(), _ptr(val), self._stream()),
-                       'tnmf_hip_events_gram')
+        self._events_call('events_gram', W, _ptr(W), _ptr(events), K, _ptr(ri32), _ptr(rj32), upper.numel(), _ptr(val))
         with self._timed('events_gram_lists'):
             # both triangles from the one value of a pair; a candidate whose value is exactly 0 is dropped
             live = val[K:] != 0
@@ -1142,10 +1130,7 @@ class HIP_Backend(Backend):
         self._check_W(W)
         K = int(events.shape[0])
         c = torch.empty(K, dtype=torch.float64, device=self._device)
-        with self._timed('events_project'):
-            _lib.check(self._lib.tnmf_hip_events_project(
-                self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0])), self._mode, _ptr(W), _ptr(events), K,
-                _ptr(self._V_dev), _ptr(c), self._stream()), 'tnmf_hip_events_project')
+        self._events_call('events_project', W, _ptr(W), _ptr(events), K, _ptr(self._V_dev), _ptr(c))
         return c
 
     def nnls_event_list(self, csr, c: torch.Tensor, start: torch.Tensor, tol: float, max_iterations: int,
@@ -1178,10 +1163,8 @@ class HIP_Backend(Backend):
         the given ones: the lists, the Gram matrix, the projection, the solver -- no render of the sample frame.  info:
         iterations, kkt, converged, nnz, history [checks, 2] (iteration, kkt).  The events must be distinct.  With a process
         group every rank solves its own samples: rows of different samples never couple, so there is no collective."""
-        if self._G_dev is not None:
-            raise NotImplementedError('solve_events is unweighted')
-        sample, plane, shift, strength = self._check_events(W.shape[0], sample, plane, shift, strength)
-        images, cell_start, events = self.event_list(sample, plane, shift)
+        images, cell_start, events, strength, _ = self._prepared_events('solve_events', W.shape[0], sample, plane, shift,
+                                                                        strength)
         csr = self.gram_event_list(W, images, cell_start, events)
         c = self.project_event_list(W, events)
         return self.nnls_event_list(csr, c, strength, tol, max_iterations, check_every)
@@ -1287,10 +1270,8 @@ class HIP_Backend(Backend):
         ||V - R(list)||^2 = ||V||^2 - 2 c'h + h'Gh in double from c, G, h and the samples' own energy -- no render --, not
         below 0.  d and b are float64 on the device, the energy a float.  The events must be distinct.  With a process
         group every rank takes its own samples: there is no collective."""
-        if self._G_dev is not None:
-            raise NotImplementedError('event_errors is unweighted')
-        sample, plane, shift, strength = self._check_events(W.shape[0], sample, plane, shift, strength)
-        images, cell_start, events = self.event_list(sample, plane, shift)
+        images, cell_start, events, strength, _ = self._prepared_events('event_errors', W.shape[0], sample, plane, shift,
+                                                                        strength)
         csr = self.gram_event_list(W, images, cell_start, events)
         c = self.project_event_list(W, events)
         h = strength.to(torch.float64)
@@ -1315,10 +1296,7 @@ class HIP_Backend(Backend):
         if len(self.atom_shape) == 3:
             raise NotImplementedError('events: 1 or 2 shift axes only')
         b = torch.empty((W.shape[0],) + self._transform_shape, dtype=torch.float64, device=self._device)
-        with self._timed('events_norms'):
-            _lib.check(self._lib.tnmf_hip_events_norms(
-                self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0])), self._mode, _ptr(W), _ptr(b),
-                self._stream()), 'tnmf_hip_events_norms')
+        self._events_call('events_norms', W, _ptr(W), _ptr(b))
         return b
 
     def pursuit_buffers(self, n_planes: int):
@@ -1381,11 +1359,8 @@ class HIP_Backend(Backend):
         strength = torch.empty(K, dtype=self._torch_dtype, device=self._device)
         gain = torch.empty(K, dtype=torch.float64, device=self._device)
         mag = torch.empty(K, dtype=torch.float64, device=self._device) if with_magnitude else None
-        with self._timed('pursuit_pick'):
-            _lib.check(self._lib.tnmf_hip_pursuit_pick(
-                self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0])), self._mode, _ptr(W), _ptr(idx), K,
-                _ptr(self._V_dev), _ptr(R), _ptr(events), _ptr(strength), _ptr(gain), _ptr(mag), self._stream()),
-                'tnmf_hip_pursuit_pick')
+        self._events_call('pursuit_pick', W, _ptr(W), _ptr(idx), K, _ptr(self._V_dev), _ptr(R), _ptr(events), _ptr(strength),
+                          _ptr(gain), _ptr(mag))
         return (events, strength, gain, mag) if with_magnitude else (events, strength, gain)
 
     def pursue_events(self, V, W: torch.Tensor, sample, plane, shift, strength, min_gain: float,
@@ -1397,8 +1372,7 @@ class HIP_Backend(Backend):
         pick_events for the kept ones and refit_events for the list; only candidates and kept rows cross to the host.  The
         resident samples and the model's activations are left as they are.  The plain Frobenius objective.  With
         ``solve = (tol, max_iterations)`` the list's strengths of a round are solve_events', not refit_events'."""
-        if self._G_dev is not None:
-            raise NotImplementedError('pursue_events is unweighted')
+        self._unweighted_only('pursue_events')
         P, k = int(W.shape[0]), len(self.atom_shape)
         sample, plane, shift, strength = self._check_events(P, sample, plane, shift, strength)
         b = self.event_norms(W)
@@ -1459,11 +1433,8 @@ class HIP_Backend(Backend):
         assert by_plane.numel() == strength.numel() and plane_start.numel() == W.shape[0] + 1
         assert R.is_contiguous() and R.dtype == self._torch_dtype and tuple(R.shape) == tuple(self._V_dev.shape)
         negpos = torch.empty((2,) + tuple(W.shape), dtype=W.dtype, device=W.device)
-        with self._timed('events_grad_W'):
-            _lib.check(self._lib.tnmf_hip_events_grad_W(
-                self._ctx, ctypes.byref(self._geom(self.n_local_samples, W.shape[0])), self._mode, _ptr(events),
-                _ptr(by_plane), _ptr(plane_start), _ptr(strength), strength.numel(), _ptr(self._V_dev), _ptr(R),
-                _ptr(workspace), _ptr(negpos), self._stream()), 'tnmf_hip_events_grad_W')
+        self._events_call('events_grad_W', W, _ptr(events), _ptr(by_plane), _ptr(plane_start), _ptr(strength),
+                          strength.numel(), _ptr(self._V_dev), _ptr(R), _ptr(workspace), _ptr(negpos))
         return negpos
 
     def update_W_event_list(self, W: torch.Tensor, W_eff: Optional[torch.Tensor], transforms, negpos_eff: torch.Tensor,
@@ -1494,12 +1465,11 @@ class HIP_Backend(Backend):
         zero off the support), W and W_eff updated in place (W_eff is None without transforms).  The plain Frobenius
         objective.  With a process group the calls are collective: every rank calls with its own events (possibly none) and
         the same ``n_iterations``."""
-        if self._G_dev is not None:
-            raise NotImplementedError('fit_events is unweighted')
         D = W if transforms is None else W_eff
-        sample, plane, shift, strength = self._check_events(D.shape[0], sample, plane, shift, strength)
-        images, cell_start, events = self.event_list(sample, plane, shift)
-        lists = self.event_plane_list(plane, D.shape[0]) if update_W else None
+        images, cell_start, events, strength, _ = self._prepared_events('fit_events', D.shape[0], sample, plane, shift,
+                                                                        strength)
+        # (column 1 of the rows: the checked planes)
+        lists = self.event_plane_list(events[:, 1].to(torch.int64), D.shape[0]) if update_W else None
         strength = strength.clone()
         R = torch.empty_like(self._V_dev)
         for _ in range(int(n_iterations)):
