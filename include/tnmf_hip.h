@@ -879,6 +879,84 @@ int tnmf_hip_events_inverse_diag(tnmf_hip_ctx *ctx, long long n_rows, long long 
                                  double *scratch /* may be NULL */, long long scratch_doubles, double *d_out /* double */,
                                  int *status_out, void *stream);
 
+/* ---- patches: the data under each event, and how an atom's occurrences vary (ABI 8, additive: the version stays 8) -----------
+ * tnmf_hip_events_grad_W sums the patches of a plane's events into one gradient and keeps the sum alone.  These two entries
+ * keep the patches themselves -- the "waveforms" of a spike sorter, the cut-outs of a motif finder -- and their second
+ * moments per atom: the spread that says where one atom should be two, as the atom Gram says where two atoms are one.
+ *
+ * For an event e = (n, p, u, h_e) with the images q_i of the table of "events: render, refit and learn" the signal s is one
+ * of three, formed in double, and the PATCH is its gather under the images:
+ *   TNMF_PATCH_DATA      s = (double)V[n]
+ *   TNMF_PATCH_RESIDUAL  s = (double)V[n] - (double)R[n]                       (R the render of the whole list)
+ *   TNMF_PATCH_CLEANED   s = fma(h_e, phi_e, (double)V[n] - (double)R[n])      (the list without the row: the d_e of
+ *                                                                              tnmf_hip_events_landscape, phi_e summed over
+ *                                                                              the images that cover the pixel, in image order)
+ *   x_e[c, j] = sum over the images i, in image order, of s[c, q_i - (A - 1) + j]          (0 <= j < A per axis)
+ * -- a pixel outside the sample contributes 0 and is never read.  x_e is the adjoint of placing the plane at shift u: it lives
+ * in the frame of W_eff[p], the IMAGE FRAME.  By construction <W_eff[p], x_e> is the a_e of tnmf_hip_events_gain for
+ * TNMF_PATCH_RESIDUAL and a_out[e, delta = 0] of tnmf_hip_events_landscape for TNMF_PATCH_CLEANED (up to the order of the
+ * additions).  The ATOM FRAME is y_e[c] = L_t^T x_e[c] with p = m * T + t: the fold the W half step applies to its summed
+ * gradient, applied to one event, so that <W[m], y_e> = <W_eff[p], x_e>.  For a transform group it is the inverse
+ * permutation; without transforms y = x.
+ *
+ * tnmf_hip_events_patches: out[n_events, C, *A] DOUBLES, whatever the element type, in the order of `events`.  events,
+ * strength, V, R: those of tnmf_hip_events_gain, read and not written; duplicates are allowed, each row puts back only itself.
+ * THE FOLD TABLE is the caller's to build, once per set of transforms, as plain device arrays (nA = prod(A)):
+ *   fold_ptr [T * nA + 1] ints, fold_src [nnz] ints, fold_w [nnz] doubles, with
+ *   y[c, i] = sum over k in [fold_ptr[t * nA + i], fold_ptr[t * nA + i + 1]) of fold_w[k] * x[c, fold_src[k]]
+ * the products summed in table order in double -- row (t, i) holds the entries (t, out pixel, in pixel = i, weight) of the
+ * operators with fold_src the out pixel.  fold_ptr == NULL gives the image frame (fold_src, fold_w and T are then not read
+ * beyond the checks below).  A run of the table that ends before it begins is empty, an entry whose source is outside
+ * [0, nA) is skipped and a start below 0 is taken as 0; the table's own length is not an operand: fold_ptr must not point
+ * beyond the entries the caller allocated.
+ * One wave per event; tap t of an image in lane t % 64, images in image order (the walk of tnmf_hip_events_gain).  With a
+ * table the wave stages x_e in LDS and gathers y_e from there, otherwise it stores x_e straight.  No atomics: the same
+ * operands give the same bits run after run.  Every element of out is written -- it needs no initialisation -- zeros for a
+ * row whose sample, plane or shift is out of range (no sample data is read for it).  TNMF_PATCH_DATA of a single-image row
+ * is (double)V at the (permuted) pixel to the bit under no table or a table of single entries of weight 1.  It reads its
+ * operands and writes out, nothing else.  Workspace: none.  Asynchronous.  With n_events == 0 or N == 0 it does nothing.
+ * Refused before anything is written, as tnmf_hip_events_gain is: TNMF_E_NULL (ctx, geom, and with n_events > 0 and N > 0
+ * events, V and out; R, W_eff and strength unless source is TNMF_PATCH_DATA; fold_src and fold_w with a fold_ptr),
+ * TNMF_E_DTYPE, TNMF_E_UNSUPPORTED for volumes, for more than 2^31 - 1 events and for n_events * C * prod(A) > 2^31 - 1,
+ * TNMF_E_GEOM for any other ndim, sizes <= 0, a negative count, an unknown mode, the per-axis limits of the mode, an unknown
+ * source, T < 1, geom->M not a multiple of T, and with a table C * prod(A) > TNMF_PATCH_STAGE_MAX doubles (what a wave's
+ * share of the workgroup's LDS holds).
+ *
+ * tnmf_hip_patch_moments: the second moments of the patches of one chunk of a list, per atom.  Y [n_rows, D] DOUBLES, the
+ * patches in the atom frame, D = C * prod(A); strength_d [n_rows] DOUBLES in the order of Y; by_atom [n_rows] ints, the rows
+ * of Y in a STABLE order of ascending atom; atom_start [n_atoms + 1] ints, atom_start[m] = the first entry of by_atom of atom
+ * m (the plane list of tnmf_hip_events_grad_W, by atom).  Outputs, all DOUBLES:
+ *   S[m, i, j] = sum_e y_e[i] * y_e[j]      g[m, i] = sum_e h_e * y_e[i]      s2[m] = sum_e h_e^2      count[m] = entries of atom m
+ * every sum over the entries of atom m in list order.  With accumulate != 0 the outputs are added to, in double, and the
+ * chunk continues the order: S is taken four entries at a time, the fours beginning at the multiples of four of the position
+ * in by_atom (entries of a four outside the atom's run, and columns beyond D, are fed as zeros), g and s2 one entry at a
+ * time.  So a list cut into chunks at multiples of four of the sorted position gives, chunk after chunk with accumulate, the
+ * values of the same list in one call (and every cut gives the same g and s2).  With accumulate == 0 every element of the
+ * outputs is written: they need no initialisation, and an atom without entries gets exact zeros.
+ * S is a batched symmetric rank-K update on the matrix cores (v_mfma_f64_16x16x4_f64): one wave owns one pair (I <= J) of
+ * 16 x 16 blocks of one atom, walks the atom's run, and stores its block and the mirror image -- of a diagonal block the
+ * upper triangle and its mirror image -- so S is symmetric to the bit.  The waves of the diagonal blocks take g (and the
+ * first of them s2 and count) from the operands they hold.  No split over the entries and no atomics: the same operands give
+ * the same bits run after run.  As in the other list entries the CONTENTS cannot be refused: an entry of by_atom outside
+ * [0, n_rows) is fed as zeros (it still counts) and atom_start is clamped to [0, n_rows]; a run that ends before it begins
+ * is empty.  Workspace: none.  Asynchronous.
+ * Refused before anything is written: TNMF_E_NULL (ctx, atom_start, an output; Y, strength_d and by_atom with n_rows > 0),
+ * TNMF_E_GEOM for D <= 0, n_atoms <= 0 and n_rows < 0, TNMF_E_UNSUPPORTED for n_atoms * D * D > 2^31 - 1 and for more than
+ * 2^31 - 1 rows. */
+#define TNMF_PATCH_DATA 0
+#define TNMF_PATCH_RESIDUAL 1
+#define TNMF_PATCH_CLEANED 2
+#define TNMF_PATCH_STAGE_MAX 2048
+
+int tnmf_hip_events_patches(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, int source, const void *W_eff,
+                            const int *events, const void *strength, long long n_events, const void *V, const void *R,
+                            const int *fold_ptr /* may be NULL */, const int *fold_src, const double *fold_w, int T,
+                            double *out /* double */, void *stream);
+
+int tnmf_hip_patch_moments(tnmf_hip_ctx *ctx, int D, int n_atoms, const double *Y, const double *strength_d,
+                           const int *by_atom, const int *atom_start, long long n_rows, int accumulate, double *S,
+                           double *g, double *s2, double *count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

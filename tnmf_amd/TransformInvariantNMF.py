@@ -38,6 +38,8 @@ from .events_host import (event_boxes, event_images, events_alternatives_numpy, 
                           events_gain_numpy, events_gram_numpy, events_inverse_diag_numpy, events_landscape_numpy,
                           events_norms_numpy, events_numpy, events_solve_numpy, find_peaks_numpy, landscape_gains, pursuit_loop, pursuit_numpy,
                           relabel_hops, relocation_hops)
+from .patches_host import (FRAMES as _PATCH_FRAMES, SOURCES as _PATCH_SOURCES, event_patch_moments_numpy,  # noqa: F401
+                           event_patches_numpy, modes_from_moments)
 
 
 class MiniBatchAlgorithm(enum.Enum):
@@ -935,6 +937,65 @@ class TransformInvariantNMF:
             self._W[...] = W
             self._expand_W()
         return self._with_strengths(det, shift, new)
+
+    # -- the data under the detections, and how the occurrences of an atom vary ------------------------------------------
+    def detection_patches(self, det, source: str = 'cleaned', frame: str = 'atom') -> np.ndarray:
+        """``[K, C, *atom_shape]`` float64, in the order of ``det``: the data under each row -- the "waveforms" of the
+        detections.  ``source``: ``'data'`` cuts V itself, ``'residual'`` ``V - R`` with R = ``reconstruct_detections(det)``,
+        ``'cleaned'`` ``V - R + h phi``, the data with every OTHER row of the list taken out.  The cut is the adjoint of
+        placing the atom: the signal under every image of the row (a wrapped or mirrored row has up to four) added up,
+        pixels outside the sample contributing 0.  ``frame='image'`` leaves it in the frame of the transformed atom
+        ``transformed_atoms[atom, transform]``; ``frame='atom'`` turns it back into the frame of ``W[atom]`` with the
+        transposed operator of the row's transform (for a group: the inverse permutation), so that the patches of one atom
+        align whatever their orientation and ``<W[atom], patch>`` is the row's correlation.  On a backend with
+        ``event_patches`` the patches are gathered on the device and only they are copied.  The plain Frobenius objective
+        only."""
+        _args.one_of('source', source, _PATCH_SOURCES)
+        _args.one_of('frame', frame, _PATCH_FRAMES)
+        self._plain_frobenius_only('detection_patches')
+        rows = self._events_of(det, distinct=False)
+        out = self._on_events('event_patches', event_patches_numpy, rows, source=source, transforms=self._transforms,
+                              frame=frame)
+        return np.asarray(out, dtype=np.float64)
+
+    def atom_patch_moments(self, det, source: str = 'cleaned', max_rows: Optional[int] = None):
+        """(S ``[n_atoms, D, D]``, g ``[n_atoms, D]``, s2 ``[n_atoms]``, count ``[n_atoms]``) float64, ``D = C *
+        prod(atom_shape)``: per atom the moments of the atom-frame patches y of its rows (``detection_patches(det, source)``
+        flattened) and their strengths h: ``S = sum y y^T``, ``g = sum h y``, ``s2 = sum h^2``, ``count`` the rows.  All
+        four are sums over the rows, so they add over disjoint lists -- and over the ranks of a process group: the call is
+        not collective, each rank reports its own samples, as ``atom_terms`` does, and ``modes_from_moments`` takes the
+        summed moments.  On a backend with ``event_patch_moments`` the patches never leave the device: the list is walked
+        in chunks of at most ``max_rows`` rows (default: 256 MiB of patches), which does not change the result.  The plain
+        Frobenius objective only."""
+        _args.one_of('source', source, _PATCH_SOURCES)
+        _args.int_at_least('max_rows', max_rows, 1, none_ok=True)
+        self._plain_frobenius_only('atom_patch_moments')
+        rows = self._events_of(det, distinct=False)
+        out = self._on_events('event_patch_moments', event_patch_moments_numpy, rows, source=source,
+                              transforms=self._transforms, max_rows=max_rows)
+        return tuple(np.asarray(x, dtype=np.float64) for x in out)
+
+    def atom_modes(self, det, n_modes: int = 3, source: str = 'cleaned'):
+        """(mean ``[n_atoms, C, *A]``, modes ``[n_atoms, n_modes, C, *A]``, variance ``[n_atoms, n_modes]``, total
+        ``[n_atoms]``) float64: how the occurrences of each atom vary -- the question opposite to ``atom_overlaps``, which
+        two atoms are one: which one atom is two.  With y the atom-frame patches of an atom's rows and h their strengths,
+        ``mean = sum h y / sum h^2`` is the least-squares template of the occurrences, and the modes are the leading
+        eigenvectors of the scatter of ``y - h mean`` (``modes_from_moments``), unit vectors with the largest entry
+        positive, ``variance`` their eigenvalues and ``total`` the trace: ``variance[m, 0] / total[m]`` near 1 says the
+        occurrences of atom m differ along ONE direction -- the dictionary wants another atom, or another transform, there.
+        An atom with fewer than two rows gets NaN modes and zero variance.  Leaves ``atom_modes_info_`` with the rows
+        (``count``) and the summed squared strengths (``s2``) per atom.  Not collective (``atom_patch_moments``).  The plain
+        Frobenius objective only."""
+        _args.int_at_least('n_modes', n_modes, 1)
+        if self._H is not None:   # (before the pass over the list; an unfitted model is refused by the helpers below)
+            D = int(np.prod(self._W.shape[1:]))
+            if n_modes > D:
+                raise ValueError(f'n_modes must be an int in [1, {D}] (C * prod(atom_shape)), not {n_modes!r}')
+        S, g, s2, count = self.atom_patch_moments(det, source)
+        mean, modes, variance, total = modes_from_moments(S, g, s2, count, n_modes)
+        shape = tuple(int(x) for x in self._W.shape[1:])
+        self.atom_modes_info_ = dict(count=count, s2=s2)
+        return mean.reshape((-1,) + shape), modes.reshape((len(mean), int(n_modes)) + shape), variance, total
 
     def sample_objective(self) -> np.ndarray:
         """[N] float64: each sample's share of ``objective()``, in the order of ``V`` (with a process group: this rank's

@@ -41,6 +41,12 @@ def finite_number(name: str, value, bound: str = None, none_ok: bool = False) ->
         _refuse(name, 'a finite number' + ('' if bound is None else ' ' + bound), value, none_ok)
 
 
+def one_of(name: str, value, choices) -> None:
+    """``value`` is one of the strings ``choices``."""
+    if not isinstance(value, str) or value not in choices:
+        _refuse(name, 'one of ' + ', '.join(repr(c) for c in choices), value, False)
+
+
 def boolean(name: str, value) -> None:
     if not is_bool(value):
         _refuse(name, 'a bool', value, False)

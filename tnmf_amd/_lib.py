@@ -37,6 +37,7 @@ EXPORTS = (
     'tnmf_hip_events_alternatives',
     'tnmf_hip_events_pairs', 'tnmf_hip_events_gram', 'tnmf_hip_events_project', 'tnmf_hip_events_nnls',
     'tnmf_hip_events_inverse_diag',
+    'tnmf_hip_events_patches', 'tnmf_hip_patch_moments',
 )
 
 MODES = {'valid': 0, 'full': 1, 'circular': 2, 'reflect': 3}
@@ -50,6 +51,10 @@ EVENT_CELLS = {1: (256,), 2: (16, 16)}
 EVENT_SEGMENT = 64
 # the largest component tnmf_hip_events_inverse_diag factors in LDS: TNMF_EVENTS_INVERSE_LDS
 EVENT_INVERSE_LDS = 200
+# the signal tnmf_hip_events_patches gathers (TNMF_PATCH_*): name -> id
+PATCH_SOURCES = {'data': 0, 'residual': 1, 'cleaned': 2}
+# the doubles of C * prod(A) a fold table allows: TNMF_PATCH_STAGE_MAX
+PATCH_STAGE_MAX = 2048
 
 PATHS = {'auto': 0, 'generic': 1, 'mfma': 2, 'fft': 3, 'hybrid': 4, 'split': 5}
 
@@ -173,6 +178,8 @@ def load() -> ctypes.CDLL:
     lib.tnmf_hip_events_nnls.argtypes = [vp, ll, ll, vp, vp, vp, vp, vp, cd, ci, ci, vp, pi, ctypes.POINTER(cd), pi,
                                          ctypes.POINTER(cd), ci, pi, vp]
     lib.tnmf_hip_events_inverse_diag.argtypes = [vp, ll, ll, vp, vp, vp, ll, vp, pi, ll, vp, vp, vp, ll, vp, vp, vp]
+    lib.tnmf_hip_events_patches.argtypes = [vp, gp, ci, ci, vp, vp, vp, ll, vp, vp, vp, vp, vp, ci, vp, vp]
+    lib.tnmf_hip_patch_moments.argtypes = [vp, ci, ci, vp, vp, vp, vp, ll, ci, vp, vp, vp, vp, vp]
     lib.tnmf_hip_pad_H.argtypes = [vp, gp, ci, vp, vp, vp]
     lib.tnmf_hip_fold_H.argtypes = [vp, gp, ci, vp, vp, vp]
     for name in EXPORTS:

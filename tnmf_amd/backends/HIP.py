@@ -20,6 +20,7 @@ import torch
 
 from .. import _lib, sharding, transforms as _transforms
 from ..events_host import pursuit_loop
+from ..patches_host import fold_table
 from ._Backend import Backend, sliceNone
 
 _DTYPES = {np.dtype('float32'): (torch.float32, 0), np.dtype('float64'): (torch.float64, 1)}
@@ -117,6 +118,7 @@ class HIP_Backend(Backend):
         self._counts_pending = None
         self._ctx = ctypes.c_void_p()
         self._ops_handles = {}      # AtomOperators.key -> (operators, library handle on self._ctx)
+        self._fold_tables = {}      # group name or AtomOperators.key -> the device table of tnmf_hip_events_patches
         _lib.check(self._lib.tnmf_hip_ctx_create(self._device.index, ctypes.byref(self._ctx)), 'tnmf_hip_ctx_create')
         _lib.check(self._lib.tnmf_hip_ctx_set_path(self._ctx, _lib.PATHS[path]), 'tnmf_hip_ctx_set_path')
         _lib.check(self._lib.tnmf_hip_ctx_set_split(self._ctx, 1 if split else 0), 'tnmf_hip_ctx_set_split')
@@ -367,6 +369,23 @@ class HIP_Backend(Backend):
                 wd.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(handle)), 'tnmf_hip_atom_ops_create')
             entry = self._ops_handles[ops.key] = (ops, handle)
         return entry[1]
+
+    def _fold_table(self, transforms):
+        """(fold_ptr, fold_src, fold_w, T): the table of tnmf_hip_events_patches for ``transforms`` on this device (None:
+        no table, T = 1), built once per (transforms, atom shape) (patches_host.fold_table) and kept beside the operator
+        handles.  The atom shape is part of the key: the table of a group name has T * prod(A) + 1 row starts, the kernel
+        reads it by the geometry of the call, and a backend may be initialised again with atoms of another shape."""
+        if transforms is None:
+            return None, None, None, 1
+        if len(self.atom_shape) == 3:
+            raise NotImplementedError('transforms: 1 or 2 shift axes only')
+        transforms = _transforms.check(transforms, self.atom_shape)
+        key = (transforms.key if isinstance(transforms, _transforms.AtomOperators) else transforms, tuple(self.atom_shape))
+        entry = self._fold_tables.get(key)
+        if entry is None:
+            ptr, src, w, T = fold_table(transforms, self.atom_shape)
+            entry = self._fold_tables[key] = tuple(torch.from_numpy(a).to(self._device) for a in (ptr, src, w)) + (T,)
+        return entry
 
     def _transform_arg(self, transforms):
         """-> (entry point family, its argument): ('group', TNMF_GROUP_*) for a group name, ('ops', handle) for an
@@ -1077,6 +1096,107 @@ class HIP_Backend(Backend):
                                                           render=W)
         a, b = self.alternatives_event_list(W, events, strength, R, n_alt, stride)
         return a.cpu().numpy(), b.cpu().numpy()
+
+    # -- events: the patches under the rows and their moments per atom ---------------------------------------------------------
+    # The data under each row, gathered where the samples live (include/tnmf_hip.h, "patches"); the moments of a long list
+    # are taken chunk by chunk through one reused buffer, so neither K * D doubles nor V cross to the host.
+    PATCH_BYTES = 256 << 20      # the patches of one chunk of event_patch_moments: at most this much
+
+    def patch_event_list(self, W: Optional[torch.Tensor], events: torch.Tensor, strength: torch.Tensor,
+                         R: Optional[torch.Tensor], source: str, table, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[K, C, *A] float64 on the device: the patch of every row, R being the render of the strengths (None for
+        ``source='data'``), folded into the atom frame by ``table`` (_fold_table; (None, None, None, 1): the image frame)
+        -> tnmf_hip_events_patches (into the first K rows of ``out`` when given: every element is written)."""
+        assert strength.is_contiguous() and strength.dtype == self._torch_dtype and events.shape[0] == strength.numel()
+        assert events.is_contiguous() and (R is None) == (source == 'data')
+        K = strength.numel()
+        shape = (K, self.n_channels) + tuple(self.atom_shape)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=self._device)
+        assert out.is_contiguous() and out.dtype == torch.float64 and out.numel() >= int(np.prod(shape))
+        ptr, src, w, T = table
+        # (the table's length is not an operand of the entry: the caller vouches that it is the one of this atom shape)
+        assert ptr is None or (ptr.numel() == T * int(np.prod(self.atom_shape)) + 1 and src.numel() == w.numel())
+        n_planes = T if W is None else W.shape[0]
+        with self._timed('events_patches'):
+            _lib.check(self._lib.tnmf_hip_events_patches(
+                self._ctx, ctypes.byref(self._geom(self.n_local_samples, n_planes)), self._mode, _lib.PATCH_SOURCES[source],
+                _ptr(W), _ptr(events), _ptr(strength), K, _ptr(self._V_dev), _ptr(R), _ptr(ptr), _ptr(src), _ptr(w), T,
+                _ptr(out), self._stream()), 'tnmf_hip_events_patches')
+        return out.reshape(-1)[:int(np.prod(shape))].reshape(shape)
+
+    def event_patches(self, V, W: torch.Tensor, sample, plane, shift, strength, source: str = 'cleaned', transforms=None,
+                      frame: str = 'atom') -> np.ndarray:
+        """[K, C, *A] float64 on the host: the data under each row of the list, against the resident samples (`V` is the
+        array given to initialize(), as for the other hooks) -- ``source`` 'data': V, 'residual': V - R, 'cleaned':
+        V - R + h phi -- in the frame of the plane (``frame='image'``) or folded by the transposed operator of the row's
+        transform into the frame of the atom (``'atom'``).  The list is rendered only when the source needs R."""
+        self._check_W(W)
+        _, _, events, strength, R = self._prepared_events('event_patches', W.shape[0], sample, plane, shift, strength,
+                                                          render=None if source == 'data' else W)
+        table = self._fold_table(transforms if frame == 'atom' else None)
+        if W.shape[0] % table[3]:
+            raise ValueError(f'event_patches: {W.shape[0]} planes are not a multiple of the {table[3]} transforms')
+        return self.patch_event_list(W, events, strength, R, source, table).cpu().numpy()
+
+    def moments_patch_list(self, Y: torch.Tensor, strength_d: torch.Tensor, by_atom: torch.Tensor, atom_start: torch.Tensor,
+                           n_rows: int, accumulate: bool, out) -> None:
+        """The moments (S [M, D, D], g [M, D], s2 [M], count [M]) = ``out`` of the first ``n_rows`` rows of ``Y[., D]``,
+        written or (``accumulate``) added to -> tnmf_hip_patch_moments."""
+        S, g, s2, count = out
+        M, D = g.shape
+        assert all(t.is_contiguous() and t.dtype == torch.float64 for t in (Y, strength_d, S, g, s2, count))
+        assert by_atom.dtype == torch.int32 and atom_start.dtype == torch.int32 and atom_start.numel() == M + 1
+        assert Y.numel() >= n_rows * D and strength_d.numel() >= n_rows and by_atom.numel() >= n_rows
+        with self._timed('patch_moments'):
+            _lib.check(self._lib.tnmf_hip_patch_moments(
+                self._ctx, D, M, _ptr(Y), _ptr(strength_d), _ptr(by_atom), _ptr(atom_start), n_rows, 1 if accumulate else 0,
+                _ptr(S), _ptr(g), _ptr(s2), _ptr(count), self._stream()), 'tnmf_hip_patch_moments')
+
+    def patch_chunk_rows(self, max_rows: Optional[int] = None) -> int:
+        """The rows of one chunk of event_patch_moments: ``max_rows`` (default: what keeps the patches within PATCH_BYTES)
+        rounded down to a multiple of _lib.EVENT_SEGMENT, and at least that."""
+        D = self.n_channels * int(np.prod(self.atom_shape))
+        rows = self.PATCH_BYTES // (8 * D) if max_rows is None else int(max_rows)
+        return max(rows // _lib.EVENT_SEGMENT, 1) * _lib.EVENT_SEGMENT
+
+    def event_patch_moments(self, V, W: torch.Tensor, sample, plane, shift, strength, source: str = 'cleaned',
+                            transforms=None, max_rows: Optional[int] = None):
+        """(S [M, D, D], g [M, D], s2 [M], count [M]) float64 on the host, M = planes / T atoms and D = C * prod(A): per atom
+        the second moments of the atom-frame patches of its rows, ``S = sum y y^T``, ``g = sum h y``, ``s2 = sum h^2``, the
+        rows of an atom in list order.  The list is sorted by atom (stable) and walked in chunks of ``patch_chunk_rows``
+        rows: the patches of a chunk into one reused buffer, then their moments added to the outputs.  The chunks depend
+        on K, D and ``max_rows`` alone and begin at multiples of four rows, where tnmf_hip_patch_moments continues the
+        bits: the result does not depend on ``max_rows``."""
+        self._check_W(W)
+        _, _, events, strength, R = self._prepared_events('event_patch_moments', W.shape[0], sample, plane, shift, strength,
+                                                          render=None if source == 'data' else W)
+        table = self._fold_table(transforms)
+        T = table[3]
+        if W.shape[0] % T:
+            raise ValueError(f'event_patch_moments: {W.shape[0]} planes are not a multiple of the {T} transforms')
+        M, K = W.shape[0] // T, strength.numel()
+        D = self.n_channels * int(np.prod(self.atom_shape))
+        if M * D * D >= 2 ** 31:
+            raise NotImplementedError('event_patch_moments: more than 2^31 - 1 entries of S')
+        with self._timed('event_atom_list'):
+            sorted_atom, order = torch.sort(torch.div(events[:, 1].to(torch.int64), T, rounding_mode='floor'), stable=True)
+            atom_start = torch.searchsorted(sorted_atom, torch.arange(M + 1, dtype=torch.int64, device=self._device))
+            events, strength = events[order].contiguous(), strength[order].contiguous()
+            strength_d = strength.to(torch.float64)
+        chunk = self.patch_chunk_rows(max_rows)
+        Y = torch.empty((min(chunk, K), D), dtype=torch.float64, device=self._device)
+        by_atom = torch.arange(min(chunk, K), dtype=torch.int32, device=self._device)
+        out = (torch.empty((M, D, D), dtype=torch.float64, device=self._device),
+               torch.empty((M, D), dtype=torch.float64, device=self._device),
+               torch.empty(M, dtype=torch.float64, device=self._device),
+               torch.empty(M, dtype=torch.float64, device=self._device))
+        for r0 in range(0, max(K, 1), chunk):      # (without rows: one call that writes the zeros)
+            n = min(chunk, K - r0)
+            self.patch_event_list(W, events[r0:r0 + n], strength[r0:r0 + n], R, source, table, out=Y)
+            self.moments_patch_list(Y, strength_d[r0:r0 + n], by_atom, (atom_start - r0).clamp(0, n).to(torch.int32), n,
+                                    r0 > 0, out)
+        return tuple(t.cpu().numpy() for t in out)
 
     # -- events: exact strengths ---------------------------------------------------------------------------------------------
     # The objective of a list is a quadratic in its strengths (include/tnmf_hip.h, "events: exact strengths"): the samples

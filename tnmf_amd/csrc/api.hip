@@ -16,6 +16,7 @@
 #include "fft.h"
 #include "generic.h"
 #include "mfma.h"
+#include "patches.h"
 #include "peaks.h"
 #include "split.h"
 #include "volume.h"
@@ -1667,6 +1668,38 @@ int tnmf_hip_events_inverse_diag(tnmf_hip_ctx *ctx, long long n_rows, long long 
     return events_inverse_diag(ctx, (int)n_rows, (int)nnz, row_start, col, val, (int)n_comp, comp_start, comp_sizes,
                                (int)n_active, member, local, scratch, scratch_doubles, d_out, status_out,
                                static_cast<hipStream_t>(stream));
+}
+
+int tnmf_hip_events_patches(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, int source, const void *W_eff,
+                            const int *events, const void *strength, long long n_events, const void *V, const void *R,
+                            const int *fold_ptr, const int *fold_src, const double *fold_w, int T, double *out,
+                            void *stream) {
+    EventFrame f;
+    const int rc = events_enter(ctx, geom, mode, &f);
+    if (rc != TNMF_OK) return rc;
+    if (n_events < 0 || source < TNMF_PATCH_DATA || source > TNMF_PATCH_CLEANED || T < 1 || f.g.P % T != 0) return TNMF_E_GEOM;
+    const long long taps = (long long)f.g.C * f.g.Ay * f.g.Ax;
+    if (fold_ptr && !patches_stage_fits(taps)) return TNMF_E_GEOM;
+    if (n_events > 0x7fffffffLL || n_events > 0x7fffffffLL / taps) return TNMF_E_UNSUPPORTED;
+    if (n_events > 0 && f.g.N > 0) {
+        if (!events || !V || !out || (fold_ptr && (!fold_src || !fold_w))) return TNMF_E_NULL;
+        if (source != TNMF_PATCH_DATA && (!R || !W_eff || !strength)) return TNMF_E_NULL;
+    }
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return events_patches(ctx, f, geom->dtype, source, W_eff, events, strength, n_events, V, R, fold_ptr, fold_src, fold_w, T,
+                          out, static_cast<hipStream_t>(stream));
+}
+
+int tnmf_hip_patch_moments(tnmf_hip_ctx *ctx, int D, int n_atoms, const double *Y, const double *strength_d,
+                           const int *by_atom, const int *atom_start, long long n_rows, int accumulate, double *S, double *g,
+                           double *s2, double *count, void *stream) {
+    if (!ctx || !atom_start || !S || !g || !s2 || !count) return TNMF_E_NULL;
+    if (D <= 0 || n_atoms <= 0 || n_rows < 0) return TNMF_E_GEOM;
+    if ((long long)n_atoms * D > 0x7fffffffLL / D || n_rows > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
+    if (n_rows > 0 && (!Y || !strength_d || !by_atom)) return TNMF_E_NULL;
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    return patch_moments(ctx, D, n_atoms, Y, strength_d, by_atom, atom_start, (int)n_rows, accumulate, S, g, s2, count,
+                         static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"
