@@ -426,6 +426,43 @@ int tnmf_hip_atom_terms(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int group,
 int tnmf_hip_atom_gram(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int group, const void *V, const void *G_or_null,
                        const void *R_or_null, const void *W, const void *H, double *a, double *B, void *stream);
 
+/* ---- sources: per-source signals by soft masks (ABI 8, additive: the version stays 8) -------------------------------------
+ * A source is a set of planes of H and W (an atom in all its orientations, or several atoms).  With r_g[c, x] the sum of
+ * what the planes of source g add to R -- r of "atom terms", in the element type -- and total = sum r over EVERY plane, the
+ * planes in no source included:
+ *   TNMF_SOURCES_CONTRIBUTION  out[n, g, c, x] = r_g
+ *   TNMF_SOURCES_MASK          out[n, g, c, x] = r_g / (total + eps)
+ *   TNMF_SOURCES_MASKED        out[n, g, c, x] = V * (r_g / (total + eps))        (evaluated in that order)
+ *   TNMF_SOURCES_DOMINANT      label[n, x] = the g with the largest sum_c r_g (the lowest g of a tie; -1 where sum_c total
+ *                              is 0),  share[n, x] = that sum / (sum_c total + eps)
+ * One pass over H on the walk of tnmf_hip_atom_terms, the planes in the order the sources list them; r_g is stored raw when
+ * its last plane is in, and after the last plane every thread rewrites its own stores over the total it then holds: the
+ * denominator is the pass's own ordered sum of the numerators (source 0 first, the unlisted planes last), so r_g <= total
+ * as computed and 0 <= mask <= 1, 0 <= masked <= V (V >= 0) hold without a clamp, whatever reconstruct() would give for R.
+ * Where total + eps is 0 the mask, the masked value and the share are 0.  For TNMF_SOURCES_DOMINANT sum_c r_g is the same
+ * walk on one channel whose taps are sum_c W, the channels added in channel order.  No atomics: one writer per element, the
+ * same bits from run to run. */
+#define TNMF_SOURCES_CONTRIBUTION 0
+#define TNMF_SOURCES_MASK 1
+#define TNMF_SOURCES_MASKED 2
+#define TNMF_SOURCES_DOMINANT 3
+
+/* plane_order[source_start[g] .. source_start[g + 1]), g < n_sources, are the planes of source g: n_listed ints and
+ * n_sources + 1 ints, in host or device memory (they are read, checked and completed on the host before anything is
+ * launched: the call waits for the stream once); the planes of [0, geom->M) that are not listed follow in ascending order
+ * as a hidden last group.  H: padded activations [N, M, *(D+A-1)], row stride honoured.  W: the M planes.  V: read for
+ * TNMF_SOURCES_MASKED only.  out: [N, n_sources, C, *D] in the element type, every element written (NULL for
+ * TNMF_SOURCES_DOMINANT); label (int) and share (element type): [N, *D], every element written (for
+ * TNMF_SOURCES_DOMINANT only).  The kernels are asynchronous on the stream.  The work buffer is that of
+ * tnmf_hip_atom_terms.
+ * TNMF_E_NULL: a pointer the call reads or writes is NULL.  TNMF_E_GEOM: n_sources < 1, emit not one of the four, eps
+ * negative or not a number, n_listed outside [n_sources, M], source_start not 0 = s[0] < s[1] < ... < s[n_sources] =
+ * n_listed, a plane outside [0, M) or listed twice.  TNMF_E_UNSUPPORTED: ndim == 3, or a tile of H beyond the LDS limit of
+ * tnmf_hip_atom_terms.  A refused call writes nothing. */
+int tnmf_hip_atom_sources(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int n_sources, const int *plane_order, int n_listed,
+                          const int *source_start, int emit, double eps, const void *V, const void *W, const void *H,
+                          void *out, int *label, void *share, void *stream);
+
 /* ---- transform groups: rotation and mirror invariance (ABI 8, additive: the version stays 8) -------------------------
  * A dictionary W[M,C,*A] stands for M * T effective atoms W_eff[m*T + t] = T_t(W[m]), every T_t a permutation of the
  * atom's pixels.  The groups, with t in the order below (numpy, a = W[m, c]):

@@ -40,6 +40,7 @@ from .events_host import (event_boxes, event_images, events_alternatives_numpy, 
                           relabel_hops, relocation_hops)
 from .patches_host import (FRAMES as _PATCH_FRAMES, SOURCES as _PATCH_SOURCES, event_patch_moments_numpy,  # noqa: F401
                            event_patches_numpy, modes_from_moments)
+from .sources_host import OUTPUTS as _SOURCE_OUTPUTS, dominant_numpy, separate_numpy, source_tables
 
 
 class MiniBatchAlgorithm(enum.Enum):
@@ -1043,6 +1044,81 @@ class TransformInvariantNMF:
         a, b = self.atom_terms()
         gain = a + 0.5 * b
         return gain if per_sample else gain.sum(axis=0)
+
+    # -- the sources of a sample: per-source signals by soft masks ---------------------------------------------------------
+    def _source_tables(self, sources) -> Tuple[np.ndarray, np.ndarray]:
+        """The refusals of ``separate`` and the two int32 tables of its sources: the planes, source after source (an atom
+        stands for its ``n_transforms`` planes), and where each source starts."""
+        if sources is None:
+            sets = [[m] for m in range(self.n_atoms)]
+        else:
+            sets = _args.disjoint_index_sets('sources', sources, self.n_atoms)
+        if self._H is None:
+            raise RuntimeError('the sources of a model need a fitted model: call fit first')
+        if len(self.atom_shape) == 3:
+            raise NotImplementedError('separate: 1 or 2 shift axes only')
+        return source_tables(sets, self.n_transforms)
+
+    def _in_order_of_V(self, out: np.ndarray) -> np.ndarray:
+        return out if self._shuffle_idx is None else out[np.argsort(self._shuffle_idx)]
+
+    def separate(self, sources=None, output: str = 'masked') -> np.ndarray:
+        """The sample split into its sources, ``[N, S, C, *D]`` in V's dtype.  ``sources``: a sequence of S disjoint,
+        non-empty sequences of atom indices (with ``transforms`` an atom stands for all its orientations); ``None``: every
+        atom is a source of its own.  With ``r_g`` the sum of what the atoms of source g add to R and ``total`` the sum over
+        ALL atoms -- atoms in no source count there and get no output -- ``output`` selects
+
+        * ``'contribution'``: ``r_g``, the source's part of R;
+        * ``'mask'``: ``r_g / (total + eps)``, the soft (Wiener-type) mask, in [0, 1];
+        * ``'masked'``: ``V * (r_g / (total + eps))``, the source's estimate, in [0, V]; over a partition of the atoms the
+          estimates add up to ``V * R / (R + eps)``, whatever objective was fitted
+
+        with the model's ``eps``; 0 where ``total + eps`` is 0.  Weights play no part in the arithmetic: the V of a weighted
+        fit holds 0 where the weight is 0, so ``'masked'`` is 0 there, while ``'contribution'`` is the model's imputation of
+        the hidden entries.  Samples in the order of ``V`` (with a process group: this rank's samples, and the call is not
+        collective).  On a backend with ``source_parts`` one pass over the activations where they live, every denominator
+        that pass's own sum; any other backend's sources are separated on the host in float64.  Any ``beta_loss``, 1 or 2
+        shift axes; ``W``, ``H`` and ``V`` are not touched."""
+        _args.one_of('output', output, _SOURCE_OUTPUTS)
+        order, start = self._source_tables(sources)
+        out = None
+        if getattr(self._backend, 'supports_sources', False):
+            try:
+                out = self._backend.to_ndarray(self._backend.source_parts(self._V, self._W_dict, self._H, order, start,
+                                                                          output, eps=self.eps))
+            except NotImplementedError:   # (a tile of H beyond the kernel's LDS: nothing was written)
+                out = None
+        if out is None:
+            V, G = self._local_V(), self._weights
+            if G is not None:   # (entries of weight 0 are not data: they count as 0, as on a backend that binds the weights)
+                if len(G) != len(V):
+                    n0 = int(getattr(self._backend, 'shard', (0, 0))[0])
+                    G = G[n0:n0 + len(V)]
+                V = np.where(G > 0, V, 0)
+            out = separate_numpy(self._backend.to_ndarray(self._W_dict), self._backend.to_ndarray(self._H), self._mode,
+                                 V, order, start, output, self.eps)
+        return self._in_order_of_V(np.asarray(out).astype(self._V.dtype, copy=False))
+
+    def dominant_source(self, sources=None) -> Tuple[np.ndarray, np.ndarray]:
+        """A segmentation of the samples by source: ``(label, share)``, both ``[N, *D]``.  ``label`` (int32) is the index g
+        of the source -- ``sources`` as for ``separate`` -- with the largest contribution summed over the channels,
+        ``sum_c r_g``, at the pixel; the lowest index wins a tie, and where the model explains nothing (``sum_c total == 0``)
+        the label is -1.  ``share`` (V's dtype) is that sum over ``sum_c total + eps``.  Samples in the order of ``V``; not
+        collective."""
+        order, start = self._source_tables(sources)
+        out = None
+        if getattr(self._backend, 'supports_sources', False):
+            try:
+                label, share = self._backend.dominant_parts(self._V, self._W_dict, self._H, order, start, eps=self.eps)
+                out = self._backend.to_ndarray(label), self._backend.to_ndarray(share)
+            except NotImplementedError:
+                out = None
+        if out is None:
+            out = dominant_numpy(self._backend.to_ndarray(self._W_dict), self._backend.to_ndarray(self._H), self._mode,
+                                 self._V.shape[2:], order, start, self.eps)
+        label, share = out
+        return (self._in_order_of_V(np.asarray(label).astype(np.int32, copy=False)),
+                self._in_order_of_V(np.asarray(share).astype(self._V.dtype, copy=False)))
 
     # -- how atoms overlap: a and the Gram matrix B of the atoms' contributions ------------------------------------------
     # With per-atom scale factors s (R(s) = sum s_m R_m) the objective is the exact quadratic

@@ -47,6 +47,27 @@ def one_of(name: str, value, choices) -> None:
         _refuse(name, 'one of ' + ', '.join(repr(c) for c in choices), value, False)
 
 
+def disjoint_index_sets(name: str, value, n: int) -> list:
+    """``value`` is a non-empty sequence of non-empty sequences of ints in ``[0, n)``, no int in two of them or twice in
+    one -> the sets as lists of Python ints."""
+    kind = f'a sequence of disjoint, non-empty sequences of ints in [0, {n})'
+    try:
+        sets = [list(one) for one in value]
+    except TypeError:
+        _refuse(name, kind, value, False)
+    seen = set()
+    for one in sets:
+        if not one:
+            _refuse(name, kind, value, False)
+        for m in one:
+            if not is_int(m) or not 0 <= m < n or int(m) in seen:
+                _refuse(name, kind, value, False)
+            seen.add(int(m))
+    if not sets:
+        _refuse(name, kind, value, False)
+    return [[int(m) for m in one] for one in sets]
+
+
 def boolean(name: str, value) -> None:
     if not is_bool(value):
         _refuse(name, 'a bool', value, False)

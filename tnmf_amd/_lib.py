@@ -30,7 +30,7 @@ EXPORTS = (
     'tnmf_hip_atom_ops_create', 'tnmf_hip_atom_ops_destroy', 'tnmf_hip_ops_expand_W', 'tnmf_hip_ops_fold_grad_W',
     'tnmf_hip_ops_apply_W',
     'tnmf_hip_ctx_set_objective_tap', 'tnmf_hip_sample_objective', 'tnmf_hip_atom_terms',
-    'tnmf_hip_atom_gram',
+    'tnmf_hip_atom_gram', 'tnmf_hip_atom_sources',
     'tnmf_hip_find_peaks',
     'tnmf_hip_events_render', 'tnmf_hip_events_update', 'tnmf_hip_events_grad_W', 'tnmf_hip_events_gain',
     'tnmf_hip_events_norms', 'tnmf_hip_pursuit_score', 'tnmf_hip_pursuit_pick', 'tnmf_hip_events_landscape',
@@ -55,6 +55,9 @@ EVENT_INVERSE_LDS = 200
 PATCH_SOURCES = {'data': 0, 'residual': 1, 'cleaned': 2}
 # the doubles of C * prod(A) a fold table allows: TNMF_PATCH_STAGE_MAX
 PATCH_STAGE_MAX = 2048
+
+# what tnmf_hip_atom_sources writes (TNMF_SOURCES_*): name -> id
+SOURCE_OUTPUTS = {'contribution': 0, 'mask': 1, 'masked': 2, 'dominant': 3}
 
 PATHS = {'auto': 0, 'generic': 1, 'mfma': 2, 'fft': 3, 'hybrid': 4, 'split': 5}
 
@@ -161,6 +164,7 @@ def load() -> ctypes.CDLL:
     lib.tnmf_hip_sample_objective.argtypes = [vp, gp, cd, cd, vp, vp, vp, vp, vp, vp]
     lib.tnmf_hip_atom_terms.argtypes = [vp, gp, ci, vp, vp, vp, vp, vp, vp, vp]
     lib.tnmf_hip_atom_gram.argtypes = [vp, gp, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.tnmf_hip_atom_sources.argtypes = [vp, gp, ci, vp, ci, vp, ci, cd, vp, vp, vp, vp, vp, vp, vp]
     lib.tnmf_hip_find_peaks.argtypes = [vp, gp, vp, cd, pi, ci, vp, vp, sz, vp, vp]
     ll = ctypes.c_longlong
     lib.tnmf_hip_events_render.argtypes = [vp, gp, vp, vp, ll, vp, vp, ll, vp, vp]

@@ -833,6 +833,58 @@ class HIP_Backend(Backend):
             'tnmf_hip_atom_gram'))
         return a.cpu().numpy(), B.cpu().numpy()
 
+    # -- sources ----------------------------------------------------------------------------------------------------------
+    # The per-source signals of the resident samples (include/tnmf_hip.h, "sources"): one pass over H on the walk of the
+    # atom terms, the planes in the order the sources list them; the result stays on the device until the caller converts it.
+    supports_sources = True
+
+    def _atom_sources(self, W: torch.Tensor, H: torch.Tensor, plane_order, source_start, emit: int, eps: float, out, label,
+                      share) -> None:
+        """tnmf_hip_atom_sources on the padded activations, the two int32 tables built on the device; TNMF_E_UNSUPPORTED
+        (answered before anything is written) becomes NotImplementedError."""
+        if len(self.atom_shape) == 3:
+            raise NotImplementedError('separate: 1 or 2 shift axes only')
+        self._check_W(W)
+        self._foreign_H()
+        self._check_H(H, W.shape[0])
+        assert H.shape[0] == self.n_local_samples
+        H = self._pad(H)
+        order = torch.as_tensor(np.ascontiguousarray(plane_order, dtype=np.int32), device=self._device)
+        start = torch.as_tensor(np.ascontiguousarray(source_start, dtype=np.int32), device=self._device)
+        try:
+            self._call_H(H, False, lambda Hc, ld: (self._lib.tnmf_hip_atom_sources(
+                self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)), int(start.numel()) - 1, _ptr(order),
+                int(order.numel()), _ptr(start), int(emit), float(eps), _ptr(self._V_dev), _ptr(W), _ptr(Hc), _ptr(out),
+                _ptr(label), _ptr(share), self._stream()), 'tnmf_hip_atom_sources'))
+        except _lib.TnmfHipError as exc:
+            if exc.code == _lib.E_UNSUPPORTED:
+                raise NotImplementedError('sources: the atom is beyond the fused kernel') from exc
+            raise
+
+    def source_parts(self, V, W: torch.Tensor, H: torch.Tensor, plane_order, source_start, output: str = 'masked',
+                     eps: float = 1e-9) -> torch.Tensor:
+        """``[n_local_samples, S, C, *D]`` on the device: per source g -- the planes
+        ``plane_order[source_start[g]:source_start[g + 1]]`` of W and H -- its 'contribution' ``r_g`` to R, its 'mask'
+        ``r_g / (total + eps)`` or the 'masked' samples ``V * mask``, ``total`` being the sum over every plane
+        -> tnmf_hip_atom_sources.  The modes other than 'valid' are the 'valid' pass over the padded activations."""
+        emit = _lib.SOURCE_OUTPUTS[output]
+        assert emit != _lib.SOURCE_OUTPUTS['dominant']
+        out = torch.empty((self.n_local_samples, len(source_start) - 1, self.n_channels) + tuple(self._sample_shape),
+                          dtype=self._torch_dtype, device=self._device)
+        self._atom_sources(W, H, plane_order, source_start, emit, eps, out, None, None)
+        return out
+
+    def dominant_parts(self, V, W: torch.Tensor, H: torch.Tensor, plane_order, source_start,
+                       eps: float = 1e-9) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(label int32, share) ``[n_local_samples, *D]`` on the device: per pixel the source with the largest contribution
+        summed over the channels (the lowest index of a tie; -1 where the total is 0) and that sum over the total + eps
+        -> tnmf_hip_atom_sources."""
+        shape = (self.n_local_samples,) + tuple(self._sample_shape)
+        label = torch.empty(shape, dtype=torch.int32, device=self._device)
+        share = torch.empty(shape, dtype=self._torch_dtype, device=self._device)
+        self._atom_sources(W, H, plane_order, source_start, _lib.SOURCE_OUTPUTS['dominant'], eps, None, label, share)
+        return label, share
+
     # -- detections -----------------------------------------------------------------------------------------------------
     # The peaks of H are found and compacted on the device (include/tnmf_hip.h, "detections"): only the list of
     # (index, value) pairs crosses to the host, never H.

@@ -39,6 +39,12 @@ weights when they are bound (include/tnmf_hip.h, "atom terms"); without it ``ato
 host): ``a`` as above and ``B[n, m, m'] = sum G R_m R_m'``, symmetric, in the order of H's atoms (include/tnmf_hip.h, "atom
 Gram"); without it ``atom_gram`` and what builds on it (``atom_overlaps``, ``atom_set_gain``, ``atom_scales``,
 ``rescale_atoms``, ``atom_elimination``) run ``atom_gram_numpy`` (tnmf_amd/atoms_host.py) on the host.
+A backend that declares ``supports_sources`` offers ``source_parts(V, W, H, plane_order, source_start, output) -> out``
+(backend-native ``[n_local, S, C, *D]``: source g is the planes ``plane_order[source_start[g]:source_start[g + 1]]``, the
+planes in no source count in the total only; ``output`` one of 'contribution', 'mask', 'masked', with the ``eps`` keyword)
+and ``dominant_parts(V, W, H, plane_order, source_start) -> (label, share)`` (include/tnmf_hip.h, "sources"); either may
+raise ``NotImplementedError``, and then, as without the hooks, ``separate`` / ``dominant_source`` run ``separate_numpy`` /
+``dominant_numpy`` (tnmf_amd/sources_host.py) on the host.
 A backend that declares ``supports_peaks`` offers ``find_peaks(H, threshold, radius, group) -> (idx, val)``: the ascending
 flat C-order indices (int64, host) in H's shape [n, P, *S] and the values of the detections of its native H
 (include/tnmf_hip.h, "detections"); without it ``detections()`` searches ``to_ndarray(H)`` on the host.

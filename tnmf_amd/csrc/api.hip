@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "atom_gram.h"
+#include "sources.h"
 #include "atoms.h"
 #include "beta.h"
 #include "events.h"
@@ -925,6 +926,49 @@ int tnmf_hip_atom_gram(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int group, 
     }
     return launch_atom_gram(ctx, g, dtype, group, V, G_or_null, R, W, H, static_cast<double *>(ctx->ob),
                             static_cast<char *>(ctx->ob) + p_bytes, a, B, s);
+}
+
+int tnmf_hip_atom_sources(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int n_sources, const int *plane_order, int n_listed,
+                          const int *source_start, int emit, double eps, const void *V, const void *W, const void *H,
+                          void *out, int *label, void *share, void *stream) {
+    if (!ctx || !geom) return TNMF_E_NULL;
+    if (is_vol(geom)) return TNMF_E_UNSUPPORTED;
+    ENTER(ctx, geom);
+    if (emit < TNMF_SOURCES_CONTRIBUTION || emit > TNMF_SOURCES_DOMINANT || !(eps >= 0.0)) return TNMF_E_GEOM;
+    if (n_sources < 1 || n_listed < n_sources || n_listed > g.M) return TNMF_E_GEOM;
+    if (g.N == 0) return TNMF_OK;
+    const bool dom = emit == TNMF_SOURCES_DOMINANT;
+    if (!plane_order || !source_start || !W || !H || (emit == TNMF_SOURCES_MASKED && !V)) return TNMF_E_NULL;
+    if (dom ? (!label || !share) : !out) return TNMF_E_NULL;
+    {
+        Geo g1 = g;
+        if (dom) g1.C = 1;
+        CHECK(atom_terms_check(g1, dtype));
+    }
+    // the two tables, wherever they live: checked and completed here, before anything is written
+    std::vector<int> order((size_t)g.M), start((size_t)n_sources + 2);
+    TNMF_HIP_TRY(hipMemcpyAsync(order.data(), plane_order, (size_t)n_listed * sizeof(int), hipMemcpyDefault, s));
+    TNMF_HIP_TRY(hipMemcpyAsync(start.data(), source_start, ((size_t)n_sources + 1) * sizeof(int), hipMemcpyDefault, s));
+    TNMF_HIP_TRY(hipStreamSynchronize(s));
+    if (start[0] != 0 || start[n_sources] != n_listed) return TNMF_E_GEOM;
+    for (int k = 0; k < n_sources; ++k)
+        if (start[k + 1] <= start[k]) return TNMF_E_GEOM;
+    std::vector<char> listed((size_t)g.M, 0);
+    for (int i = 0; i < n_listed; ++i) {
+        if (order[i] < 0 || order[i] >= g.M || listed[order[i]]) return TNMF_E_GEOM;
+        listed[order[i]] = 1;
+    }
+    int fill = n_listed;
+    for (int m = 0; m < g.M; ++m)
+        if (!listed[m]) order[fill++] = m;
+    start[n_sources + 1] = g.M;
+    const SourcesWork wk = atom_sources_work(g, dtype, n_sources, emit);
+    CHECK(ensure_buffer(&ctx->ob, &ctx->ob_bytes, wk.total, false));
+    char *work = static_cast<char *>(ctx->ob);
+    TNMF_HIP_TRY(hipMemcpyAsync(work + wk.order_off, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    TNMF_HIP_TRY(hipMemcpyAsync(work + wk.start_off, start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    TNMF_HIP_TRY(hipStreamSynchronize(s));   // (the two vectors end with this call)
+    return launch_atom_sources(ctx, g, dtype, n_sources, emit, eps, work, V, W, H, out, label, share, s);
 }
 
 int tnmf_hip_beta_fields(tnmf_hip_ctx *ctx, int dtype, double beta, double eps, const void *V, const void *R, void *Q,

@@ -32,3 +32,6 @@ int atom_terms_check(const Geo &g, int dtype);
 int launch_atom_terms(const tnmf_hip_ctx *ctx, const Geo &g, int dtype, int group, const void *V, const void *G,
                       const void *R, const void *W, const void *H, double *partials, void *taps, double *ab,
                       hipStream_t s);
+// taps (atom_terms_taps_bytes) = the flipped copy of W[g.M, g.C, *A] that the walk of atom_walk.h reads: what
+// launch_atom_terms does first, for the other kernels on that walk (sources.hip)
+int launch_atom_taps(const tnmf_hip_ctx *ctx, const Geo &g, int dtype, const void *W, void *taps, hipStream_t s);

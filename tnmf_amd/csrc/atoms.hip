@@ -11,28 +11,18 @@
 // scalar cache, from a flipped copy of W (k_atom_taps) -- and after the last plane of an atom folds r * (G d) and G * r^2
 // into two doubles.
 //
-// The multiply-adds are written on pairs, for the packed f32 instruction: r of a pixel is kept as two sums, over the even
-// and the odd elements of the thread's window X of the LDS row, and added up when the atom is complete.  A pair of X sits
-// in an aligned register pair only at an even offset, so the taps come in two copies: E[i] = t[i] for the even pixels
-// (r[px] = sum_i X[px + i] E[i]) and O[i] = t[i - 1], O[0] = 0, for the odd ones (r[px] = sum_i X[px - 1 + i] O[i]).
+// The walk itself -- the staging of H, the taps in two copies, the multiply-adds on pairs -- is atom_walk.h, shared with
+// sources.hip.
 //
 // The two doubles are summed over the wave by a shuffle tree and over the waves in wave order: partial sums per (sample,
 // tile, atom); k_atom_terms_finalize adds the tiles in tile order.  No atomics: the same bits every run.
 #include <algorithm>
 
-#include "atoms.h"
+#include "atom_walk.h"
 
 namespace {
 
 constexpr int kStage = 10;   // tile elements per thread that the register stage holds; larger tiles: the plain loop
-
-static_assert(kAtomPix == 4, "the multiply-adds below are written for four pixels per thread");
-template <typename T>
-using Quad = T __attribute__((ext_vector_type(4)));
-template <typename T>
-using Pair = T __attribute__((ext_vector_type(2)));
-template <typename T>
-using Oct = T __attribute__((ext_vector_type(8)));
 
 // With t[b] = W[plane, c, Ay-1-a, Ax-1-b] the taps of a row of the flipped atom, run j of kAtomPix elements i = 4 j + e:
 //   Wf[plane, c, a, j, 0, e] = E[i] = t[i]       (i < Ax, else 0)
@@ -78,10 +68,7 @@ __global__ __launch_bounds__(kAtomThreads) void k_atom_terms(Geo g, AtomPlan p, 
     const int c0 = chunk * CH;
     const int nc = g.C - c0 < CH ? g.C - c0 : CH;   // channels of this chunk (uniform)
 
-    const int txt = p.TX / kAtomPix;                // threads along x
-    const int tx = (int)threadIdx.x % txt, ty = (int)threadIdx.x / txt;
-    const int y0 = tyi * p.TY, x0 = txi * p.TX;
-    const int y = y0 + ty, xb = x0 + tx * kAtomPix;
+    ATOM_WALK_PIXELS();
 
     // G * d and G of this thread's pixels, every channel of the chunk: read once, kept in registers.  Pixels outside the
     // sample, channels past the last one and entries of weight 0 (whatever V holds there) carry exact zeros.
@@ -101,33 +88,9 @@ __global__ __launch_bounds__(kAtomThreads) void k_atom_terms(Geo g, AtomPlan p, 
             gd[c][px] = w > T(0) ? w * d : T(0);
         }
     }
-    // the rows of taps of the chunk's channels (a channel past the last one reads the last one's: its sums are times zero)
-    size_t wrow[CH];
-#pragma unroll
-    for (int c = 0; c < CH; ++c) wrow[c] = (size_t)(c < nc ? c0 + c : g.C - 1) * g.Ay * p.NBO;
-
-    // the tile of a plane: element tid + 256 k sits at row and column (r_first, q_first) + k * (dr, dq)
-    const int nel = p.SH * p.SW;
-    const int dr = kAtomThreads / p.SW, dq = kAtomThreads - dr * p.SW;
-    const int r_first = (int)threadIdx.x / p.SW, q_first = (int)threadIdx.x - r_first * p.SW;
-    const bool pre_ok = nel <= kStage * kAtomThreads;   // (uniform)
-    T pre[kStage];
-    auto fetch = [&](int plane) {
-        const T *h = H + ((size_t)n * g.M + plane) * g.Hy * g.Hs;   // (rows of H may be padded: g.Hs >= g.Hx)
-        int rr = r_first, q = q_first;
-#pragma unroll
-        for (int k = 0; k < kStage; ++k) {
-            const int hy = y0 + rr, hx = x0 + q;
-            pre[k] = (k * kAtomThreads + (int)threadIdx.x < nel && hy < g.Hy && hx < g.Hx) ? h[(size_t)hy * g.Hs + hx]
-                                                                                            : T(0);
-            rr += dr;
-            q += dq;
-            if (q >= p.SW) {
-                q -= p.SW;
-                ++rr;
-            }
-        }
-    };
+    ATOM_WALK_TILE();
+    const bool pre_ok = nel <= kStage * kAtomThreads;   // the tile fits the register stage (uniform)
+    ATOM_WALK_FETCH();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 
     Pair<T> r[CH][kAtomPix];   // (r of pixel px is r[c][px].x + r[c][px].y)
@@ -140,59 +103,8 @@ __global__ __launch_bounds__(kAtomThreads) void k_atom_terms(Geo g, AtomPlan p, 
 #pragma unroll
                 for (int px = 0; px < kAtomPix; ++px) r[c][px] = Pair<T>(T(0));
         }
-        __syncthreads();   // every wave is done with the previous plane
-        if (pre_ok) {
-#pragma unroll
-            for (int k = 0; k < kStage; ++k) {
-                const int i = k * kAtomThreads + threadIdx.x;
-                if (i < nel) Hs[i] = pre[k];
-            }
-        } else {
-            const T *h = H + ((size_t)n * g.M + plane) * g.Hy * g.Hs;
-            for (int i = threadIdx.x; i < nel; i += kAtomThreads) {
-                const int rr = i / p.SW, q = i - rr * p.SW;
-                const int hy = y0 + rr, hx = x0 + q;
-                Hs[i] = (hy < g.Hy && hx < g.Hx) ? h[(size_t)hy * g.Hs + hx] : T(0);
-            }
-        }
-        __syncthreads();
-        if (pre_ok && plane + 1 < g.M) fetch(plane + 1);   // in flight under the multiply-adds
-        const Oct<T> *wq = reinterpret_cast<const Oct<T> *>(Wf) + (size_t)plane * g.C * g.Ay * p.NBO;
-        for (int a = 0; a < g.Ay; ++a) {
-            const Quad<T> *row = reinterpret_cast<const Quad<T> *>(Hs + (ty + a) * p.SW) + tx;
-            // (the taps of a run: the same address in every thread; the next run's are loaded under this run's multiply-adds)
-            const Oct<T> *taps[CH];
-            Oct<T> eo_next[CH];
-#pragma unroll
-            for (int c = 0; c < CH; ++c) {
-                taps[c] = wq + wrow[c] + (size_t)a * p.NBO;
-                eo_next[c] = taps[c][0];
-            }
-            Quad<T> cur = row[0];
-#pragma unroll 2
-            for (int j = 0; j < p.NBO; ++j) {
-                const Quad<T> nxt = row[j + 1];
-                const Pair<T> x0 = cur.xy, x1 = cur.zw, x2 = nxt.xy;   // X[4j .. 4j + 5]
-                const int jn = j + 1 < p.NBO ? j + 1 : j;
-#pragma unroll
-                for (int c = 0; c < CH; ++c) {
-                    const Oct<T> eo = eo_next[c];
-                    eo_next[c] = taps[c][jn];
-                    const Quad<T> e = eo.lo, o = eo.hi;
-                    r[c][1] += x0 * o.xy;
-                    r[c][1] += x1 * o.zw;
-                    r[c][3] += x1 * o.xy;
-                    r[c][3] += x2 * o.zw;
-                    if (j < p.NB) {   // (E is one run shorter than O when Ax is a multiple of kAtomPix)
-                        r[c][0] += x0 * e.xy;
-                        r[c][0] += x1 * e.zw;
-                        r[c][2] += x1 * e.xy;
-                        r[c][2] += x2 * e.zw;
-                    }
-                }
-                cur = nxt;
-            }
-        }
+        ATOM_WALK_STAGE(plane, plane + 1 < g.M, plane + 1);
+        ATOM_WALK_MACS(plane, r);
         if (t != group - 1) continue;
         // r_m is complete: fold into the two sums, in double
         double pa = 0.0, pb = 0.0;
@@ -322,6 +234,20 @@ int launch_atom_terms(const tnmf_hip_ctx *ctx, const Geo &g, int dtype, int grou
     const size_t out_rows = (size_t)g.N * (g.M / group);
     hipLaunchKernelGGL(k_atom_terms_finalize, dim3((unsigned)((out_rows + kAtomThreads - 1) / kAtomThreads)),
                        dim3(kAtomThreads), 0, s, out_rows, p.slots, g.M / group, (const double *)partials, ab);
+    TNMF_LAUNCH_CHECK();
+    return TNMF_OK;
+}
+
+int launch_atom_taps(const tnmf_hip_ctx *ctx, const Geo &g, int dtype, const void *W, void *taps, hipStream_t s) {
+    const AtomPlan p = atom_terms_plan(g);
+    const int rows = g.M * g.C;
+    const size_t n_taps = (size_t)rows * g.Ay * p.NBO * 2 * kAtomPix;
+    const unsigned tap_blocks = (unsigned)std::min<size_t>((n_taps + kAtomThreads - 1) / kAtomThreads, (size_t)ctx->num_cu * 8);
+    with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_atom_taps<T>, dim3(tap_blocks), dim3(kAtomThreads), 0, s, rows, g.Ay, g.Ax, p.NBO, (const T *)W,
+                           (T *)taps);
+    });
     TNMF_LAUNCH_CHECK();
     return TNMF_OK;
 }
