@@ -560,6 +560,28 @@ int tnmf_hip_find_peaks(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void
                         int group, long long *idx_out, void *val_out, size_t capacity, unsigned long long *count_out,
                         void *stream);
 
+/* ---- activation correlogram: which planes co-occur, and at what offset (ABI 8, additive: the version stays 8) -------------
+ * The second-order structure of the activations.  H is viewed as [N, P, *S] exactly as under "detections": P = geom->M
+ * planes of shift shape S = D + A - 1 (the caller passes D = S, A = 1 for H as it is in any reconstruction mode), rows
+ * `h_row_stride` apart, pad columns never read; C is not read.  1 or 2 shift axes.  For the lags |D_k| <= L_k = max_lag[k]
+ *   C[n, p, q, D] = sum_u H[n, p, u] H[n, q, u + D]     over the u with u and u + D inside the plane (nothing wraps),
+ * stored at index D_k + L_k of axis k: C_out is [P, P, *(2 L + 1)] doubles on the device, the sum over the samples, or with
+ * per_sample != 0 [N, P, P, *(2 L + 1)].  Every element is written; lags at or beyond the extent of an axis are exactly 0.
+ * C[p, q, D] and C[q, p, -D] are the same sum and have the same bits.
+ * Arithmetic: both operands converted to double, the products and sums on v_mfma_f64_16x16x4_f64 -- for float H every
+ * product is exact.  Blocks of 16 planes, every ordered pair of blocks a workgroup of its own, and only the half of the
+ * lags that is >= 0 in C order; per (sample, pixel tile) the tile of the first block (one axis: 256 pixels, double 128; two:
+ * 4 x 64, double 2 x 64) and the window of the second that it meets under one chunk of lags -- one D_y, up to 32 consecutive D_x --
+ * are staged in LDS.  Partial sums per (sample with per_sample, else the whole call; strip of (sample, tile) items; block
+ * pair; lag) live in the work buffer of tnmf_hip_atom_terms and are added in strip order by a second kernel that also
+ * writes the mirror: no floating-point atomics, the same bits from run to run.
+ * Limits: max_lag <= 1023 with one shift axis, <= 63 per axis with two; any P.  Asynchronous on the stream.
+ * TNMF_E_UNSUPPORTED: ndim == 3, a lag beyond that limit, more than 2^31 - 1 workgroups.  TNMF_E_GEOM: any other ndim, a
+ * negative lag, sizes <= 0 (N < 0), a row stride below the shift width.  TNMF_E_NULL (ctx, geom, max_lag, C_out, and H
+ * with N > 0) and TNMF_E_DTYPE as usual -- all before anything is written. */
+int tnmf_hip_activation_correlogram(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *H, const int *max_lag,
+                                    int per_sample, double *C_out, void *stream);
+
 /* ---- events: render, refit and learn from a list of detections (ABI 8, additive: the version stays 8) -----------------------------
  * The H side with the activations held as a list.  An EVENT is (n, p, u, h): local sample n, plane p of the effective
  * dictionary W_eff[P, C, *A] (P = geom->M; with transforms p = atom * T + transform), shift index u in the activations of

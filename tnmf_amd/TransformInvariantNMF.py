@@ -33,6 +33,7 @@ from . import transforms as _transforms
 from .atoms_host import (atom_gram_numpy, atom_terms_numpy, gram_drop, gram_elimination, gram_scales,
                          gram_set_gain)
 from .backends._Backend import Backend, sliceNone
+from .correlogram_host import activation_correlogram_numpy, cooccurrence
 # (the host side of the events; the names stay importable from this module)
 from .events_host import (event_boxes, event_images, events_alternatives_numpy, events_fit_numpy,  # noqa: F401
                           events_gain_numpy, events_gram_numpy, events_inverse_diag_numpy, events_landscape_numpy,
@@ -1119,6 +1120,63 @@ class TransformInvariantNMF:
         label, share = out
         return (self._in_order_of_V(np.asarray(label).astype(np.int32, copy=False)),
                 self._in_order_of_V(np.asarray(share).astype(self._V.dtype, copy=False)))
+
+    # -- which atoms co-occur, and at what offset: the correlogram of the activations ------------------------------------
+    def _max_lag(self, max_lag) -> Tuple[int, ...]:
+        """``max_lag`` as one int >= 0 per shift axis; ``None``: ``atom_shape - 1``, the range over which two occurrences
+        touch."""
+        k = len(self.atom_shape)
+        if max_lag is None:
+            return tuple(int(a) - 1 for a in self.atom_shape)
+        if _args.is_int(max_lag):
+            lags = (max_lag,) * k
+        elif isinstance(max_lag, (tuple, list)) and len(max_lag) == k:
+            lags = tuple(max_lag)
+        else:
+            raise ValueError(f'max_lag must be None, an int or {k} ints, not {max_lag!r}')
+        for lag in lags:
+            _args.int_at_least('max_lag', lag, 0)
+        return tuple(int(lag) for lag in lags)
+
+    def activation_correlogram(self, max_lag: Union[None, int, Tuple[int, ...]] = None,
+                               per_sample: bool = False) -> np.ndarray:
+        """How often plane q fires at offset D from plane p: ``C[p, q, D] = sum_n sum_u H[n, p, u] H[n, q, u + D]`` over
+        the u with u and u + D inside the plane (nothing wraps, in any reconstruction mode), for the lags
+        ``|D_k| <= max_lag[k]`` with lag ``D_k`` at index ``D_k + max_lag[k]``: float64 ``[P, P, *(2 L + 1)]``, or with
+        ``per_sample=True`` ``[N, P, P, *(2 L + 1)]`` in the order of ``H``.  P counts the effective planes (``atom * T +
+        transform`` with transforms).  ``C[p, q, D] == C[q, p, -D]``, and ``C[p, q, D]^2 <= C[p, p, 0] C[q, q, 0]``.
+
+        max_lag : ``None`` (``atom_shape - 1``: the range over which two occurrences touch), an int or one int >= 0 per
+                  shift axis; lags at or beyond the extent of an axis are 0
+
+        The correlogram reads ``H`` alone: any ``beta_loss``, weights, reconstruction mode and transforms.  On a backend
+        with ``activation_correlogram`` one pass over the activations where they live, every sum in double; any other
+        backend's ``H`` -- and a lag beyond that hook's limit -- goes through ``activation_correlogram_numpy`` on the
+        host.  Not collective: with a process group each rank reports its own samples, and C adds over the ranks."""
+        if self._H is None:
+            raise RuntimeError('activation_correlogram() needs a fitted model: call fit first')
+        lags = self._max_lag(max_lag)
+        _args.boolean('per_sample', per_sample)
+        hook = getattr(self._backend, 'activation_correlogram', None)
+        C = None
+        if hook is not None:
+            try:
+                C = hook(self._H, lags, per_sample=bool(per_sample))
+            except NotImplementedError:   # (volumes, a lag beyond the kernel's limit: nothing was written)
+                C = None
+        if C is None:
+            C = activation_correlogram_numpy(self._backend.to_ndarray(self._H), lags, bool(per_sample))
+        C = np.asarray(C, dtype=np.float64)
+        return self._in_order_of_V(C) if per_sample else C
+
+    def atom_cooccurrence(self, max_lag: Union[None, int, Tuple[int, ...]] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """(score ``[P, P]`` float64, lag ``[P, P, k]`` int64): ``score[p, q] = max_D C[p, q, D] / sqrt(C[p, p, 0]
+        C[q, q, 0])`` of ``activation_correlogram(max_lag)``, in [0, 1], and ``lag`` the D that reaches it (the first in C
+        order on a tie).  For p == q the lag 0 is left out; a plane with ``C[p, p, 0] == 0`` scores 0.  A score near 1 at
+        ``lag != 0`` says q is p's fixed-offset partner -- two halves of one larger motif: the atom window is too small, or
+        ``n_atoms`` too large; a high ``score[p, p]`` at lag D is a rhythm of period D.  Host algebra on the one pass; not
+        collective."""
+        return cooccurrence(self.activation_correlogram(max_lag))
 
     # -- how atoms overlap: a and the Gram matrix B of the atoms' contributions ------------------------------------------
     # With per-atom scale factors s (R(s) = sum s_m R_m) the objective is the exact quadratic

@@ -31,7 +31,7 @@ EXPORTS = (
     'tnmf_hip_ops_apply_W',
     'tnmf_hip_ctx_set_objective_tap', 'tnmf_hip_sample_objective', 'tnmf_hip_atom_terms',
     'tnmf_hip_atom_gram', 'tnmf_hip_atom_sources',
-    'tnmf_hip_find_peaks',
+    'tnmf_hip_find_peaks', 'tnmf_hip_activation_correlogram',
     'tnmf_hip_events_render', 'tnmf_hip_events_update', 'tnmf_hip_events_grad_W', 'tnmf_hip_events_gain',
     'tnmf_hip_events_norms', 'tnmf_hip_pursuit_score', 'tnmf_hip_pursuit_pick', 'tnmf_hip_events_landscape',
     'tnmf_hip_events_alternatives',
@@ -166,6 +166,7 @@ def load() -> ctypes.CDLL:
     lib.tnmf_hip_atom_gram.argtypes = [vp, gp, ci, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.tnmf_hip_atom_sources.argtypes = [vp, gp, ci, vp, ci, vp, ci, cd, vp, vp, vp, vp, vp, vp, vp]
     lib.tnmf_hip_find_peaks.argtypes = [vp, gp, vp, cd, pi, ci, vp, vp, sz, vp, vp]
+    lib.tnmf_hip_activation_correlogram.argtypes = [vp, gp, vp, pi, ci, vp, vp]
     ll = ctypes.c_longlong
     lib.tnmf_hip_events_render.argtypes = [vp, gp, vp, vp, ll, vp, vp, ll, vp, vp]
     lib.tnmf_hip_events_update.argtypes = [vp, gp, ci, vp, vp, vp, ll, vp, vp, cd, cd, vp]

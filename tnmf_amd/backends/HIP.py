@@ -921,6 +921,39 @@ class HIP_Backend(Backend):
         idx, order = torch.sort(idx[:total])
         return idx.cpu().numpy(), val[:total][order].cpu().numpy()
 
+    # -- activation correlogram ------------------------------------------------------------------------------------------
+    # Which planes of H co-occur, and at what offset (include/tnmf_hip.h, "activation correlogram"): one pass over H on the
+    # f64 matrix cores, and only the [P, P, lags] sums cross to the host.
+    CORRELOGRAM_MAX_LAG = {1: 1023, 2: 63}   # correlogram.h: kCorrMaxLag1, kCorrMaxLag2
+
+    def activation_correlogram(self, H: torch.Tensor, max_lag: Sequence[int], per_sample: bool = False) -> np.ndarray:
+        """``C[p, q, D] = sum_n sum_u H[n, p, u] H[n, q, u + D]`` for ``|D_k| <= max_lag[k]``, float64
+        ``[P, P, *(2 L + 1)]`` on the host, or per sample ``[n, P, P, *(2 L + 1)]`` -- of the resident activations as they
+        are, row-padded or not, in any reconstruction mode -> tnmf_hip_activation_correlogram.  NotImplementedError for
+        volumes and for a lag beyond the library's limit."""
+        k = len(self.atom_shape)
+        if k == 3:
+            raise NotImplementedError('activation correlogram: 1 or 2 shift axes only')
+        assert H.is_cuda and H.dtype == self._torch_dtype and H.dim() == 2 + k and len(max_lag) == k
+        limit = self.CORRELOGRAM_MAX_LAG[k]
+        if any(int(x) > limit for x in max_lag):
+            raise NotImplementedError(f'activation correlogram: max_lag {tuple(max_lag)!r} is beyond the limit of {limit} '
+                                      f'per axis on {k} shift ax{"is" if k == 1 else "es"}')
+        ld = self._row_stride(H)
+        if ld is None:
+            H, ld = H.contiguous(), 0
+        n, P = int(H.shape[0]), int(H.shape[1])
+        # (the shift shape is H's own, whatever the reconstruction mode: D = S, A = 1)
+        g = _lib.make_geom(n, P, self.n_channels, tuple(H.shape[2:]), (1,) * k, self._dtype_code, ld)
+        lags = (ctypes.c_int * 3)(*[int(x) for x in max_lag])
+        shape = ((n,) if per_sample else ()) + (P, P) + tuple(2 * int(x) + 1 for x in max_lag)
+        C = torch.empty(shape, dtype=torch.float64, device=self._device)
+        with self._timed('activation_correlogram'):
+            _lib.check(self._lib.tnmf_hip_activation_correlogram(self._ctx, ctypes.byref(g), _ptr(H), lags,
+                                                                 int(bool(per_sample)), _ptr(C), self._stream()),
+                       'tnmf_hip_activation_correlogram')
+        return C.cpu().numpy()
+
     # -- events: the detections rendered and refitted --------------------------------------------------------------------
     # The H side on a list of events (include/tnmf_hip.h, "events"): no buffer of H's size exists on this path.  The
     # support is fixed over a refit, so the sorted image list and the cell offsets are built once (event_list); only the

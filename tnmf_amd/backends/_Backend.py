@@ -48,6 +48,10 @@ raise ``NotImplementedError``, and then, as without the hooks, ``separate`` / ``
 A backend that declares ``supports_peaks`` offers ``find_peaks(H, threshold, radius, group) -> (idx, val)``: the ascending
 flat C-order indices (int64, host) in H's shape [n, P, *S] and the values of the detections of its native H
 (include/tnmf_hip.h, "detections"); without it ``detections()`` searches ``to_ndarray(H)`` on the host.
+``activation_correlogram(H, max_lag, per_sample=False) -> C`` (float64 ``[P, P, *(2 L + 1)]`` or ``[n, P, P, *(2 L + 1)]``,
+host): the correlogram of its native H (include/tnmf_hip.h, "activation correlogram"); it may raise ``NotImplementedError``,
+and then, as without the hook, ``activation_correlogram()`` runs ``activation_correlogram_numpy``
+(tnmf_amd/correlogram_host.py) on the host.
 A backend that declares ``supports_events`` works on lists of events (local sample, plane of the effective dictionary,
 shift in its H, strength; include/tnmf_hip.h, "events"): ``render_events(W, sample, plane, shift, strength) -> R``
 (backend-native ``[n_local, C, *D]``) and ``refit_events(V, W, sample, plane, shift, strength, n_iterations, sparsity=0.,

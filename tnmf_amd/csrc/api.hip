@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "atom_gram.h"
+#include "correlogram.h"
 #include "sources.h"
 #include "atoms.h"
 #include "beta.h"
@@ -1442,6 +1443,35 @@ int tnmf_hip_find_peaks(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
     return peaks_find(ctx, g, geom->dtype, H, threshold, idx_out, val_out, capacity, count_out,
                       static_cast<hipStream_t>(stream));
+}
+
+int tnmf_hip_activation_correlogram(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *H, const int *max_lag,
+                                    int per_sample, double *C_out, void *stream) {
+    if (!ctx || !geom || !max_lag) return TNMF_E_NULL;
+    if (geom->dtype != 0 && geom->dtype != 1) return TNMF_E_DTYPE;
+    if (geom->ndim == 3) return TNMF_E_UNSUPPORTED;
+    if ((geom->ndim != 1 && geom->ndim != 2) || geom->N < 0 || geom->M <= 0) return TNMF_E_GEOM;
+    int S[2] = {1, 1};   // one shift axis: a single row
+    for (int i = 0; i < geom->ndim; ++i) {
+        if (geom->D[i] <= 0 || geom->A[i] <= 0) return TNMF_E_GEOM;
+        if ((long long)geom->D[i] + geom->A[i] - 1 > 0x7fffffffLL) return TNMF_E_UNSUPPORTED;
+        S[2 - geom->ndim + i] = geom->D[i] + geom->A[i] - 1;
+    }
+    if (geom->h_row_stride > 0 && geom->h_row_stride < S[1]) return TNMF_E_GEOM;
+    const int Hs = geom->h_row_stride > 0 ? geom->h_row_stride : S[1];
+    CorrPlan p;
+    CHECK(correlogram_plan(geom->N, geom->M, S[0], S[1], Hs, geom->ndim, max_lag, per_sample != 0, geom->dtype, &p));
+    if (!C_out || (geom->N > 0 && !H)) return TNMF_E_NULL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    if (geom->N == 0) {   // no sample: nothing per sample, and sums of nothing
+        if (!per_sample)
+            TNMF_HIP_TRY(hipMemsetAsync(C_out, 0, (size_t)p.P * p.P * (2 * p.Ly + 1) * (2 * p.Lx + 1) * sizeof(double), s));
+        return TNMF_OK;
+    }
+    // work buffer: the partial sums per (segment, strip, pair of plane blocks, lag)
+    CHECK(ensure_buffer(&ctx->ob, &ctx->ob_bytes, correlogram_partial_bytes(p), false));
+    return launch_correlogram(p, geom->dtype, H, static_cast<double *>(ctx->ob), C_out, s);
 }
 
 // the geometry of the events entry points, checked: ndim 1 or 2 (3: TNMF_E_UNSUPPORTED), every size positive

@@ -73,7 +73,8 @@ struct tnmf_hip_ctx {
     size_t qb_bytes = 0;
     double *obj_tap = nullptr;   // objective tap (tnmf_hip_ctx_set_objective_tap): the caller's per-sample doubles, or NULL
     void *ob = nullptr;          // per-block partial sums of the per-sample objective (objective.hip); the partial sums and
-                                 // the taps of tnmf_hip_atom_terms (atoms.hip) and of tnmf_hip_atom_gram (atom_gram.hip)
+                                 // the taps of tnmf_hip_atom_terms (atoms.hip) and of tnmf_hip_atom_gram (atom_gram.hip);
+                                 // the partial sums of tnmf_hip_activation_correlogram (correlogram.hip)
     size_t ob_bytes = 0;
     // persistent schedule kernel: the operation list travels host -> device through a ring of PINNED staging slots (an
     // asynchronous copy from the caller's pageable array could still be reading it after the call has returned); a slot is
