@@ -73,16 +73,17 @@ def test_unknown_backend_name():
         TransformInvariantNMF(n_atoms=2, atom_shape=(3,), backend='numpy_fft')
 
 
+@pytest.mark.parametrize('sag_lambda', [0.8, 1.0])
 @pytest.mark.parametrize('algorithm', list(MiniBatchAlgorithm))
-def test_epochs_as_operation_lists_equal_the_batch_by_batch_schedules(algorithm):
+def test_epochs_as_operation_lists_equal_the_batch_by_batch_schedules(algorithm, sag_lambda):
     """The front end describes a mini-batch epoch as ONE operation list for backends that offer `run_schedule`
     (HIP_Backend -> tnmf_hip_run_schedule): H half steps, gradient blends acc = a * acc + b * g with the coefficients of
-    reference TransformInvariantNMF.py:444-455 (first use from the integer 0 included), W updates.  Interpreted step by step
-    with the oracle's primitives, the lists must reproduce the batch-by-batch schedules -- same RNG draws, same accumulator
-    side effect (pos += eps) across epochs."""
+    reference TransformInvariantNMF.py:444-455 (first use from the integer 0 included; (1, 1) for sag_lambda == 1), W updates.
+    Interpreted step by step with the oracle's primitives, the lists must reproduce the batch-by-batch schedules -- same RNG
+    draws, same accumulator side effect (pos += eps) across epochs."""
     rng = np.random.default_rng(3)
     V = rng.random((7, 2, 12, 14))
-    kw = dict(algorithm=algorithm, batch_size=2, n_epochs=3, sag_lambda=0.8, sparsity_H=0.05)
+    kw = dict(algorithm=algorithm, batch_size=2, n_epochs=3, sag_lambda=sag_lambda, sparsity_H=0.05)
     res = {}
     for flavour in ('lists', 'batch_by_batch'):
         np.random.seed(42)
@@ -99,6 +100,68 @@ def test_epochs_as_operation_lists_equal_the_batch_by_batch_schedules(algorithm)
                 assert be.schedule_calls[0] == ['H'] * 4 + ['G', 'W']
     np.testing.assert_allclose(res['lists'][0], res['batch_by_batch'][0], rtol=1e-12, atol=0)
     np.testing.assert_allclose(res['lists'][1], res['batch_by_batch'][1], rtol=1e-12, atol=1e-300)
+
+
+_FH, _FW, _LG = 'fused_update_H', 'fused_update_W', 'local_gradient_W'
+_AR, _AW = ('all_reduce_gradient_W',), ('apply_W',)
+_H, _GW, _N = 'reconstruction_gradient_H', 'reconstruction_gradient_W', ('normalize',)
+# one epoch at batch_size=2, seed 42: N = 4 draws the order (0, 1) of its two batches, N = 6 the order (1, 0, 2) of its three
+_STEP_BY_STEP_CALLS = {
+    (4, True): {
+        'Cyclic_MU': [(_FH, 0, 2), (_LG, 0, 2), (_FH, 2, 4), (_LG, 2, 4), _AR, _AW],
+        'ASG_MU': [(_FH, 0, 2), (_FW, 0, 2), (_FH, 2, 4), (_FW, 2, 4)],
+        'GSG_MU': [(_FH, 0, 4), (_FW, 2, 4)],
+        'ASAG_MU': [(_FH, 0, 2), (_GW, 0, 2), _N, (_FH, 2, 4), (_GW, 2, 4), _N],
+        'GSAG_MU': [(_FH, 0, 4), (_GW, 2, 4), _N],
+    },
+    (4, False): {
+        'Cyclic_MU': [(_H, 0, 2), (_GW, 0, 2), (_H, 2, 4), (_GW, 2, 4), _N],
+        'ASG_MU': [(_H, 0, 2), (_GW, 0, 2), _N, (_H, 2, 4), (_GW, 2, 4), _N],
+        'GSG_MU': [(_H, 0, 4), (_GW, 2, 4), _N],
+        'ASAG_MU': [(_H, 0, 2), (_GW, 0, 2), _N, (_H, 2, 4), (_GW, 2, 4), _N],
+        'GSAG_MU': [(_H, 0, 4), (_GW, 2, 4), _N],
+    },
+    (6, True): {
+        'Cyclic_MU': [(_FH, 0, 2), (_LG, 0, 2), (_FH, 2, 4), (_LG, 2, 4), (_FH, 4, 6), (_LG, 4, 6), _AR, _AW],
+        'ASG_MU': [(_FH, 2, 4), (_FW, 2, 4), (_FH, 0, 2), (_FW, 0, 2), (_FH, 4, 6), (_FW, 4, 6)],
+        'GSG_MU': [(_FH, 0, 6), (_FW, 4, 6)],
+        'ASAG_MU': [(_FH, 2, 4), (_GW, 2, 4), _N, (_FH, 0, 2), (_GW, 0, 2), _N, (_FH, 4, 6), (_GW, 4, 6), _N],
+        'GSAG_MU': [(_FH, 0, 6), (_GW, 4, 6), _N],
+    },
+    (6, False): {
+        'Cyclic_MU': [(_H, 0, 2), (_GW, 0, 2), (_H, 2, 4), (_GW, 2, 4), (_H, 4, 6), (_GW, 4, 6), _N],
+        'ASG_MU': [(_H, 2, 4), (_GW, 2, 4), _N, (_H, 0, 2), (_GW, 0, 2), _N, (_H, 4, 6), (_GW, 4, 6), _N],
+        'GSG_MU': [(_H, 0, 6), (_GW, 4, 6), _N],
+        'ASAG_MU': [(_H, 2, 4), (_GW, 2, 4), _N, (_H, 0, 2), (_GW, 0, 2), _N, (_H, 4, 6), (_GW, 4, 6), _N],
+        'GSAG_MU': [(_H, 0, 6), (_GW, 4, 6), _N],
+    },
+}
+
+
+@pytest.mark.parametrize('hooks', [True, False])
+@pytest.mark.parametrize('n_samples', [4, 6])
+@pytest.mark.parametrize('algorithm', list(MiniBatchAlgorithm))
+def test_step_by_step_epochs_issue_the_recorded_backend_calls(algorithm, n_samples, hooks):
+    """An epoch that does not go out as one operation list (here: a backend without `run_schedule`) is walked step by step:
+    the backend must see exactly the calls, on exactly the slices, recorded before the epochs were stated as lists only --
+    the launch structure that a batch-by-batch run has on the GPU.  Three batches drawn out of order show the H steps of
+    GSG / GSAG joined into one call."""
+    be, log = OracleBackend(hooks=hooks), []
+    for name in (_FH, _FW, _LG, _AR[0], _AW[0], _H, _GW, _N[0]):
+        fn = getattr(be, name, None)
+        if fn is None:
+            continue
+
+        def logged(*args, _fn=fn, _name=name, **kw):
+            s = [(a.start, a.stop) for a in args if isinstance(a, slice)]
+            log.append((_name,) + (s[0] if s else ()))
+            return _fn(*args, **kw)
+        setattr(be, name, logged)
+    V = np.random.default_rng(3).random((n_samples, 2, 12, 14))
+    np.random.seed(42)
+    nmf = TransformInvariantNMF(n_atoms=3, atom_shape=(3, 4), backend=be)
+    nmf.fit(V, algorithm=algorithm, batch_size=2, n_epochs=1, sag_lambda=0.8)
+    assert log == _STEP_BY_STEP_CALLS[n_samples, hooks][algorithm.name]
 
 
 def test_tiny_full_batch_iterations_go_out_as_operation_lists():

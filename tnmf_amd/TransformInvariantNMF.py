@@ -71,10 +71,11 @@ def _joined(batches: list) -> list:
     Overlapping or strided slices: the list as it is."""
     spans = []
     for b in batches:
-        if b.step not in (None, 1) or b.start is None or b.stop is None or b.start < 0 or b.stop < 0:
+        lo, hi = b.start, b.stop
+        if b.step not in (None, 1) or lo is None or hi is None or lo < 0 or hi < 0:
             return list(batches)
-        if b.stop > b.start:
-            spans.append((b.start, b.stop))
+        if hi > lo:
+            spans.append((lo, hi))
     spans.sort()
     if any(spans[i][0] < spans[i - 1][1] for i in range(1, len(spans))):
         return list(batches)
@@ -1506,21 +1507,28 @@ class TransformInvariantNMF:
         if self._beta <= 0 and np.any(V == 0 if G is None else (V == 0) & (G > 0)):
             raise ValueError(f'beta_loss={self._beta} <= 0 needs V without zeros')
 
+    def _begin_fit(self, V: np.ndarray, weights, keep_W: bool, objective_every, tol, sparsity_H: float,
+                   inhibition_strength: float, cross_atom_inhibition_strength: float):
+        """What fit_batch and fit_minibatches share before their loops: the arguments checked, W and H initialised, an empty
+        history.  Returns (objective_every, tol, h_args)."""
+        every, tol = self._convergence_args(objective_every, tol)
+        G = self._weights_of(V, weights)
+        self._check_samples(V, G)
+        assert sparsity_H >= 0 and inhibition_strength >= 0 and cross_atom_inhibition_strength >= 0
+        self._check_beta_samples(V, G)
+        self._init_fit(V, keep_W, G)
+        self._begin_history()
+        return every, tol, dict(sparsity=sparsity_H, inhibition=inhibition_strength,
+                                cross_inhibition=cross_atom_inhibition_strength)
+
     # -- full batch (reference :282-348) ------------------------------------------------------------------------
     def fit_batch(self, V: np.ndarray, n_iterations: int = 1000, update_H: bool = True, update_W: bool = True,
                   keep_W: bool = False, sparsity_H: float = 0., inhibition_strength: float = 0.,
                   cross_atom_inhibition_strength: float = 0., progress_callback: ProgressCallback = None,
                   weights=None, objective_every: Optional[int] = None, tol: Optional[float] = None):
-        every, tol = self._convergence_args(objective_every, tol)
-        G = self._weights_of(V, weights)
-        self._check_samples(V, G)
         assert update_H or update_W
-        assert sparsity_H >= 0 and inhibition_strength >= 0 and cross_atom_inhibition_strength >= 0
-        self._check_beta_samples(V, G)
-        self._init_fit(V, keep_W, G)
-        h_args = dict(sparsity=sparsity_H, inhibition=inhibition_strength,
-                      cross_inhibition=cross_atom_inhibition_strength)
-        self._begin_history()
+        every, tol, h_args = self._begin_fit(V, weights, keep_W, objective_every, tol, sparsity_H, inhibition_strength,
+                                             cross_atom_inhibition_strength)
         n_done = 0
         for iteration in range(n_iterations):
             record = every is not None and iteration % every == 0
@@ -1538,19 +1546,13 @@ class TransformInvariantNMF:
                         sparsity_H: float = 0., inhibition_strength: float = 0.,
                         cross_atom_inhibition_strength: float = 0., progress_callback: ProgressCallback = None,
                         weights=None, objective_every: Optional[int] = None, tol: Optional[float] = None):
-        every, tol = self._convergence_args(objective_every, tol)
-        G = self._weights_of(V, weights)
-        self._check_samples(V, G)
-        assert sparsity_H >= 0 and inhibition_strength >= 0 and cross_atom_inhibition_strength >= 0
         assert isinstance(algorithm, MiniBatchAlgorithm)
-        self._check_beta_samples(V, G)
         # The reference decides whether to shuffle V with `algorithm in (5, 6, 7, 8)` (:410), an Enum-vs-int test
         # that is never true, so V is never shuffled; this front end keeps that behaviour.
-        self._init_fit(V, keep_W, G)
+        every, tol, h_args = self._begin_fit(V, weights, keep_W, objective_every, tol, sparsity_H, inhibition_strength,
+                                             cross_atom_inhibition_strength)
         plan = getattr(self._backend, 'minibatch_slices', None)
         batches = plan(batch_size) if plan is not None else _sequential_minibatches(len(self._V), batch_size)
-        h_args = dict(sparsity=sparsity_H, inhibition=inhibition_strength,
-                      cross_inhibition=cross_atom_inhibition_strength)
         epoch_fn = {
             MiniBatchAlgorithm.Cyclic_MU: self._epoch_cyclic,
             MiniBatchAlgorithm.ASG_MU: self._epoch_asg,
@@ -1559,7 +1561,6 @@ class TransformInvariantNMF:
             MiniBatchAlgorithm.GSAG_MU: self._epoch_gsag,
         }[algorithm]
         state = None
-        self._begin_history()
         n_done = 0
         for epoch in range(n_epochs):
             # (the exact objective at the epoch boundary: one reconstruction per recorded epoch; the epochs run as they do)
@@ -1582,26 +1583,25 @@ class TransformInvariantNMF:
             return lambda V, W, H, s: self._backend.local_gradient_W(V, W, H, s, **self._objective())
         return self._fused('local_gradient_W')
 
-    def _blend_gradient_W(self, acc, lam: float, s: slice):
-        """acc <- (1 - lam) * acc + lam * grad_W(batch s); lam == 1 is a plain sum (reference :444-455)."""
+    def _blend_gradient_W(self, acc, a: float, b: float, s: slice):
+        """acc <- a * acc + b * grad_W(batch s), the gradient summed over the ranks (reference :444-455); a == 0: acc is still
+        the reference's integer 0 and the result a new accumulator."""
         if not self._plain_frobenius:
             negpos = self._backend.all_reduce_gradient_W(self._local_gradient_W()(self._V, self._W, self._H, s))
             neg, pos = negpos[0], negpos[1]
         else:
             neg, pos = self._backend.reconstruction_gradient_W(self._V, self._W, self._H, s)
-        if acc is None:
-            # the reference starts from the integers (0, 0): `0 + g` / `0 * (1 - lam) + lam * g`
-            if lam == 1:
-                return [neg, pos]
-            return [lam * neg, lam * pos]
-        if lam == 1:
+        if a == 0:
+            # `0 + g` / `0 * (1 - lam) + lam * g`
+            return [neg, pos] if b == 1 else [b * neg, b * pos]
+        if a == 1 and b == 1:
             acc[0] += neg
             acc[1] += pos
         else:
-            acc[0] *= (1 - lam)
-            acc[1] *= (1 - lam)
-            acc[0] += lam * neg
-            acc[1] += lam * pos
+            acc[0] *= a
+            acc[1] *= a
+            acc[0] += b * neg
+            acc[1] += b * pos
         return acc
 
     def _apply_accumulated_W(self, acc):
@@ -1609,10 +1609,10 @@ class TransformInvariantNMF:
         self._multiplicative_update(self._W, acc[0], acc[1], normalization_axes=self._axes_W_normalization)
         self._expand_W()
 
-    # One epoch of a mini-batch schedule as ONE call of the backend (HIP_Backend.run_schedule -> tnmf_hip_run_schedule):
-    # the epoch functions below describe the epoch as a list of operations -- ('H', batch), ('G', batch, a, b) for
-    # acc = a * acc + b * gradient_W(batch), ('W',) for the W update from acc -- where the backend offers that and no
-    # lateral term is on (those go through tnmf_hip_update_H_ex batch by batch).
+    # An epoch of a mini-batch schedule is stated ONCE, as a list of operations -- ('H', batch), ('G', batch, a, b) for
+    # acc = a * acc + b * gradient_W(batch), ('W',) for the W update from acc: the epoch functions below only build that list,
+    # _run_ops executes it.  Where the backend offers that and no lateral term is on (those go through tnmf_hip_update_H_ex
+    # batch by batch) the list is ONE call of the backend (HIP_Backend.run_schedule -> tnmf_hip_run_schedule).
     def _scheduler(self, h_args):
         run = self._fused('run_schedule') if self._use_schedules and self._plain_frobenius else None
         if run is None or not getattr(self._backend, 'supports_schedules', False):
@@ -1628,111 +1628,108 @@ class TransformInvariantNMF:
             return 0., (1. if lam == 1 else lam)
         return (1., 1.) if lam == 1 else (1. - lam, lam)
 
+    def _summing_hook(self, ops, h_args):
+        """_local_gradient_W() when the list only sums gradients for the W update that ends it -- this rank's [neg | pos]
+        can then be summed as they are and cross the collective ONCE per list -- else False."""
+        local = None if h_args['inhibition'] > 0 or h_args['cross_inhibition'] > 0 else self._local_gradient_W()
+        if local is None or ops[-1][0] != 'W':
+            return False
+        sums = all(op[0] == 'H' or (op[0] == 'G' and op[2] in (0, 1) and op[3] == 1) for op in ops[:-1])
+        return local if sums else False
+
+    def _run_ops(self, ops, h_args, state=None, carried=False):
+        """Execute the operation list of one epoch.  `carried`: the accumulator outlives the list (ASAG / GSAG) -- `state` is
+        the one the previous epoch returned, None before the first; returns the accumulator, None when not carried.
+
+        One call of the backend where _scheduler offers it.  Otherwise step by step with the half steps above:
+        * a run of H steps is issued per contiguous run of samples (_joined: they commute), a single one as it is (an empty
+          tail batch of a multi-rank plan included);
+        * ('G', s, 0, 1) directly followed by ('W',), accumulator not carried, is the W half step _update_W(s);
+        * a list that only sums gradients, not carried, takes the local sums of _summing_hook: one all-reduce at 'W';
+        * anything else blends the reduced gradient of every batch into the accumulator (_blend_gradient_W)."""
+        run = self._scheduler(h_args)
+        if run is not None and len(ops) > 1:   # (not a Cyclic epoch without batches, a lone ('W',))
+            acc = self._backend.new_gradient_accumulator(self._W) if state is None else state
+            run(self._V, self._W, self._H, ops, acc, sparsity=h_args['sparsity'], eps=self.eps)
+            return acc if carried else None
+        acc, blend = state, None
+        local = False if carried else None   # (None: decided by the first gradient that is no W half step of its own)
+        rest = iter(ops + [(None,)])         # (a sentinel: every operation has a next one to look at)
+        op = next(rest)
+        while op[0] is not None:
+            kind, nxt = op[0], next(rest)
+            if kind == 'H':
+                if nxt[0] == 'H':
+                    span = [op[1], nxt[1]]
+                    for nxt in rest:
+                        if nxt[0] != 'H':
+                            break
+                        span.append(nxt[1])
+                    for s in _joined(span):
+                        self._update_H(s, **h_args)
+                else:
+                    self._update_H(op[1], **h_args)
+            elif kind == 'G':
+                _, s, a, b = op
+                if a == 0 and b == 1 and nxt[0] == 'W' and not carried:
+                    self._update_W(s)
+                    nxt = next(rest)
+                else:
+                    if local is None:
+                        local, blend = self._summing_hook(ops, h_args), self._fused('blend_gradient_W')
+                    if not local:
+                        acc = self._blend_gradient_W(acc, a, b, s)
+                    else:
+                        part = local(self._V, self._W, self._H, s)
+                        if a == 0:
+                            acc = part
+                        elif blend is not None:
+                            blend(acc, part, 1., 1.)
+                        else:
+                            acc += part
+            elif local:
+                self._backend.apply_W(self._W, self._backend.all_reduce_gradient_W(acc), eps=self.eps)
+                self._expand_W()
+            else:
+                self._apply_accumulated_W(acc)
+            op = nxt
+        return acc if carried else None
+
     def _epoch_cyclic(self, _state, batches, h_args, _lam):
         """Algorithm 4: H per batch, W once per epoch from the summed gradient (reference :457-465)."""
-        run = self._scheduler(h_args)
-        if run is not None and len(batches):
-            ops = []
-            for i, batch in enumerate(batches):
-                ops += [('H', batch), ('G', batch, 0. if i == 0 else 1., 1.)]
-            run(self._V, self._W, self._H, ops + [('W',)], self._backend.new_gradient_accumulator(self._W),
-                sparsity=h_args['sparsity'], eps=self.eps)
-            return None
-        local = self._local_gradient_W()
-        lateral = h_args['inhibition'] > 0 or h_args['cross_inhibition'] > 0
-        if local is not None and not lateral:
-            # sum this rank's [neg | pos] over its batches, ONE all-reduce per epoch, then the fused MU
-            total = None
-            blend = self._fused('blend_gradient_W')
-            for batch in batches:
-                self._update_H(batch, **h_args)
-                part = local(self._V, self._W, self._H, batch)
-                if total is None:
-                    total = part
-                elif blend is not None:
-                    blend(total, part, 1., 1.)
-                else:
-                    total += part
-            total = self._backend.all_reduce_gradient_W(total)
-            self._backend.apply_W(self._W, total, eps=self.eps)
-            self._expand_W()
-            return None
-        acc = None
-        for batch in batches:
-            self._update_H(batch, **h_args)
-            acc = self._blend_gradient_W(acc, 1., batch)
-        self._apply_accumulated_W(acc)
-        return None
+        ops = []
+        for i, batch in enumerate(batches):
+            ops += [('H', batch), ('G', batch, 0. if i == 0 else 1., 1.)]
+        return self._run_ops(ops + [('W',)], h_args)
 
     def _epoch_asg(self, _state, batches, h_args, _lam):
         """Algorithm 5: H and W after every (shuffled) batch (reference :467-472)."""
-        run = self._scheduler(h_args)
-        if run is not None:
-            ops = []
-            for batch in _permuted(batches):
-                ops += [('H', batch), ('G', batch, 0., 1.), ('W',)]
-            run(self._V, self._W, self._H, ops, self._backend.new_gradient_accumulator(self._W),
-                sparsity=h_args['sparsity'], eps=self.eps)
-            return None
+        ops = []
         for batch in _permuted(batches):
-            self._update_H(batch, **h_args)
-            self._update_W(batch)
-        return None
+            ops += [('H', batch), ('G', batch, 0., 1.), ('W',)]
+        return self._run_ops(ops, h_args)
 
     def _epoch_gsg(self, _state, batches, h_args, _lam):
         """Algorithm 6: H for every shuffled batch, W from the last batch only (reference :474-479)."""
-        batch = slice(0, 0)
-        run = self._scheduler(h_args)
-        if run is not None:
-            order = _permuted(batches)
-            ops = [('H', b) for b in order] + [('G', order[-1] if len(order) else batch, 0., 1.), ('W',)]
-            run(self._V, self._W, self._H, ops, self._backend.new_gradient_accumulator(self._W),
-                sparsity=h_args['sparsity'], eps=self.eps)
-            return None
         order = _permuted(batches)
-        batch = order[-1] if len(order) else batch
-        for run_ in _joined(order):     # (the H steps of an epoch commute: one call per contiguous run of samples)
-            self._update_H(run_, **h_args)
-        self._update_W(batch)
-        return None
+        ops = [('H', b) for b in order] + [('G', order[-1] if len(order) else slice(0, 0), 0., 1.), ('W',)]
+        return self._run_ops(ops, h_args)
 
     def _epoch_asag(self, state, batches, h_args, lam):
         """Algorithm 7: running average of the W gradient over batches AND epochs (reference :481-491)."""
-        run = self._scheduler(h_args)
-        if run is not None:
-            first = state is None
-            acc = self._backend.new_gradient_accumulator(self._W) if first else state
-            ops = []
-            for batch in _permuted(batches):
-                ops += [('H', batch), ('G', batch) + self._blend_coefficients(first, lam), ('W',)]
-                first = False
-            run(self._V, self._W, self._H, ops, acc, sparsity=h_args['sparsity'], eps=self.eps)
-            return acc if len(ops) else state
+        first = state is None
+        ops = []
         for batch in _permuted(batches):
-            self._update_H(batch, **h_args)
-            state = self._blend_gradient_W(state, lam, batch)
-            self._apply_accumulated_W(state)
-        return state
+            ops += [('H', batch), ('G', batch) + self._blend_coefficients(first, lam), ('W',)]
+            first = False
+        return self._run_ops(ops, h_args, state, carried=True)
 
     def _epoch_gsag(self, state, batches, h_args, lam):
         """Algorithm 8: H for every batch, averaged gradient refreshed from the last one (reference :493-504)."""
-        batch = slice(0, 0)
-        run = self._scheduler(h_args)
-        if run is not None:
-            first = state is None
-            acc = self._backend.new_gradient_accumulator(self._W) if first else state
-            order = _permuted(batches)
-            ops = [('H', b) for b in order]
-            ops += [('G', order[-1] if len(order) else batch) + self._blend_coefficients(first, lam), ('W',)]
-            run(self._V, self._W, self._H, ops, acc, sparsity=h_args['sparsity'], eps=self.eps)
-            return acc
         order = _permuted(batches)
-        batch = order[-1] if len(order) else batch
-        for run_ in _joined(order):
-            self._update_H(run_, **h_args)
-        state = self._blend_gradient_W(state, lam, batch)
-        self._apply_accumulated_W(state)
-        return state
+        ops = [('H', b) for b in order]
+        ops += [('G', order[-1] if len(order) else slice(0, 0)) + self._blend_coefficients(state is None, lam), ('W',)]
+        return self._run_ops(ops, h_args, state, carried=True)
 
     # -- streaming (reference :506-523) ---------------------------------------------------------------------------
     def fit_stream(self, V: Iterator[np.ndarray], subsample_size: int = 3, max_subsamples: int = None, **kwargs):
