@@ -119,7 +119,9 @@ const char *tnmf_hip_ctx_last_path(const tnmf_hip_ctx *ctx);
  * spectra of the samples V it transformed last, and reuse them while the same pointers and geometry come back (the
  * reference's NumPy_CachingFFT.py:22-140 caches spectra the same way).  Off by default.  A caller that enables it
  * vouches that H changes only through this library and V not at all, and calls tnmf_hip_ctx_invalidate() after
- * writing either by any other means. */
+ * writing either by any other means.  The spectra of the dictionary W are kept likewise, between the entry points that
+ * write W (tnmf_hip_mu_update, _normalize_W, _apply_W, the group and atom-operator entry points, _run_schedule): a
+ * caller who writes W by other means calls tnmf_hip_ctx_invalidate() as well, and that call is sufficient. */
 int tnmf_hip_ctx_set_cache(tnmf_hip_ctx *ctx, int enable);
 int tnmf_hip_ctx_invalidate(tnmf_hip_ctx *ctx);
 /* The resident problem of a fit: geom->N samples of activations at H (row stride geom->h_row_stride) and of samples at V

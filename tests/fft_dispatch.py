@@ -130,7 +130,8 @@ def family(geometry, dtype, path, primitive):
     return 'fft'
 
 
-Layout = namedtuple('Layout', 'Ly Lx KX KXP resident ngroups nper chunk mgroups mper sT')
+Layout = namedtuple('Layout', 'Ly Lx KX KXP resident ngroups nper chunk mgroups mper sT '
+                              'sSH sS sD T SH SV VT SW TWr total_no_window total')   # (byte sizes per sample, byte offsets)
 
 
 def sample_groups(N, M, tiles):
@@ -159,7 +160,40 @@ def make_layout(geometry, dtype, path, n_call=None, budget=WINDOW_BUDGET):
     mg = max(1, min(cdiv(1024, chunk * cdiv(KX, 16) * 2), M))                   # :115-117
     mper = cdiv(M, mg)                                                          # :118
     resident = not (mixed_has_reconstruct(geometry, dtype) and mixed_has_grad_W(geometry, dtype))   # :131
-    return Layout(Ly, Lx, KX, KXP, resident, ngroups, nper, chunk, cdiv(M, mper), mper, sT)
+    # the workspace, in the order fft.hip takes it: sizes follow the resident sample count N, never the call's
+    Dy, _, Ay, Ax, _, _ = _dims(geometry)
+    Nf = N if N > 0 else 1                                                      # :100
+    sSH, sS, sD = M * Ly * KXP * csz, C * Ly * KXP * csz, C * Dy * KXP * csz    # :102-104
+    nSW = M * C * Ly * KXP * csz                                                # :120
+    at = [0]
+
+    def take(nbytes):                                                           # :122-126
+        o = at[0]
+        at[0] += align_up(nbytes, 256)
+        return o
+
+    T = take(Nf * sT + 64 * KXP * csz)                                          # :128
+    SH = take(Nf * sSH if resident else 0)                                      # :132
+    SV = take(Nf * sS)                                                          # :133
+    take(Nf * sS)                                                               # :134  SR
+    take(Nf * sD)                                                               # :135  Ts
+    VT = take(Nf * sD)                                                          # :136
+    take(Nf * sD)                                                               # :137  RT
+    SW = take(nSW)                                                              # :138
+    take(nSW)                                                                   # :139  SWf
+    take(2 * M * C * Ay * KXP * csz)                                            # :140  TW
+    TWr = take(M * C * Ay * KXP * csz)                                          # :141
+    take(2 * M * C * Ay * Ax * (csz // 2))                                      # :142  Wt
+    nG = max(nSW * sample_groups(N, M, tiles)[0], MIX_MAX_GROUPS * M * C * Ay * KXP * csz)   # :145
+    take(nG)                                                                    # :146  Gn
+    take(nG)                                                                    # :147  Gp
+    take(nSW * 2)                                                               # :148  Gs
+    take(2 * M * C * Ay * Ax * (csz // 2))                                      # :149  Wo
+    total_no_window = at[0]                                                     # :150
+    take(chunk_full * sT)                                                       # :152  Tn
+    take(chunk_full * sT)                                                       # :153  Tp
+    return Layout(Ly, Lx, KX, KXP, resident, ngroups, nper, chunk, cdiv(M, mper), mper, sT,
+                  sSH, sS, sD, T, SH, SV, VT, SW, TWr, total_no_window, at[0])
 
 
 def mix_groups(N, C, M, Ay, KX, num_cu=NUM_CU):

@@ -592,13 +592,18 @@ int fft_reconstruct(tnmf_hip_ctx *ctx, const Geo &g, int dtype, const void *W, c
     const Lay &l = c.l;
     CHECK(rows_of_H(ctx, g, c, dtype, H, s));
     FftState &f = ctx->fft;
-    // the spectra of W this primitive needs are kept while W stays the same (mini-batch schedules: one W per epoch)
+    // the spectra of W this primitive needs are kept while W stays the same (mini-batch schedules: one W per epoch).
+    // Their workspace offset follows the sample count the layout was made for (make_layout: SW and TWr come after the
+    // per-sample arrays), so W_geo.N records THAT count -- the binding's for a slice of it, the call's otherwise -- and a
+    // hit needs the same: a foreign problem, an implicit re-binding or an unbind in between lays the workspace out anew.
+    const int resident_N = c.sl.cached ? f.geo.N : g.N;
     const bool w_hit = f.cache_enabled && f.W_ok && f.W_owner == W && f.W_dtype == dtype && same_shape(f.W_geo, g) &&
-                       (c.sl.cached || f.W_geo.N == g.N);   // (same layout: a slice of the binding, or the same call shape)
+                       f.W_geo.N == resident_N;
     auto w_mark = [&]() {
         f.W_ok = f.cache_enabled;
         f.W_owner = W;
         f.W_geo = g;
+        f.W_geo.N = resident_N;
         f.W_dtype = dtype;
     };
     if (use_mixed(g, dtype, false)) {
