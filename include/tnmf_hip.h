@@ -584,6 +584,39 @@ int tnmf_hip_find_peaks(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void
 int tnmf_hip_activation_correlogram(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *H, const int *max_lag,
                                     int per_sample, double *C_out, void *stream);
 
+/* ---- triggered sums: the data around the places where a plane fires (ABI 8, additive: the version stays 8) -----------------
+ * The W gradient's own correlation on a window larger than the atom.  geom describes the samples as everywhere (N, M = P
+ * planes, D, A, dtype, h_row_stride; C is not read).  H is the PADDED activations [N, P, *(D + A - 1)] (the padding table
+ * of "reconstruction modes"), rows `h_row_stride` apart, pad columns never read; Y is [N, n_fields, *D], C-contiguous, of
+ * the geometry's dtype: the data, the reconstruction, the residual, the weights.  With a margin m_k >= 0 per shift axis
+ *   X[p, f, j] = sum_n sum_q H[n, p, q]^power * Y[n, f, q - (A - 1) - m + j]      0 <= j_k < A_k + 2 m_k, power 1 or 2,
+ * over the terms whose index of Y lies inside the sample: X_out is [P, n_fields, *(A + 2 m)] doubles on the device, or
+ * with per_sample != 0 [N, P, n_fields, *(A + 2 m)].  Every element is written; an entry with no term is an exact 0, and
+ * N = 0 gives zeros for the summed form.  At m = 0 and power 1 this is `neg` (Y = V) and `pos` (Y = R) of the W gradient.
+ * 1 or 2 shift axes.
+ * Arithmetic: both operands converted to double, the square of power = 2 taken in double (exact for float H), products and
+ * sums on v_mfma_f64_16x16x4_f64: 16 planes of H are the rows, 16 consecutive window columns of one (field, window row)
+ * the columns -- the B operand is a Toeplitz read of one staged row of Y -- and 4 pixels along x the contraction.  Per
+ * (sample, pixel tile) the tile of 16 planes (one axis: 256 pixels, double 128; two: 4 x 64, double 2 x 64) and the patch
+ * of Y it meets under one chunk of up to 32 such cells are staged in LDS.  Partial sums per (sample with per_sample, else
+ * the whole call; strip of (sample, tile) items; block of 16 planes; cell) are added in strip order by a second kernel: no
+ * floating-point atomics, the same bits from run to run.
+ * The work buffer is the CALLER's (as the workspace of tnmf_hip_events_grad_W): tnmf_hip_triggered_sums_plan writes the
+ * bytes the call with the same geom, n_fields, margin and per_sample needs into *work_bytes (0 with N = 0) and refuses
+ * exactly what the call refuses, so a caller learns TNMF_E_UNSUPPORTED before it allocates.  The context's own buffers
+ * are not touched.
+ * Limits: a window A + 2 m <= 4096 with one shift axis, <= 128 per axis with two; any P, any n_fields.  Asynchronous on
+ * the stream.
+ * TNMF_E_NULL: ctx, geom, margin, X_out (work_bytes of _plan), work with work_bytes > 0, H or Y with N > 0.  TNMF_E_DTYPE.
+ * TNMF_E_GEOM: ndim not 1..3, sizes <= 0 (N < 0), a negative margin, n_fields < 1, power not 1 or 2, a row stride below the
+ * shift width.  TNMF_E_UNSUPPORTED: ndim == 3, a window beyond that limit, more than 2^31 - 1 workgroups or outputs.
+ * TNMF_E_WORKSPACE: work_bytes below the plan's -- all before anything is written. */
+int tnmf_hip_triggered_sums_plan(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int n_fields, const int *margin,
+                                 int per_sample, size_t *work_bytes);
+int tnmf_hip_triggered_sums(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *H, const void *Y, int n_fields,
+                            const int *margin, int power, int per_sample, void *work, size_t work_bytes,
+                            double *X_out, void *stream);
+
 /* ---- events: render, refit and learn from a list of detections (ABI 8, additive: the version stays 8) -----------------------------
  * The H side with the activations held as a list.  An EVENT is (n, p, u, h): local sample n, plane p of the effective
  * dictionary W_eff[P, C, *A] (P = geom->M; with transforms p = atom * T + transform), shift index u in the activations of

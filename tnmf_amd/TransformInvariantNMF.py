@@ -31,7 +31,7 @@ import numpy as np
 from . import _args
 from . import transforms as _transforms
 from .atoms_host import (atom_gram_numpy, atom_terms_numpy, gram_drop, gram_elimination, gram_scales,
-                         gram_set_gain)
+                         gram_set_gain, pad_activations_numpy)
 from .backends._Backend import Backend, sliceNone
 from .correlogram_host import activation_correlogram_numpy, cooccurrence
 # (the host side of the events; the names stay importable from this module)
@@ -42,6 +42,10 @@ from .events_host import (event_boxes, event_images, events_alternatives_numpy, 
 from .patches_host import (FRAMES as _PATCH_FRAMES, SOURCES as _PATCH_SOURCES, event_patch_moments_numpy,  # noqa: F401
                            event_patches_numpy, modes_from_moments)
 from .sources_host import OUTPUTS as _SOURCE_OUTPUTS, dominant_numpy, separate_numpy, source_tables
+from .triggered_host import extend_atoms, tap_gains_from_sums, triggered_sums_numpy, window_gains
+
+# the fields activation_triggered_sums correlates the activations with
+_TRIGGERED_SOURCES = ('data', 'reconstruction', 'residual')
 
 
 class MiniBatchAlgorithm(enum.Enum):
@@ -1179,6 +1183,124 @@ class TransformInvariantNMF:
         collective."""
         return cooccurrence(self.activation_correlogram(max_lag))
 
+    # -- the data around the places where an atom fires: triggered sums on a window larger than the atom ----------------
+    def _margin(self, margin) -> Tuple[int, ...]:
+        """``margin`` as one int >= 0 per shift axis; ``None``: ``(a + 1) // 2``, a window about twice the atom."""
+        k = len(self.atom_shape)
+        if margin is None:
+            return tuple((int(a) + 1) // 2 for a in self.atom_shape)
+        if _args.is_int(margin):
+            margins = (margin,) * k
+        elif isinstance(margin, (tuple, list)) and len(margin) == k:
+            margins = tuple(margin)
+        else:
+            raise ValueError(f'margin must be None, an int or {k} ints, not {margin!r}')
+        for x in margins:
+            _args.int_at_least('margin', x, 0)
+        return tuple(int(x) for x in margins)
+
+    def _triggered_refusals(self, what: str) -> None:
+        if self._H is None:
+            raise RuntimeError(f'{what}() needs a fitted model: call fit first')
+        if len(self.atom_shape) == 3:
+            raise NotImplementedError(f'{what}: 1 or 2 shift axes only')
+
+    def _triggered(self, source: str, margin: Tuple[int, ...], power: int = 1, per_sample: bool = False) -> np.ndarray:
+        """The triggered sums of the field ``source`` ('data', 'reconstruction', 'residual', each times the weights of a
+        weighted fit, or 'weights': the weights, ones without), float64, samples in the order of ``H``."""
+        backend = self._backend
+        if getattr(backend, 'supports_triggered', False):
+            Y = backend.triggered_field(self._V, self._W_dict, self._H, source)
+            try:
+                return np.asarray(backend.triggered_sums(self._H, Y, margin, power=power, per_sample=per_sample),
+                                  dtype=np.float64)
+            except NotImplementedError:   # (a window beyond the kernel's limit: nothing was written)
+                Y = backend.to_ndarray(Y)
+        else:
+            V, G = np.asarray(self._local_V(), dtype=np.float64), self._weights
+            if G is not None and len(G) != len(V):
+                n0 = int(getattr(backend, 'shard', (0, 0))[0])
+                G = G[n0:n0 + len(V)]
+            if source == 'weights':
+                Y = np.ones(V.shape) if G is None else np.where(G > 0, G, 0.)
+            else:
+                R = None if source == 'data' else np.asarray(backend.to_ndarray(backend.reconstruct(self._W_dict, self._H)),
+                                                             dtype=np.float64)
+                Y = V if source == 'data' else R if source == 'reconstruction' else V - R
+                if G is not None:   # (entries of weight 0 are not data: they add exactly 0 whatever V holds there)
+                    with np.errstate(invalid='ignore'):
+                        Y = np.where(G > 0, G * Y, 0.)
+        Hp = pad_activations_numpy(backend.to_ndarray(self._H), self.atom_shape, self._mode)
+        return triggered_sums_numpy(Hp, Y, self.atom_shape, margin, power, per_sample)
+
+    def activation_triggered_sums(self, margin: Union[None, int, Tuple[int, ...]] = None, source: str = 'residual',
+                                  per_sample: bool = False) -> np.ndarray:
+        """The data around the places where a plane fires: ``X[p, c, j] = sum_n sum_q Hp[n, p, q] S[n, c, q - (A - 1) - m
+        + j]`` for ``0 <= j_k < A_k + 2 m_k``, with ``Hp`` the padded activations every mode reconstructs from and ``S`` the
+        field ``source`` of the samples' shape; terms whose index falls outside the sample are absent.  float64
+        ``[P, C, *(A + 2 m)]``, or with ``per_sample=True`` ``[N, P, C, *(A + 2 m)]`` in the order of ``V``.  P counts the
+        effective planes (``atom * T + transform`` with transforms).
+
+        margin : ``None`` (``(a + 1) // 2`` per axis: a window about twice the atom), an int or one int >= 0 per shift axis
+        source : ``'data'`` (V), ``'reconstruction'`` (R) or ``'residual'`` (V - R); after a weighted fit each is
+                 multiplied by the weights
+
+        The entries ``[m, m + A)`` of the window are ``neg`` (data) and ``pos`` (reconstruction) of the W gradient of the
+        effective planes -- of the Frobenius objective only; under any other ``beta_loss`` the sums are a plain correlation
+        and no gradient.  The entries outside are what that gradient would be for taps the atom does not have.  Any
+        ``beta_loss``, weights, reconstruction mode and transforms; 1 or 2 shift axes.  On a backend with
+        ``triggered_sums`` one pass over the activations where they live, every sum in double; any other backend -- and a
+        window beyond that hook's limit -- goes through ``triggered_sums_numpy`` on the host.  Not collective: with a
+        process group each rank reports its own samples, and X adds over the ranks.  ``W``, ``H`` and ``V`` are not
+        touched."""
+        self._triggered_refusals('activation_triggered_sums')
+        m = self._margin(margin)
+        _args.one_of('source', source, _TRIGGERED_SOURCES)
+        _args.boolean('per_sample', per_sample)
+        X = self._triggered(source, m, 1, bool(per_sample))
+        return self._in_order_of_V(X) if per_sample else X
+
+    def activation_triggered_average(self, margin: Union[None, int, Tuple[int, ...]] = None,
+                                     source: str = 'data') -> np.ndarray:
+        """The weighted mean of the field's values where plane p fires -- the spike-triggered average of the dense model:
+        ``activation_triggered_sums(margin, source)`` divided by ``mass[p, c, j] = sum Hp G`` over the same terms (G the
+        weights of a weighted fit, else 1), float64 ``[P, C, *(A + 2 m)]``; NaN where ``mass == 0``.  Arguments and limits
+        as for ``activation_triggered_sums``."""
+        self._triggered_refusals('activation_triggered_average')
+        m = self._margin(margin)
+        _args.one_of('source', source, _TRIGGERED_SOURCES)
+        X, mass = self._triggered(source, m), self._triggered('weights', m)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return np.where(mass == 0, np.nan, X / mass)
+
+    def atom_tap_gains(self, margin: Union[None, int, Tuple[int, ...]] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """(gain, step), float64 ``[P, C, *(A + 2 m)]``: would a larger ``atom_shape`` pay, on which side, for which atom.
+        With ``E`` the triggered sums of ``G (V - R)`` and ``b = sum Hp^2 G`` over the same terms, the objective as a
+        function of a change t of ONE tap of ONE effective plane, everything else held, is ``-t E + t^2 b / 2``; a tap stays
+        >= 0, so ``step = max(E / b, -W_ext)`` (``W_ext`` the effective atoms zero-extended to the window; 0 where ``b`` is
+        0) and ``gain = step E - step^2 b / 2 >= 0`` is the exact drop of ``1/2 ||V - R||^2`` (weighted when weights are
+        bound) under that one change -- the ``a^2 / (2 b)`` of ``pursue_detections``.  Entries outside ``[m, m + A)`` are
+        taps the atom does not have.
+
+        What this is not: taps interact through the autocorrelogram of H, so the gains of several taps do not add; with
+        ``transforms`` the planes of an atom share their taps; and W is normalised after every step.  Sums of gains rank
+        atoms and sides of the window; they do not predict the objective of a refit.
+
+        The Frobenius objective only, with or without weights; 1 or 2 shift axes; not collective; ``W``, ``H`` and ``V`` are
+        not touched."""
+        self._atom_refusals()
+        m = self._margin(margin)
+        E, b = self._triggered('residual', m), self._triggered('weights', m, power=2)
+        W_ext = extend_atoms(self._backend.to_ndarray(self._W_dict), m)
+        return tap_gains_from_sums(E, b, W_ext)
+
+    def atom_window_gains(self, margin: Union[None, int, Tuple[int, ...]] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """(inside, outside), float64 ``[n_atoms]``: the gains of ``atom_tap_gains(margin)`` summed over an atom's planes,
+        its channels and the taps inside / outside ``[m, m + A)``.  An ``outside`` that is not small beside ``inside`` says
+        this atom wants a larger ``atom_shape``; the per-tap map says on which side.  A ranking, not a prediction."""
+        gain, _ = self.atom_tap_gains(margin)
+        return window_gains(gain, self._margin(margin), self.n_atoms)
+
     # -- how atoms overlap: a and the Gram matrix B of the atoms' contributions ------------------------------------------
     # With per-atom scale factors s (R(s) = sum s_m R_m) the objective is the exact quadratic
     #   E(s) = E(1) - a^T (s - 1) + 1/2 (s - 1)^T B (s - 1),        B[m, m'] = sum G R_m R_m'  (diag(B) = b of atom_terms)
@@ -1447,8 +1569,8 @@ class TransformInvariantNMF:
         self._iteration_acc = None    # (sized and typed for the W of ONE fit: a refit may change dtype or device)
         self._objective_buf = None    # (one value per local sample of ONE fit)
         self._weighted = weights is not None
-        # (the host copy, kept only for atom_terms / atom_gram on a backend without the hooks)
-        hooks = [getattr(self._backend, name, None) for name in ('atom_terms', 'atom_gram')]
+        # (the host copy, kept only for atom_terms / atom_gram / the triggered sums on a backend without the hooks)
+        hooks = [getattr(self._backend, name, None) for name in ('atom_terms', 'atom_gram', 'triggered_sums')]
         self._weights = weights if None in hooks else None
         kw = {} if weights is None else {'weights': weights}
         if self._transforms is not None:

@@ -32,6 +32,7 @@ EXPORTS = (
     'tnmf_hip_ctx_set_objective_tap', 'tnmf_hip_sample_objective', 'tnmf_hip_atom_terms',
     'tnmf_hip_atom_gram', 'tnmf_hip_atom_sources',
     'tnmf_hip_find_peaks', 'tnmf_hip_activation_correlogram',
+    'tnmf_hip_triggered_sums_plan', 'tnmf_hip_triggered_sums',
     'tnmf_hip_events_render', 'tnmf_hip_events_update', 'tnmf_hip_events_grad_W', 'tnmf_hip_events_gain',
     'tnmf_hip_events_norms', 'tnmf_hip_pursuit_score', 'tnmf_hip_pursuit_pick', 'tnmf_hip_events_landscape',
     'tnmf_hip_events_alternatives',
@@ -79,6 +80,8 @@ OP_UPDATE_H, OP_GRAD_W, OP_APPLY_W = 0, 1, 2
 
 E_GEOM = -2
 E_UNSUPPORTED = -5
+# the largest window A + 2 m of tnmf_hip_triggered_sums per number of shift axes: triggered.h, kTrigMaxWindow1 / 2
+TRIGGERED_MAX_WINDOW = {1: 4096, 2: 128}
 E_STRIDE = -6   # TNMF_E_STRIDE: the kernel family of this call wants C-contiguous H
 
 
@@ -167,6 +170,8 @@ def load() -> ctypes.CDLL:
     lib.tnmf_hip_atom_sources.argtypes = [vp, gp, ci, vp, ci, vp, ci, cd, vp, vp, vp, vp, vp, vp, vp]
     lib.tnmf_hip_find_peaks.argtypes = [vp, gp, vp, cd, pi, ci, vp, vp, sz, vp, vp]
     lib.tnmf_hip_activation_correlogram.argtypes = [vp, gp, vp, pi, ci, vp, vp]
+    lib.tnmf_hip_triggered_sums_plan.argtypes = [vp, gp, ci, pi, ci, ctypes.POINTER(sz)]
+    lib.tnmf_hip_triggered_sums.argtypes = [vp, gp, vp, vp, ci, pi, ci, ci, vp, sz, vp, vp]
     ll = ctypes.c_longlong
     lib.tnmf_hip_events_render.argtypes = [vp, gp, vp, vp, ll, vp, vp, ll, vp, vp]
     lib.tnmf_hip_events_update.argtypes = [vp, gp, ci, vp, vp, vp, ll, vp, vp, cd, cd, vp]

@@ -954,6 +954,63 @@ class HIP_Backend(Backend):
                        'tnmf_hip_activation_correlogram')
         return C.cpu().numpy()
 
+    # -- triggered sums --------------------------------------------------------------------------------------------------
+    # The data around the places where a plane fires, on a window larger than the atom (include/tnmf_hip.h, "triggered
+    # sums"): one pass over the padded H and a field of the samples' shape on the f64 matrix cores, and only the
+    # [P, F, window] sums cross to the host.  The work buffer is this backend's, not the context's.
+    supports_triggered = True
+    TRIGGERED_MAX_WINDOW = _lib.TRIGGERED_MAX_WINDOW
+
+    def triggered_field(self, V, W: torch.Tensor, H: torch.Tensor, source: str) -> torch.Tensor:
+        """The field ``[n, C, *D]`` of ``source``: 'data' (the resident samples), 'reconstruction', 'residual' (their
+        difference) -- each times the bound weights when there are any -- or 'weights' (the weights; ones without)."""
+        if source == 'weights':
+            return torch.ones_like(self._V_dev) if self._G_dev is None else self._G_dev
+        if source == 'data':
+            Y = self._V_dev
+        elif source == 'reconstruction':
+            Y = self.reconstruct(W, H)
+        elif source == 'residual':
+            Y = self._V_dev - self.reconstruct(W, H)
+        else:
+            raise ValueError(f'unknown source {source!r}')
+        return Y if self._G_dev is None else Y * self._G_dev
+
+    def triggered_sums(self, H: torch.Tensor, Y: torch.Tensor, margin: Sequence[int], power: int = 1,
+                       per_sample: bool = False) -> np.ndarray:
+        """``X[p, f, j] = sum_n sum_q Hp[n, p, q]^power Y[n, f, q - (A - 1) - m + j]`` with Hp the padded activations of
+        ``H`` and ``Y`` a field ``[n, F, *D]`` on the device, float64 ``[P, F, *(A + 2 m)]`` on the host, or per sample
+        ``[n, P, F, *(A + 2 m)]`` -> tnmf_hip_triggered_sums.  NotImplementedError for volumes and for a window beyond the
+        library's limit."""
+        k = len(self.atom_shape)
+        if k == 3:
+            raise NotImplementedError('triggered sums: 1 or 2 shift axes only')
+        assert H.is_cuda and H.dtype == self._torch_dtype and len(margin) == k
+        assert Y.is_cuda and Y.dtype == self._torch_dtype and tuple(Y.shape[2:]) == tuple(self._sample_shape)
+        assert Y.shape[0] == H.shape[0]
+        n, P, F = int(H.shape[0]), int(H.shape[1]), int(Y.shape[1])
+        m = (ctypes.c_int * 3)(*[min(int(x), 2 ** 30) for x in margin])
+        window = tuple(int(a) + 2 * int(x) for a, x in zip(self.atom_shape, margin))
+        # the plan first: it refuses exactly what the call refuses, so nothing is allocated for a window the library does
+        # not take (the bytes do not depend on the row stride)
+        need = ctypes.c_size_t(0)
+        rc = self._lib.tnmf_hip_triggered_sums_plan(self._ctx, ctypes.byref(self._geom(n, P)), F, m, int(bool(per_sample)),
+                                                    ctypes.byref(need))
+        if rc == _lib.E_UNSUPPORTED:
+            raise NotImplementedError(f'triggered sums: a window of {window}, or the number of its sums, is beyond the library\'s limit')
+        _lib.check(rc, 'tnmf_hip_triggered_sums_plan')
+        X = torch.empty(((n,) if per_sample else ()) + (P, F) + window, dtype=torch.float64, device=self._device)
+        if X.numel() == 0:   # (per sample, and no sample)
+            return X.cpu().numpy()
+        Y = Y.contiguous()
+        Hp = self._pad(H)
+        work = torch.empty(max(1, need.value), dtype=torch.uint8, device=self._device)
+        with self._timed('triggered_sums'):
+            self._call_H(Hp, False, lambda Hc, ld: (self._lib.tnmf_hip_triggered_sums(
+                self._ctx, ctypes.byref(self._geom(n, P, ld)), _ptr(Hc), _ptr(Y), F, m, int(power), int(bool(per_sample)),
+                _ptr(work), need.value, _ptr(X), self._stream()), 'tnmf_hip_triggered_sums'))
+        return X.cpu().numpy()
+
     # -- events: the detections rendered and refitted --------------------------------------------------------------------
     # The H side on a list of events (include/tnmf_hip.h, "events"): no buffer of H's size exists on this path.  The
     # support is fixed over a refit, so the sorted image list and the cell offsets are built once (event_list); only the

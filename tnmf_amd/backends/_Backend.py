@@ -52,6 +52,12 @@ flat C-order indices (int64, host) in H's shape [n, P, *S] and the values of the
 host): the correlogram of its native H (include/tnmf_hip.h, "activation correlogram"); it may raise ``NotImplementedError``,
 and then, as without the hook, ``activation_correlogram()`` runs ``activation_correlogram_numpy``
 (tnmf_amd/correlogram_host.py) on the host.
+A backend with ``supports_triggered = True`` offers ``triggered_field(V, W, H, source) -> Y`` (its native array ``[n, C, *D]``:
+the field 'data', 'reconstruction' or 'residual', times the bound weights when there are any, or 'weights') and
+``triggered_sums(H, Y, margin, power=1, per_sample=False) -> X`` (float64 ``[P, F, *(A + 2 m)]`` or ``[n, P, F, *(A + 2 m)]``,
+host): the triggered sums of its native H and that field (include/tnmf_hip.h, "triggered sums"); ``triggered_sums`` may
+raise ``NotImplementedError``, and then, as without the flag, the front end runs ``triggered_sums_numpy``
+(tnmf_amd/triggered_host.py) on the host.
 A backend that declares ``supports_events`` works on lists of events (local sample, plane of the effective dictionary,
 shift in its H, strength; include/tnmf_hip.h, "events"): ``render_events(W, sample, plane, shift, strength) -> R``
 (backend-native ``[n_local, C, *D]``) and ``refit_events(V, W, sample, plane, shift, strength, n_iterations, sparsity=0.,

@@ -21,6 +21,7 @@
 #include "patches.h"
 #include "peaks.h"
 #include "split.h"
+#include "triggered.h"
 #include "volume.h"
 
 namespace {
@@ -1472,6 +1473,52 @@ int tnmf_hip_activation_correlogram(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom
     // work buffer: the partial sums per (segment, strip, pair of plane blocks, lag)
     CHECK(ensure_buffer(&ctx->ob, &ctx->ob_bytes, correlogram_partial_bytes(p), false));
     return launch_correlogram(p, geom->dtype, H, static_cast<double *>(ctx->ob), C_out, s);
+}
+
+// the arguments tnmf_hip_triggered_sums and its _plan share, checked, and the plan of the call
+static int triggered_args(const tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int n_fields, const int *margin, int power,
+                          int per_sample, TrigPlan *p) {
+    if (!ctx || !geom || !margin) return TNMF_E_NULL;
+    if (geom->dtype != 0 && geom->dtype != 1) return TNMF_E_DTYPE;
+    if (geom->ndim == 3) return TNMF_E_UNSUPPORTED;
+    if ((geom->ndim != 1 && geom->ndim != 2) || geom->N < 0 || geom->M <= 0) return TNMF_E_GEOM;
+    for (int i = 0; i < geom->ndim; ++i)
+        if (geom->D[i] <= 0 || geom->A[i] <= 0 || margin[i] < 0) return TNMF_E_GEOM;
+    if (n_fields < 1 || (power != 1 && power != 2)) return TNMF_E_GEOM;
+    const int last = geom->ndim - 1;
+    if ((long long)geom->D[last] + geom->A[last] - 1 > 0x7fffffffLL || (long long)geom->D[0] + geom->A[0] - 1 > 0x7fffffffLL)
+        return TNMF_E_UNSUPPORTED;
+    const int Sx = geom->D[last] + geom->A[last] - 1;
+    if (geom->h_row_stride > 0 && geom->h_row_stride < Sx) return TNMF_E_GEOM;
+    return triggered_plan(geom->N, geom->M, n_fields, geom->D, geom->A, geom->h_row_stride > 0 ? geom->h_row_stride : Sx,
+                          geom->ndim, margin, power, per_sample != 0, geom->dtype, p);
+}
+
+int tnmf_hip_triggered_sums_plan(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int n_fields, const int *margin,
+                                 int per_sample, size_t *work_bytes) {
+    TrigPlan p;
+    CHECK(triggered_args(ctx, geom, n_fields, margin, 1, per_sample, &p));
+    if (!work_bytes) return TNMF_E_NULL;
+    *work_bytes = geom->N == 0 ? 0 : triggered_partial_bytes(p);
+    return TNMF_OK;
+}
+
+int tnmf_hip_triggered_sums(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *H, const void *Y, int n_fields,
+                            const int *margin, int power, int per_sample, void *work, size_t work_bytes,
+                            double *X_out, void *stream) {
+    TrigPlan p;
+    CHECK(triggered_args(ctx, geom, n_fields, margin, power, per_sample, &p));
+    if (!X_out || (work_bytes > 0 && !work) || (geom->N > 0 && (!H || !Y))) return TNMF_E_NULL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    if (geom->N == 0) {   // no sample: nothing per sample, and sums of nothing
+        if (!per_sample)
+            TNMF_HIP_TRY(hipMemsetAsync(X_out, 0, (size_t)p.P * p.F * p.Wy * p.Wx * sizeof(double), s));
+        return TNMF_OK;
+    }
+    // the partial sums per (segment, strip, block of planes, cell) live in the caller's work buffer
+    if (work_bytes < triggered_partial_bytes(p)) return TNMF_E_WORKSPACE;
+    return launch_triggered(p, geom->dtype, H, Y, static_cast<double *>(work), X_out, s);
 }
 
 // the geometry of the events entry points, checked: ndim 1 or 2 (3: TNMF_E_UNSUPPORTED), every size positive
