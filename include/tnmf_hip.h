@@ -428,6 +428,49 @@ int tnmf_hip_atom_terms(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int group,
 int tnmf_hip_atom_gram(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int group, const void *V, const void *G_or_null,
                        const void *R_or_null, const void *W, const void *H, double *a, double *B, void *stream);
 
+/* ---- atom terms, beta: what each atom explains under a beta-divergence (ABI 8, additive: the version stays 8) -----------
+ * With R_m and r = R_m[n] as under "atom terms", x = max(R, 0) + eps, x_m = max(R - r, 0) + eps and D_beta the element
+ * divergence of tnmf_hip_energy_beta:
+ *   gain[n, m]  = sum G (D_beta(V | x_m) - D_beta(V | x))       what the sample's objective rises by without atom m: exact
+ *   a[n, m]     = sum G r (V x^(beta-2) - x^(beta-1))           = <R_m, Q - P> of tnmf_hip_beta_fields: -dE/ds_m at s = 1
+ *   b[n, m]     = sum G r^2 c,   c = (beta-1) x^(beta-2) + (2-beta) V x^(beta-3)                        d^2E/ds_m^2 at s = 1
+ *   B[n, m, m'] = sum G c r_m r_m'                              diag(B) = b
+ * (G = 1 without weights).  E(s) ~ E(1) - a^T (s - 1) + 1/2 (s - 1)^T B (s - 1) in per-atom scale factors is the local
+ * second-order model, exact only at beta = 2.  c is negative where V > x (beta-1) / (beta-2) for beta > 2 and where
+ * V < x (1-beta) / (2-beta) for beta < 1: the weights G c are signed, b and diag(B) can be negative, and only G <= 0
+ * selects an exact zero (whatever V holds there).
+ * The walk over H, r in the element type, the partial sums and their order are those of tnmf_hip_atom_terms and
+ * tnmf_hip_atom_gram: no floating-point atomics, the same bits from run to run.  The pixel factors G (V x^(beta-2) -
+ * x^(beta-1)) and G c are formed in double from the element-type V, R and G (no pow for beta 0 and 1) and rounded once to
+ * the element type; r times them and, for B, (G c) r_m times r_m' are accumulated in double.  The gain term of a pixel is
+ * evaluated in double, R - r in double, in forms in which nothing cancels where r is small beside R --
+ *   beta 1: V log(x / x_m) + (x_m - x)  (x_m - x where V == 0);    beta 0: V (1 / x_m - 1 / x) + log(x_m / x);
+ *   else:   [(beta-1) (x_m^beta - x^beta) - beta V (x_m^(beta-1) - x^(beta-1))] / (beta (beta-1)),
+ * the logarithm as log1p((x - x_m) / x_m), the differences of powers as x^p expm1(p log(x_m / x)) -- and a pixel with
+ * r == 0 or G <= 0 adds an exact 0 without evaluating anything.  Where an atom alone explains a pixel with V > 0 (x_m
+ * = eps) the term is of the size V log(R / eps): the objective's own.
+ * beta == 2 runs the kernels of tnmf_hip_atom_terms / tnmf_hip_atom_gram (d = V - R: no clamp, no eps): a, b and B are
+ * theirs bit for bit, and gain = a + b / 2 in double. */
+
+/* a, b, gain of every atom: abg[(n*(M/group) + m)*3 + {0,1,2}] (double, device).  Operands, `group`, G_or_null, R_or_null
+ * (NULL: reconstructed into the ctx scratch by the ctx's kernel family), the row stride of H and the work buffer as for
+ * tnmf_hip_atom_terms (three partial sums per (sample, tile, atom) instead of two; at beta == 2 the two of
+ * tnmf_hip_atom_terms and its (a, b) behind the taps).  eps: the model's, >= 0.  Every element of abg is written.
+ * Asynchronous on the stream.
+ * TNMF_E_GEOM: group < 1, M % group != 0, a beta that is not finite, or eps < 0 (or NaN).  TNMF_E_UNSUPPORTED: as
+ * tnmf_hip_atom_terms.  A refused call writes nothing. */
+int tnmf_hip_atom_terms_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int group, double beta, double eps, const void *V,
+                             const void *G_or_null, const void *R_or_null, const void *W, const void *H, double *abg,
+                             void *stream);
+
+/* a[n*(M/group) + m] and B[(n*(M/group) + m)*(M/group) + m'] (double, device) as defined above, B symmetric and written in
+ * full.  Everything else as for tnmf_hip_atom_gram, whose plan, partial sums and finalize it shares.
+ * TNMF_E_GEOM: group < 1, M % group != 0, a beta that is not finite, or eps < 0 (or NaN).  TNMF_E_UNSUPPORTED: as
+ * tnmf_hip_atom_gram.  A refused call writes nothing. */
+int tnmf_hip_atom_gram_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int group, double beta, double eps, const void *V,
+                            const void *G_or_null, const void *R_or_null, const void *W, const void *H, double *a, double *B,
+                            void *stream);
+
 /* ---- sources: per-source signals by soft masks (ABI 8, additive: the version stays 8) -------------------------------------
  * A source is a set of planes of H and W (an atom in all its orientations, or several atoms).  With r_g[c, x] the sum of
  * what the planes of source g add to R -- r of "atom terms", in the element type -- and total = sum r over EVERY plane, the

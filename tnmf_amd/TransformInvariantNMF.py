@@ -30,8 +30,8 @@ import numpy as np
 
 from . import _args
 from . import transforms as _transforms
-from .atoms_host import (atom_gram_numpy, atom_terms_numpy, gram_drop, gram_elimination, gram_scales,
-                         gram_set_gain, pad_activations_numpy)
+from .atoms_host import (atom_divergence_gram_numpy, atom_divergence_terms_numpy, atom_gram_numpy, atom_terms_numpy,
+                         gram_drop, gram_elimination, gram_scales, gram_set_gain, pad_activations_numpy)
 from .backends._Backend import Backend, sliceNone
 from .correlogram_host import activation_correlogram_numpy, cooccurrence
 # (the host side of the events; the names stay importable from this module)
@@ -1344,6 +1344,75 @@ class TransformInvariantNMF:
         B = self._atom_gram()[1]
         return B if per_sample else B.sum(axis=0)
 
+    # -- the same questions under the model's own objective, any beta_loss ------------------------------------------------
+    # With x = max(R, 0) + eps, x_m = max(R - R_m, 0) + eps and D the element divergence of the objective:
+    #   gain = sum G (D(V | x_m) - D(V | x))                                  exact: the objective without atom m, minus the objective
+    #   a = sum G R_m (V x^(beta-2) - x^(beta-1)),   B = sum G c R_m R_m',    c = (beta-1) x^(beta-2) + (2-beta) V x^(beta-3)
+    # E(s) ~ E(1) - a^T (s - 1) + 1/2 (s - 1)^T B (s - 1) is the local second-order model in per-atom scale factors, exact
+    # only at beta_loss 2, where all of this is atom_terms / atom_gains / atom_gram.
+    def _atom_divergence(self, gram: bool):
+        """(a, b, gain) or (a, B), float64, samples in the order of ``H``: the backend's hook, else the host fallback."""
+        if self._H is None:
+            raise RuntimeError('the atom gains of a model need a fitted model: call fit first')
+        if len(self.atom_shape) == 3:
+            raise NotImplementedError('atom gains: 1 or 2 shift axes only')
+        if self._beta == 2.:
+            if gram:
+                return self._atom_gram()
+            a, b = self.atom_terms()
+            return a, b, a + 0.5 * b
+        name = 'atom_divergence_gram' if gram else 'atom_divergence_terms'
+        hook = getattr(self._backend, name, None)
+        if hook is not None:
+            out = hook(self._V, self._W_dict, self._H, self.n_transforms, self._beta, self.eps)
+        else:
+            G = self._weights
+            if G is not None and len(G) != int(self._H.shape[0]):
+                n0 = int(getattr(self._backend, 'shard', (0, 0))[0])
+                G = G[n0:n0 + int(self._H.shape[0])]
+            fallback = atom_divergence_gram_numpy if gram else atom_divergence_terms_numpy
+            out = fallback(self._backend.to_ndarray(self._W_dict), self._backend.to_ndarray(self._H), self._mode,
+                           self._local_V(), G, self.n_transforms, self._beta, self.eps)
+        out = tuple(np.asarray(o, dtype=np.float64) for o in out)
+        if self._shuffle_idx is not None:
+            order = np.argsort(self._shuffle_idx)
+            out = tuple(o[order] for o in out)
+        return out
+
+    def atom_divergence_terms(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(a, b), float64 ``[N, n_atoms]``, under the model's own objective (any ``beta_loss``, with or without weights):
+        with ``R_m`` the contribution of atom m in all its orientations and ``x = max(R, 0) + eps``,
+        ``a = sum G R_m (V x^(beta-2) - x^(beta-1))`` is minus the slope and ``b = sum G R_m^2 c``,
+        ``c = (beta-1) x^(beta-2) + (2-beta) V x^(beta-3)``, the curvature of sample n's objective in a scale factor on atom
+        m, at 1.  A local model, not an identity: ``1 + a / b`` is one Newton step towards the best rescaling of the atom,
+        and ``b`` can be negative for ``beta_loss`` outside [1, 2].  What IS exact is ``atom_divergence_gains``.  Samples in
+        the order of ``H``; not collective; one pass over the activations on a backend with the hook, the host otherwise.
+        At ``beta_loss`` 2 this is ``atom_terms``.  ``W``, ``H`` and ``V`` are not touched."""
+        return self._atom_divergence(False)[:2]
+
+    def atom_divergence_gains(self, per_sample: bool = False) -> np.ndarray:
+        """What each atom explains under the model's own objective: ``sample_objective()`` of the model without atom m (in
+        all its orientations; its planes of ``H`` at 0) minus ``sample_objective()`` of the model -- exact, for any
+        ``beta_loss``, with or without weights, in one pass over the activations.  ``[n_atoms]`` float64, summed over the
+        samples, or with ``per_sample=True`` ``[N, n_atoms]`` in the order of ``H``.  Not collective.  Where an atom alone
+        explains a pixel with ``V > 0`` the model without it falls to ``eps`` there and the gain carries a term of the size
+        ``V log(R / eps)`` (Kullback-Leibler; ``V / eps`` for Itakura-Saito): that is the objective's own, not an artefact.
+        At ``beta_loss`` 2 this is ``atom_gains``."""
+        _args.boolean('per_sample', per_sample)
+        gain = self._atom_divergence(False)[2]
+        return gain if per_sample else gain.sum(axis=0)
+
+    def atom_divergence_gram(self, per_sample: bool = False) -> np.ndarray:
+        """``B[m, m'] = sum G c R_m R_m'`` with the curvature weights ``c`` of ``atom_divergence_terms``: the Hessian of the
+        objective in per-atom scale factors at 1, float64 ``[n_atoms, n_atoms]`` summed over the samples, or with
+        ``per_sample=True`` ``[N, n_atoms, n_atoms]`` in the order of ``H``.  Symmetric; its diagonal is ``b``.  With ``a``,
+        ``E(s) ~ E(1) - a^T (s - 1) + 1/2 (s - 1)^T B (s - 1)`` is a local model, exact only at ``beta_loss`` 2 (where this is
+        ``atom_gram``); for ``beta_loss`` outside [1, 2] the weights are signed and ``B`` need not be positive
+        semi-definite.  Not collective; ``W``, ``H``, ``V`` are not touched."""
+        _args.boolean('per_sample', per_sample)
+        B = self._atom_divergence(True)[1]
+        return B if per_sample else B.sum(axis=0)
+
     def atom_overlaps(self) -> np.ndarray:
         """``B[m, m'] / sqrt(B[m, m] B[m', m'])``, float64 ``[n_atoms, n_atoms]``: the cosine between two atoms'
         contributions to R, 1 for duplicates -- duplicates up to a shift included, since H absorbs the shift -- and 0 where
@@ -1569,8 +1638,10 @@ class TransformInvariantNMF:
         self._iteration_acc = None    # (sized and typed for the W of ONE fit: a refit may change dtype or device)
         self._objective_buf = None    # (one value per local sample of ONE fit)
         self._weighted = weights is not None
-        # (the host copy, kept only for atom_terms / atom_gram / the triggered sums on a backend without the hooks)
-        hooks = [getattr(self._backend, name, None) for name in ('atom_terms', 'atom_gram', 'triggered_sums')]
+        # (the host copy, kept only for atom_terms / atom_gram / their divergence forms / the triggered sums on a backend
+        # without the hooks)
+        hooks = [getattr(self._backend, name, None) for name in ('atom_terms', 'atom_gram', 'atom_divergence_terms',
+                                                                 'atom_divergence_gram', 'triggered_sums')]
         self._weights = weights if None in hooks else None
         kw = {} if weights is None else {'weights': weights}
         if self._transforms is not None:

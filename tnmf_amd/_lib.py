@@ -30,7 +30,7 @@ EXPORTS = (
     'tnmf_hip_atom_ops_create', 'tnmf_hip_atom_ops_destroy', 'tnmf_hip_ops_expand_W', 'tnmf_hip_ops_fold_grad_W',
     'tnmf_hip_ops_apply_W',
     'tnmf_hip_ctx_set_objective_tap', 'tnmf_hip_sample_objective', 'tnmf_hip_atom_terms',
-    'tnmf_hip_atom_gram', 'tnmf_hip_atom_sources',
+    'tnmf_hip_atom_gram', 'tnmf_hip_atom_sources', 'tnmf_hip_atom_terms_beta', 'tnmf_hip_atom_gram_beta',
     'tnmf_hip_find_peaks', 'tnmf_hip_activation_correlogram',
     'tnmf_hip_triggered_sums_plan', 'tnmf_hip_triggered_sums',
     'tnmf_hip_events_render', 'tnmf_hip_events_update', 'tnmf_hip_events_grad_W', 'tnmf_hip_events_gain',
@@ -167,6 +167,8 @@ def load() -> ctypes.CDLL:
     lib.tnmf_hip_sample_objective.argtypes = [vp, gp, cd, cd, vp, vp, vp, vp, vp, vp]
     lib.tnmf_hip_atom_terms.argtypes = [vp, gp, ci, vp, vp, vp, vp, vp, vp, vp]
     lib.tnmf_hip_atom_gram.argtypes = [vp, gp, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.tnmf_hip_atom_terms_beta.argtypes = [vp, gp, ci, cd, cd, vp, vp, vp, vp, vp, vp, vp]
+    lib.tnmf_hip_atom_gram_beta.argtypes = [vp, gp, ci, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.tnmf_hip_atom_sources.argtypes = [vp, gp, ci, vp, ci, vp, ci, cd, vp, vp, vp, vp, vp, vp, vp]
     lib.tnmf_hip_find_peaks.argtypes = [vp, gp, vp, cd, pi, ci, vp, vp, sz, vp, vp]
     lib.tnmf_hip_activation_correlogram.argtypes = [vp, gp, vp, pi, ci, vp, vp]

@@ -74,6 +74,70 @@ def atom_gram_numpy(W: np.ndarray, H: np.ndarray, mode: str, V: np.ndarray, G: O
     return np.sum(parts * gd[:, None], axis=tuple(range(2, parts.ndim))), B
 
 
+def _divergence_factors(parts, V, g, beta, eps):
+    """(R, x, V, G (V x^(beta-2) - x^(beta-1)), G c) of include/tnmf_hip.h, "atom terms, beta": V and the two factors
+    with exact zeros where the weight is <= 0 (``g``: the weights clipped at 0), whatever V holds there."""
+    R = parts.sum(axis=1)
+    x = np.maximum(R, 0.) + eps
+    with np.errstate(invalid='ignore', over='ignore'):
+        v = np.where(g > 0, np.asarray(V, dtype=np.float64), 0.)
+        gd = g * ((v - x) * x ** (beta - 2.))
+        gc = g * (((beta - 1.) * x + (2. - beta) * v) * x ** (beta - 3.))
+    return R, x, v, np.where(g > 0, gd, 0.), np.where(g > 0, gc, 0.)
+
+
+def atom_divergence_terms_numpy(W: np.ndarray, H: np.ndarray, mode: str, V: np.ndarray, G: Optional[np.ndarray] = None,
+                                group: int = 1, beta: float = 1., eps: float = 1e-9
+                                ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(a, b, gain), float64 ``[N, P / group]``, under the beta-divergence (include/tnmf_hip.h, "atom terms, beta"): with
+    ``r = R_m`` of ``atom_terms_numpy``, ``x = max(R, 0) + eps`` and ``x_m = max(R - r, 0) + eps``,
+    ``a = sum G r (V x^(beta-2) - x^(beta-1))``, ``b = sum G r^2 c`` with ``c = (beta-1) x^(beta-2) + (2-beta) V x^(beta-3)``
+    and ``gain = sum G (D_beta(V | x_m) - D_beta(V | x))``, the last in the forms of the header in which nothing cancels.
+    ``beta == 2``: ``atom_terms_numpy`` and ``a + b / 2``."""
+    if beta == 2:
+        a, b = atom_terms_numpy(W, H, mode, V, G, group)
+        return a, b, a + b / 2
+    parts, _, g = _parts_and_residual(W, H, mode, V, G, group)
+    R, x, v, gd, gc = _divergence_factors(parts, V, g, float(beta), float(eps))
+    axes = tuple(range(2, parts.ndim))
+    a = np.sum(parts * gd[:, None], axis=axes)
+    b = np.sum(gc[:, None] * parts * parts, axis=axes)
+    c0, rm = np.maximum(R, 0.)[:, None], R[:, None] - parts
+    # x - x_m, from R_m itself where neither clamp acts (the rounding of R - R_m is of the size of R, not of R_m)
+    dx = np.where(rm > 0, np.where(R[:, None] > 0, parts, -rm), c0)
+    xm, x, v = np.maximum(rm, 0.) + eps, x[:, None], v[:, None]
+    with np.errstate(invalid='ignore', over='ignore', divide='ignore'):
+        l1p = np.log1p(dx / xm)   # log(x / x_m)
+        if beta == 1:
+            term = np.where(v > 0, v * l1p, 0.) - dx
+        elif beta == 0:
+            term = v * (dx / (x * xm)) - l1p
+        else:
+            p1 = x ** (beta - 1.)
+            term = ((beta - 1.) * (p1 * x) * np.expm1(-beta * l1p) - beta * v * p1 * np.expm1((1. - beta) * l1p)) \
+                / (beta * (beta - 1.))
+        term = np.where((g[:, None] > 0) & (parts != 0), g[:, None] * term, 0.)
+    return a, b, np.sum(term, axis=axes)
+
+
+def atom_divergence_gram_numpy(W: np.ndarray, H: np.ndarray, mode: str, V: np.ndarray, G: Optional[np.ndarray] = None,
+                               group: int = 1, beta: float = 1., eps: float = 1e-9) -> Tuple[np.ndarray, np.ndarray]:
+    """(a, B), float64 ``[N, Mo]`` and ``[N, Mo, Mo]``: ``a`` of ``atom_divergence_terms_numpy`` and
+    ``B[n, m, m'] = sum G c R_m R_m'``, symmetric, whose diagonal is its ``b``; the weights ``G c`` are signed.
+    ``beta == 2``: ``atom_gram_numpy``."""
+    if beta == 2:
+        return atom_gram_numpy(W, H, mode, V, G, group)
+    parts, _, g = _parts_and_residual(W, H, mode, V, G, group)
+    _, _, _, gd, gc = _divergence_factors(parts, V, g, float(beta), float(eps))
+    N, Mo = parts.shape[:2]
+    flat = parts.reshape(N, Mo, -1)
+    B = np.einsum('nmx,nkx->nmk', flat * gc.reshape(N, 1, -1), flat)
+    B = 0.5 * (B + B.transpose(0, 2, 1))
+    axes = tuple(range(2, parts.ndim))
+    B[:, np.arange(Mo), np.arange(Mo)] = np.sum(gc[:, None] * parts * parts, axis=axes)
+    return np.sum(parts * gd[:, None], axis=axes), B
+
+
 # -- the algebra on (a, B): E(s) = E(1) - a^T (s - 1) + 1/2 (s - 1)^T B (s - 1) for per-atom scale factors s ------------------
 def gram_drop(a: np.ndarray, B: np.ndarray, s: np.ndarray) -> float:
     """E(1) - E(s): what the objective falls by under the scale factors s."""

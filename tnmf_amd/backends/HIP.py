@@ -833,6 +833,51 @@ class HIP_Backend(Backend):
             'tnmf_hip_atom_gram'))
         return a.cpu().numpy(), B.cpu().numpy()
 
+    def atom_divergence_terms(self, V, W: torch.Tensor, H: torch.Tensor, group: int = 1, beta: float = 2.,
+                              eps: float = 1e-9) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(a, b, gain), float64 ``[n_local_samples, n_planes / group]`` on the host, under the beta-divergence with the
+        bound weights G (include/tnmf_hip.h, "atom terms, beta") -> tnmf_hip_atom_terms_beta: the pass of ``atom_terms``
+        with the slope, the curvature and the exact leave-one-out gain of every (sample, atom); ``beta == 2`` gives the
+        bits of ``atom_terms`` and ``a + b / 2``."""
+        if len(self.atom_shape) == 3:
+            raise NotImplementedError('atom gains: 1 or 2 shift axes only')
+        self._check_beta(beta)
+        self._check_W(W)
+        self._foreign_H()
+        self._check_H(H, W.shape[0])
+        assert H.shape[0] == self.n_local_samples
+        H = self._pad(H)
+        abg = torch.empty((H.shape[0], W.shape[0] // max(int(group), 1), 3), dtype=torch.float64, device=self._device)
+        self._call_H(H, False, lambda Hc, ld: (self._lib.tnmf_hip_atom_terms_beta(
+            self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)), int(group), float(beta), float(eps),
+            _ptr(self._V_dev), None if self._G_dev is None else _ptr(self._G_dev), None, _ptr(W), _ptr(Hc), _ptr(abg),
+            self._stream()), 'tnmf_hip_atom_terms_beta'))
+        out = abg.cpu().numpy()
+        return tuple(np.ascontiguousarray(out[..., k]) for k in range(3))
+
+    def atom_divergence_gram(self, V, W: torch.Tensor, H: torch.Tensor, group: int = 1, beta: float = 2.,
+                             eps: float = 1e-9) -> Tuple[np.ndarray, np.ndarray]:
+        """(a, B), float64 ``[n_local_samples, Mo]`` and ``[n_local_samples, Mo, Mo]`` on the host: ``a`` of
+        ``atom_divergence_terms`` and ``B[n, m, m'] = sum G c R_m R_m'`` under the signed curvature weights of the
+        beta-divergence (include/tnmf_hip.h, "atom terms, beta") -> tnmf_hip_atom_gram_beta; ``beta == 2`` gives the bits
+        of ``atom_gram``."""
+        if len(self.atom_shape) == 3:
+            raise NotImplementedError('atom gains: 1 or 2 shift axes only')
+        self._check_beta(beta)
+        self._check_W(W)
+        self._foreign_H()
+        self._check_H(H, W.shape[0])
+        assert H.shape[0] == self.n_local_samples
+        H = self._pad(H)
+        Mo = W.shape[0] // max(int(group), 1)
+        a = torch.empty((H.shape[0], Mo), dtype=torch.float64, device=self._device)
+        B = torch.empty((H.shape[0], Mo, Mo), dtype=torch.float64, device=self._device)
+        self._call_H(H, False, lambda Hc, ld: (self._lib.tnmf_hip_atom_gram_beta(
+            self._ctx, ctypes.byref(self._geom(Hc.shape[0], W.shape[0], ld)), int(group), float(beta), float(eps),
+            _ptr(self._V_dev), None if self._G_dev is None else _ptr(self._G_dev), None, _ptr(W), _ptr(Hc), _ptr(a),
+            _ptr(B), self._stream()), 'tnmf_hip_atom_gram_beta'))
+        return a.cpu().numpy(), B.cpu().numpy()
+
     # -- sources ----------------------------------------------------------------------------------------------------------
     # The per-source signals of the resident samples (include/tnmf_hip.h, "sources"): one pass over H on the walk of the
     # atom terms, the planes in the order the sources list them; the result stays on the device until the caller converts it.

@@ -39,6 +39,9 @@ weights when they are bound (include/tnmf_hip.h, "atom terms"); without it ``ato
 host): ``a`` as above and ``B[n, m, m'] = sum G R_m R_m'``, symmetric, in the order of H's atoms (include/tnmf_hip.h, "atom
 Gram"); without it ``atom_gram`` and what builds on it (``atom_overlaps``, ``atom_set_gain``, ``atom_scales``,
 ``rescale_atoms``, ``atom_elimination``) run ``atom_gram_numpy`` (tnmf_amd/atoms_host.py) on the host.
+``atom_divergence_terms(V, W, H, group, beta, eps) -> (a, b, gain)`` and ``atom_divergence_gram(V, W, H, group, beta, eps)
+-> (a, B)``: the same shapes under the beta-divergence (include/tnmf_hip.h, "atom terms, beta"); without them the front
+end's ``atom_divergence_*`` run ``atom_divergence_terms_numpy`` / ``atom_divergence_gram_numpy`` on the host.
 A backend that declares ``supports_sources`` offers ``source_parts(V, W, H, plane_order, source_start, output) -> out``
 (backend-native ``[n_local, S, C, *D]``: source g is the planes ``plane_order[source_start[g]:source_start[g + 1]]``, the
 planes in no source count in the total only; ``output`` one of 'contribution', 'mask', 'masked', with the ``eps`` keyword)

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "atom_beta.h"
 #include "atom_gram.h"
 #include "correlogram.h"
 #include "sources.h"
@@ -552,6 +553,27 @@ int vol_api_pad_fold(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, boo
 }
 
 }  // namespace
+
+// ---- the context's side of the atom entries that live beside their kernels (atom_beta.h)
+int atom_entry_geo(const tnmf_hip_geom *geom, Geo *g) {
+    if (!geom) return TNMF_E_NULL;
+    if (is_vol(geom)) return TNMF_E_UNSUPPORTED;
+    return to_geo(geom, g);
+}
+
+int atom_entry_buffers(tnmf_hip_ctx *ctx, const Geo &g, int dtype, size_t work_bytes, const void *W, const void *H,
+                       const void **R, void **work, hipStream_t s) {
+    CHECK(ensure_buffer(&ctx->ob, &ctx->ob_bytes, work_bytes, false));
+    *work = ctx->ob;
+    if (!*R) {
+        const Scratch sc = plan_scratch(ctx, g, dtype);
+        CHECK(ensure_scratch(ctx, sc.total));
+        void *Rs = ws_at(ctx, sc.r_off);
+        CHECK(do_reconstruct(ctx, g, dtype, W, H, Rs, s));
+        *R = Rs;
+    }
+    return TNMF_OK;
+}
 
 extern "C" {
 

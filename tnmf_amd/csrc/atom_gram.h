@@ -33,3 +33,6 @@ int atom_gram_check(const Geo &g, int dtype, int group);
 int launch_atom_gram(const tnmf_hip_ctx *ctx, const Geo &g, int dtype, int group, const void *V, const void *G,
                      const void *R, const void *W, const void *H, double *partials, void *taps, double *a, double *B,
                      hipStream_t s);
+// a and B from the partial sums that a kernel on the plan p has written (what launch_atom_gram does last; atom_gram_beta.hip)
+int launch_atom_gram_finalize(const Geo &g, const GramPlan &p, int group, const double *partials, double *a, double *B,
+                              hipStream_t s);

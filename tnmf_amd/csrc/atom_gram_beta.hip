@@ -1,30 +1,20 @@
-// atom_gram.hip -- how atoms overlap, in one pass over the activations (tnmf_hip_atom_gram).
+// atom_gram_beta.hip -- how atoms overlap under a beta-divergence, in one pass over the activations
+// (tnmf_hip_atom_gram_beta).
 //
-// With R_m the contribution of atom m in its `group` orientations (planes m * group + t of H and W) and d = V - R:
-//   a[n, m] = sum G * R_m * d        B[n, m, m'] = sum G * R_m * R_m'        (G = 1 without weights)
-// diag(B) is the b of atoms.hip; with a and B the objective is an exact quadratic in per-atom scale factors.
+// The kernel of atom_gram.hip -- one workgroup per (sample, strip of pixel tiles, pair of atom blocks), r_m of the tile
+// parked in LDS and contracted over the pixels on the matrix cores (v_mfma_f64_16x16x4_f64) -- with the pixel factors of
+// atom_beta.h in the place of G d and G.  With x = max(R, 0) + eps:
+//   a[n, m]     = sum G R_m (V x^(beta-2) - x^(beta-1))
+//   B[n, m, m'] = sum G c R_m R_m',       c = (beta-1) x^(beta-2) + (2-beta) V x^(beta-3)
+// The weights G c of the contraction are signed (c < 0 occurs outside 1 <= beta <= 2): nothing clamps them at 0, and only
+// G <= 0 selects an exact zero.  Both factors are formed in double and rounded once to the element type.
 //
-// One workgroup = one (sample, strip of kGramStripTiles pixel tiles, pair (I, J) of atom blocks).  Per tile and channel it
-// builds r_m of the atoms of its two blocks exactly as k_atom_terms does -- planes of H streamed through LDS, taps through
-// the scalar cache from the flipped copy, packed f32 pairs -- and, when an atom's last plane is in, parks r_m of the tile in
-// LDS (and folds r * (G d) into a double, as k_atom_terms).  Then the four waves contract the parked rows over the tile's
-// pixels on the matrix cores: v_mfma_f64_16x16x4_f64 on 16 x 16 blocks of atom pairs, operands G * r_m (the product in
-// double) and r_m' converted to double, a quarter of the pixels per wave.  The accumulators stay in registers over the
-// tiles and channels of the strip; at its end the waves' blocks are added in wave order and written once per workgroup.
-//
-// Only blocks on or above the diagonal are accumulated, and k_atom_gram_finalize reads entry (m, m') and (m', m) from the
-// same place: B is symmetric to the bit.  It adds the strips in strip order.  No atomics: the same bits every run.
-//
-// With 32 rows parked only one workgroup fits a CU, so there the workgroup has 512 threads where the LDS allows: two halves
-// of 256 that build different atoms of the same tile at the same time, each from a tile of H of its own (HALVES = 2; the
-// contraction then gives every one of the eight waves an eighth of the pixels).
-//
-// M / group <= cap: one pair, blocks 0 and 1 are the atoms in order.  More atoms: every pair I < J of blocks of cap / 2
-// atoms is a workgroup of its own that builds r of both blocks again; the diagonal block of I (and a) is taken from the pair
-// (I, I + 1), of the last block from (I - 1, I).
+// The plan, the partial sums, the taps and the finalize kernel are those of atom_gram.hip (launch_atom_gram_finalize); B is
+// symmetric to the bit and the same from run to run for the same reasons.
 #include <algorithm>
+#include <cmath>
 
-#include "atom_gram.h"
+#include "atom_beta.h"
 
 namespace {
 
@@ -40,26 +30,6 @@ template <typename T>
 using Oct = T __attribute__((ext_vector_type(8)));
 using Acc = Quad<double>;
 
-// the flipped dictionary in runs of kAtomPix taps, plain (E) and shifted by one (O): the layout of k_atom_taps (atoms.hip)
-template <typename T>
-__global__ __launch_bounds__(kAtomThreads) void k_gram_taps(int rows, int Ay, int Ax, int NBO, const T *__restrict__ W,
-                                                            T *__restrict__ Wf) {
-    const size_t total = (size_t)rows * Ay * NBO * 2 * kAtomPix;
-    const int nA = Ay * Ax;
-    for (size_t i = (size_t)blockIdx.x * kAtomThreads + threadIdx.x; i < total; i += (size_t)gridDim.x * kAtomThreads) {
-        const int e = (int)(i % kAtomPix);
-        size_t rest = i / kAtomPix;
-        const int odd = (int)(rest % 2);
-        rest /= 2;
-        const int j = (int)(rest % NBO);
-        rest /= NBO;
-        const int a = (int)(rest % Ay);
-        const size_t mc = rest / Ay;
-        const int b = j * kAtomPix + e - odd;
-        Wf[i] = (b >= 0 && b < Ax) ? W[mc * nA + (nA - 1 - (a * Ax + b))] : T(0);
-    }
-}
-
 // the pair (I, J), I < J < nbk, of index `pair` in the order (0,1) (0,2) .. (1,2) ..
 __host__ __device__ inline void pair_blocks(int pair, int nbk, int &I, int &J) {
     I = 0;
@@ -70,15 +40,16 @@ __host__ __device__ inline void pair_blocks(int pair, int nbk, int &I, int &J) {
     J = I + 1 + pair;
 }
 
-template <typename T, int NBLK, int HALVES>   // NBLK = cap / 16
-__global__ __launch_bounds__(kAtomThreads * HALVES) void k_atom_gram(Geo g, GramPlan p, int group,
-                                                                     const T *__restrict__ V, const T *__restrict__ G,
-                                                                     const T *__restrict__ R, const T *__restrict__ Wf,
-                                                                     const T *__restrict__ H, double *__restrict__ partials) {
+template <typename T, int NBLK, int HALVES, int K>   // NBLK = cap / 16; K: the beta_kind of atom_beta.h
+__global__ __launch_bounds__(kAtomThreads * HALVES) void k_atom_gram_beta(Geo g, GramPlan p, int group, double beta,
+                                                                          double eps, const T *__restrict__ V,
+                                                                          const T *__restrict__ G, const T *__restrict__ R,
+                                                                          const T *__restrict__ Wf, const T *__restrict__ H,
+                                                                          double *__restrict__ partials) {
     extern __shared__ __attribute__((aligned(32))) unsigned char smem_raw[];
     constexpr int CAP = 16 * NBLK, HB = CAP / 2, NU = NBLK * (NBLK + 1) / 2;
     T *rs = reinterpret_cast<T *>(smem_raw);   // r[slot][pixel]
-    T *Gs = rs + CAP * kGramStride;            // G of the tile's pixels (0: outside the sample or weight <= 0)
+    T *Gs = rs + CAP * kGramStride;            // G c of the tile's pixels, signed (0: outside the sample or weight <= 0)
     // the half is the same for a whole wave; read through lane 0 so that the compiler knows it too: the plane, and with it
     // the address of the taps, is then uniform and the taps come through the scalar cache
     const int half = HALVES == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)threadIdx.x / kAtomThreads);
@@ -133,21 +104,21 @@ __global__ __launch_bounds__(kAtomThreads * HALVES) void k_atom_gram(Geo g, Gram
         const int y0 = tyi * ap.TY, x0 = txi * ap.TX;
         const int y = y0 + ty, xb = x0 + tx * kAtomPix;
         for (int c = 0; c < g.C; ++c) {
-            // G * d and G of this thread's pixels: pixels outside the sample and entries of weight <= 0 (whatever V holds
-            // there) carry exact zeros
+            // the two factors of atom_beta.h at this thread's pixels, formed in double: pixels outside the sample and
+            // entries of weight <= 0 (whatever V holds there) carry exact zeros and evaluate nothing
             T gd[kAtomPix];
             Quad<T> gw;
 #pragma unroll
             for (int px = 0; px < kAtomPix; ++px) {
                 const bool in = y < g.Dy && xb + px < g.Dx;
-                T w = T(0), d = T(0);
+                double d = 0.0, cw = 0.0;
                 if (in) {
                     const size_t o = (((size_t)n * g.C + c) * g.Dy + y) * g.Dx + xb + px;
-                    w = G ? G[o] : T(1);
-                    d = V[o] - R[o];
+                    const T w = G ? G[o] : T(1);
+                    if (w > T(0)) beta_pixel<K>((double)V[o], (double)R[o], (double)w, eps, beta, d, cw);
                 }
-                gw[px] = w > T(0) ? w : T(0);
-                gd[px] = w > T(0) ? w * d : T(0);
+                gw[px] = (T)cw;
+                gd[px] = (T)d;
             }
             // (the previous pass's contraction is behind the barrier that ends it)
             if (half == 0) reinterpret_cast<Quad<T> *>(Gs)[tid] = gw;
@@ -309,124 +280,87 @@ __global__ __launch_bounds__(kAtomThreads * HALVES) void k_atom_gram(Geo g, Gram
     if (threadIdx.x < CAP) out[CAP * CAP + tid] = acc_a;
 }
 
-// B[n, m, m'] = B[n, m', m] = the strips' sums of the entry (min, max) in strip order; a[n, m] next to the diagonal
-__global__ __launch_bounds__(kAtomThreads) void k_atom_gram_finalize(size_t total, GramPlan p, int Mo,
-                                                                     const double *__restrict__ partials,
-                                                                     double *__restrict__ a, double *__restrict__ B) {
-    const size_t i = (size_t)blockIdx.x * kAtomThreads + threadIdx.x;
-    if (i >= total) return;
-    const int m2 = (int)(i % Mo);
-    const size_t rest = i / Mo;
-    const int m1 = (int)(rest % Mo);
-    const size_t n = rest / Mo;
-    const int lo = m1 < m2 ? m1 : m2, hi = m1 < m2 ? m2 : m1;
-    int I = lo / p.hb, J = hi / p.hb;
-    if (I == J) {
-        if (I + 1 < p.nbk) J = I + 1;
-        else I = J - 1;
-    }
-    int pair = J - I - 1;
-    for (int k = 0; k < I; ++k) pair += p.nbk - 1 - k;
-    const int si = lo / p.hb == I ? lo - I * p.hb : p.hb + lo - J * p.hb;
-    const int sj = hi / p.hb == I ? hi - I * p.hb : p.hb + hi - J * p.hb;
-    const double *in = partials + ((size_t)n * p.strips * p.pairs + pair) * p.wg_doubles;
-    double sb = 0.0, sa = 0.0;
-    for (int s = 0; s < p.strips; ++s) {
-        const double *wg = in + (size_t)s * p.pairs * p.wg_doubles;
-        sb += wg[si * p.cap + sj];
-        if (m1 == m2) sa += wg[p.cap * p.cap + si];
-    }
-    B[i] = sb;
-    if (m1 == m2) a[n * Mo + m1] = sa;
-}
-
-template <typename T, int NBLK, int HALVES>
-int launch_gram(const tnmf_hip_ctx *ctx, const Geo &g, const GramPlan &p, int group, unsigned blocks, const void *V,
-                const void *G, const void *R,
-                const void *Wf, const void *H, double *partials, hipStream_t s) {
+template <typename T, int NBLK, int HALVES, int K>
+int launch_gram_kind(const tnmf_hip_ctx *ctx, const GramPlan &p, unsigned blocks, hipStream_t s, Geo g, int group, double beta,
+                     double eps, const T *V, const T *G, const T *R, const T *Wf, const T *H, double *partials) {
     // more than 64 KiB of dynamic LDS is an attribute of the (function, device) pair: set once for each
     static bool opted_in[64] = {};
     const int dev = ctx->device;
     if (p.lds > 64 * 1024 && !(dev >= 0 && dev < 64 && opted_in[dev])) {
-        TNMF_HIP_TRY(hipFuncSetAttribute((const void *)k_atom_gram<T, NBLK, HALVES>,
+        TNMF_HIP_TRY(hipFuncSetAttribute((const void *)k_atom_gram_beta<T, NBLK, HALVES, K>,
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGramLds));
         if (dev >= 0 && dev < 64) opted_in[dev] = true;
     }
-    hipLaunchKernelGGL((k_atom_gram<T, NBLK, HALVES>), dim3(blocks), dim3(kAtomThreads * HALVES), p.lds, s, g, p, group,
-                       (const T *)V,
-                       (const T *)G, (const T *)R, (const T *)Wf, (const T *)H, partials);
+    hipLaunchKernelGGL((k_atom_gram_beta<T, NBLK, HALVES, K>), dim3(blocks), dim3(kAtomThreads * HALVES), p.lds, s, g, p,
+                       group, beta, eps, V, G, R, Wf, H, partials);
     return TNMF_OK;
+}
+
+template <typename T, int NBLK, int HALVES>
+int launch_gram(const tnmf_hip_ctx *ctx, const Geo &g, const GramPlan &p, int group, double beta, double eps,
+                unsigned blocks, const void *V, const void *G, const void *R, const void *Wf, const void *H,
+                double *partials, hipStream_t s) {
+    const T *v = (const T *)V, *gp = (const T *)G, *r = (const T *)R, *wf = (const T *)Wf, *h = (const T *)H;
+    switch (beta_kind(beta)) {
+        case 0: return launch_gram_kind<T, NBLK, HALVES, 0>(ctx, p, blocks, s, g, group, beta, eps, v, gp, r, wf, h, partials);
+        case 1: return launch_gram_kind<T, NBLK, HALVES, 1>(ctx, p, blocks, s, g, group, beta, eps, v, gp, r, wf, h, partials);
+        default: return launch_gram_kind<T, NBLK, HALVES, 3>(ctx, p, blocks, s, g, group, beta, eps, v, gp, r, wf, h, partials);
+    }
 }
 
 }  // namespace
 
-GramPlan atom_gram_plan(const Geo &g, int dtype, int group) {
-    GramPlan p;
-    p.ap = atom_terms_plan(g);
-    const int Mo = g.M / group;
-    const size_t es = esize(dtype);
-    const size_t h_bytes = align_up((size_t)p.ap.SH * p.ap.SW * es, 32);
-    auto lds_of = [&](int cap, int halves) {
-        return ((size_t)cap * kGramStride + kGramTilePix) * es + halves * h_bytes + (size_t)cap * kWaves * sizeof(double);
-    };
-    p.cap = Mo > 16 && lds_of(32, 1) <= kGramLds ? 32 : lds_of(16, 1) <= kGramLds ? 16 : 0;
-    p.halves = p.cap == 32 && lds_of(32, 2) <= kGramLds ? 2 : 1;   // (16 rows leave room for two workgroups per CU as it is)
-    p.h_elems = h_bytes / es;
-    p.hb = p.cap / 2;
-    p.nbk = p.cap ? std::max(2, cdiv(Mo, p.hb)) : 2;
-    p.pairs = p.nbk * (p.nbk - 1) / 2;
-    p.tiles = p.ap.tiles_y * p.ap.tiles_x;
-    p.strips = cdiv(p.tiles, kGramStripTiles);
-    p.red_off = ((size_t)p.cap * kGramStride + kGramTilePix) * es + p.halves * h_bytes;
-    p.lds = lds_of(p.cap, p.halves);
-    p.wg_doubles = (size_t)p.cap * p.cap + p.cap;
-    return p;
-}
-
-size_t atom_gram_partial_bytes(const Geo &g, int dtype, int group) {
-    const GramPlan p = atom_gram_plan(g, dtype, group);
-    return align_up((size_t)g.N * p.strips * p.pairs * p.wg_doubles * sizeof(double), 256);
-}
-
-int atom_gram_check(const Geo &g, int dtype, int group) {
-    const GramPlan p = atom_gram_plan(g, dtype, group);
-    if (p.cap == 0) return TNMF_E_UNSUPPORTED;
-    if ((size_t)g.N * p.strips * p.pairs > 0x7fffffffull) return TNMF_E_GEOM;
-    return TNMF_OK;
-}
-
-int launch_atom_gram(const tnmf_hip_ctx *ctx, const Geo &g, int dtype, int group, const void *V, const void *G,
-                     const void *R, const void *W, const void *H, double *partials, void *taps, double *a, double *B,
-                     hipStream_t s) {
+int launch_atom_gram_beta(const tnmf_hip_ctx *ctx, const Geo &g, int dtype, int group, double beta, double eps,
+                          const void *V, const void *G, const void *R, const void *W, const void *H, double *partials,
+                          void *taps, double *a, double *B, hipStream_t s) {
     const int rc = atom_gram_check(g, dtype, group);
     if (rc != TNMF_OK) return rc;
     const GramPlan p = atom_gram_plan(g, dtype, group);
     const size_t blocks = (size_t)g.N * p.strips * p.pairs;
-    const int rows = g.M * g.C;
-    const size_t n_taps = (size_t)rows * g.Ay * p.ap.NBO * 2 * kAtomPix;
-    const unsigned tap_blocks = (unsigned)std::min<size_t>((n_taps + kAtomThreads - 1) / kAtomThreads, (size_t)ctx->num_cu * 8);
+    const int trc = launch_atom_taps(ctx, g, dtype, W, taps, s);
+    if (trc != TNMF_OK) return trc;
     const int lrc = with_dtype(dtype, [&](auto zero) {
         using T = decltype(zero);
-        hipLaunchKernelGGL(k_gram_taps<T>, dim3(tap_blocks), dim3(kAtomThreads), 0, s, rows, g.Ay, g.Ax, p.ap.NBO,
-                           (const T *)W, (T *)taps);
         if constexpr (sizeof(T) == sizeof(float)) {   // (32 rows of doubles never fit: those kernels do not exist)
-            if (p.halves == 2) return launch_gram<T, 2, 2>(ctx, g, p, group, (unsigned)blocks, V, G, R, taps, H, partials, s);
-            if (p.cap == 32) return launch_gram<T, 2, 1>(ctx, g, p, group, (unsigned)blocks, V, G, R, taps, H, partials, s);
+            if (p.halves == 2)
+                return launch_gram<T, 2, 2>(ctx, g, p, group, beta, eps, (unsigned)blocks, V, G, R, taps, H, partials, s);
+            if (p.cap == 32)
+                return launch_gram<T, 2, 1>(ctx, g, p, group, beta, eps, (unsigned)blocks, V, G, R, taps, H, partials, s);
         }
         if (p.cap != 16) return (int)TNMF_E_UNSUPPORTED;
-        return launch_gram<T, 1, 1>(ctx, g, p, group, (unsigned)blocks, V, G, R, taps, H, partials, s);
+        return launch_gram<T, 1, 1>(ctx, g, p, group, beta, eps, (unsigned)blocks, V, G, R, taps, H, partials, s);
     });
     if (lrc != TNMF_OK) return lrc;
     TNMF_LAUNCH_CHECK();
     return launch_atom_gram_finalize(g, p, group, partials, a, B, s);
 }
 
-int launch_atom_gram_finalize(const Geo &g, const GramPlan &p, int group, const double *partials, double *a, double *B,
-                              hipStream_t s) {
-    const int Mo = g.M / group;
-    const size_t total = (size_t)g.N * Mo * Mo;
-    hipLaunchKernelGGL(k_atom_gram_finalize, dim3((unsigned)((total + kAtomThreads - 1) / kAtomThreads)), dim3(kAtomThreads),
-                       0, s, total, p, Mo, partials, a, B);
-    TNMF_LAUNCH_CHECK();
-    return TNMF_OK;
+extern "C" {
+
+int tnmf_hip_atom_gram_beta(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int group, double beta, double eps, const void *V,
+                            const void *G_or_null, const void *R_or_null, const void *W, const void *H, double *a, double *B,
+                            void *stream) {
+    if (!ctx || !geom) return TNMF_E_NULL;
+    Geo g;
+    int rc = atom_entry_geo(geom, &g);
+    if (rc != TNMF_OK) return rc;
+    const int dtype = geom->dtype;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    TNMF_HIP_TRY(hipSetDevice(ctx->device));
+    if (group < 1 || g.M % group != 0 || !std::isfinite(beta) || !(eps >= 0.0)) return TNMF_E_GEOM;
+    if (beta == 2.0) return tnmf_hip_atom_gram(ctx, geom, group, V, G_or_null, R_or_null, W, H, a, B, stream);
+    if (g.N == 0) return TNMF_OK;
+    if (!V || !W || !H || !a || !B) return TNMF_E_NULL;
+    rc = atom_gram_check(g, dtype, group);
+    if (rc != TNMF_OK) return rc;
+    // work buffer: as tnmf_hip_atom_gram
+    const size_t p_bytes = atom_gram_partial_bytes(g, dtype, group);
+    const void *R = R_or_null;
+    void *buf = nullptr;
+    rc = atom_entry_buffers(ctx, g, dtype, p_bytes + atom_terms_taps_bytes(g, dtype), W, H, &R, &buf, s);
+    if (rc != TNMF_OK) return rc;
+    return launch_atom_gram_beta(ctx, g, dtype, group, beta, eps, V, G_or_null, R, W, H, static_cast<double *>(buf),
+                                 static_cast<char *>(buf) + p_bytes, a, B, s);
 }
+
+}  // extern "C"
