@@ -1,5 +1,5 @@
 """
-Host mirror of the launch of tnmf_amd/csrc/atom_gram.hip (k_gram_taps, k_atom_gram, k_atom_gram_finalize), restated in plain
+Host mirror of the launch of tnmf_amd/csrc/atom_gram.hip (k_atom_taps, k_atom_gram, k_atom_gram_finalize), restated in plain
 Python in the manner of tests/atoms_dispatch.py, so that tests/test_hip_atom_gram.py can choose the smallest problems that
 execute every branch of the kernel and tests/test_atom_gram_dispatch_cpu.py can check without a GPU that the choice covers
 them.  The pixel tile, the halo and the tap runs are those of atoms_dispatch.plan().

@@ -231,6 +231,7 @@ def test_both_entry_points_are_declared_exported_and_built():
         assert re.search(rf'\bint {entry}\s*\(', header) and entry in _lib.EXPORTS
         assert re.search(rf'^SRCS\s*:=.*\b{re.escape(source)}\b', makefile, flags=re.M)
     assert re.search(r'^HDRS\s*:=.*\batom_beta\.h\b', makefile, flags=re.M)
+    assert re.search(r'^HDRS\s*:=.*\batom_gram_kernel\.h\b', makefile, flags=re.M)   # the kernel text both Gram files include
     assert _lib.ABI_VERSION == 8
     lib = _lib.load()
     vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double

@@ -1,6 +1,6 @@
-"""CPU guard of tests/atom_gram_dispatch.py: its constants are those of atom_gram.h / atom_gram.hip, and the shapes of its
-matrix -- the ones tests/test_hip_atom_gram.py runs -- reach every branch of the kernel in both precisions.  Sources read as
-text; no GPU."""
+"""CPU guard of tests/atom_gram_dispatch.py: its constants are those of atom_gram.h / atom_gram.hip with the kernel text it
+includes (atom_gram_kernel.h, atom_walk.h), and the shapes of its matrix -- the ones tests/test_hip_atom_gram.py runs -- reach
+every branch of the kernel in both precisions.  Sources read as text; no GPU."""
 import os
 import re
 
@@ -15,7 +15,8 @@ def _flat(name):
 
 
 def test_the_constants_are_the_kernels():
-    h, hip = _flat('atom_gram.h'), _flat('atom_gram.hip')
+    # (the kernel is built from atom_gram.hip and the body, constants and aliases it includes)
+    h, hip = _flat('atom_gram.h'), ' '.join(_flat(name) for name in ('atom_gram.hip', 'atom_gram_kernel.h', 'atom_walk.h'))
     assert 'constexpr int kGramTilePix = kAtomThreads * kAtomPix;' in h and gd.TILE_PIX == 1024
     assert f'constexpr int kGramStride = kGramTilePix + {gd.STRIDE - gd.TILE_PIX};' in h
     assert f'constexpr int kGramStripTiles = {gd.STRIP_TILES};' in h

@@ -1,5 +1,6 @@
-// atom_walk.h -- the walk over the planes of H that atoms.hip (what each atom explains) and sources.hip (the per-source
-// signals) share: device code only, included by those two.
+// atom_walk.h -- the walk over the planes of H that atoms.hip and atoms_beta.hip (what each atom explains) and sources.hip
+// (the per-source signals) share: device code only, included by those three (and, for the vector aliases alone, by
+// atom_gram_kernel.h).
 //
 // One workgroup of kAtomThreads threads owns a pixel tile of one sample and a chunk of up to CH channels.  A plane's tile +
 // halo goes through LDS (the next plane's is fetched into registers under the multiply-adds), every thread accumulates the
@@ -15,8 +16,10 @@
 //
 // The steps are statement macros, not functions: tnmf_hip_atom_terms is pinned to its device code (tools/
 // device_code_diff.py), and every function boundary tried around these lines -- a struct with inlined members, a single
-// inlined function around the multiply-adds alone -- changed the register allocation of k_atom_terms.  Text pasted into
-// the kernel cannot.  A kernel that uses them is a template over <typename T, int CH> with these names in scope:
+// inlined function around the multiply-adds alone, the whole body of k_atom_gram as an inlined template under a thin
+// __global__ wrapper -- changed the register allocation of the kernel.  Text pasted into the kernel does not: neither these
+// macros nor a body that the kernel #includes (atom_gram_kernel.h).  A kernel that uses them is a template over
+// <typename T, int CH> with these names in scope:
 //   Geo g, AtomPlan p; const T *H, *Wf (the flipped taps); T *Hs (LDS, p.SH * p.SW elements, 32-byte aligned);
 //   int n, tyi, txi (sample, tile row, tile column); int c0, nc (first channel and channels of the chunk, uniform);
 //   constexpr int kStage, the kernel file's own: tile elements per thread that the register stage holds (what its
@@ -130,3 +133,37 @@ using Oct = T __attribute__((ext_vector_type(8)));
             cur = nxt;                                                                            \
         }                                                                                         \
     }
+
+// ---- The two steps that only the terms kernels take (atoms.hip, atoms_beta.hip) ----
+//
+// 0. The workgroup's place, before step 1: sample n, tile (tyi, txi) and channel chunk from blockIdx.x; `slot` numbers the
+// partial sums of a (sample, atom).
+#define ATOM_TERMS_BLOCK()                                       \
+    unsigned bid = blockIdx.x;                                   \
+    const int chunk = bid % p.chunks;                            \
+    bid /= p.chunks;                                             \
+    const int txi = bid % p.tiles_x;                             \
+    bid /= p.tiles_x;                                            \
+    const int tyi = bid % p.tiles_y;                             \
+    const int n = bid / p.tiles_y;                               \
+    const int slot = (tyi * p.tiles_x + txi) * p.chunks + chunk; \
+    const int c0 = chunk * CH;                                   \
+    const int nc = g.C - c0 < CH ? g.C - c0 : CH;
+
+// 5. Inside the loop over the planes, after `if (pre_ok) fetch(0);`: plane = orientation t of atom mo; r starts from zero at
+// an atom's first plane; steps 3 and 4.  After its last plane (t == group - 1) the kernel folds r_m into its sums.  Needs
+// int group (planes per atom) besides the names above.
+#define ATOM_TERMS_PLANE(plane, r)                                                            \
+    const int mo = plane / group, t = plane - mo * group;                                     \
+    if (t == 0) {                                                                             \
+        _Pragma("unroll") for (int c = 0; c < CH; ++c)                                        \
+            _Pragma("unroll") for (int px = 0; px < kAtomPix; ++px) r[c][px] = Pair<T>(T(0)); \
+    }                                                                                         \
+    ATOM_WALK_STAGE(plane, plane + 1 < g.M, plane + 1);                                       \
+    ATOM_WALK_MACS(plane, r);
+
+// The reduction of those sums -- a shuffle tree over the wave, the waves' sums through LDS, added in wave order and written
+// every kAtomChunk (kBetaChunk) atoms -- is written out in both kernels, on named doubles.  Written once on double ps[NS]
+// it reproduces the device code of k_atom_terms (NS = 2) but not of k_atom_terms_beta (NS = 3): the shuffle tree on an
+// array element changes the register allocation of 3 to 24 of its 24 instances, in either loop order, with and without
+// an unroll pragma.  Do not retry without a new idea.

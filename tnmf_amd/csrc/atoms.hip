@@ -57,17 +57,7 @@ __global__ __launch_bounds__(kAtomThreads) void k_atom_terms(Geo g, AtomPlan p, 
     T *Hs = reinterpret_cast<T *>(smem_raw);
     const int Mo = g.M / group;
 
-    unsigned bid = blockIdx.x;
-    const int chunk = bid % p.chunks;
-    bid /= p.chunks;
-    const int txi = bid % p.tiles_x;
-    bid /= p.tiles_x;
-    const int tyi = bid % p.tiles_y;
-    const int n = bid / p.tiles_y;
-    const int slot = (tyi * p.tiles_x + txi) * p.chunks + chunk;
-    const int c0 = chunk * CH;
-    const int nc = g.C - c0 < CH ? g.C - c0 : CH;   // channels of this chunk (uniform)
-
+    ATOM_TERMS_BLOCK();
     ATOM_WALK_PIXELS();
 
     // G * d and G of this thread's pixels, every channel of the chunk: read once, kept in registers.  Pixels outside the
@@ -96,15 +86,7 @@ __global__ __launch_bounds__(kAtomThreads) void k_atom_terms(Geo g, AtomPlan p, 
     Pair<T> r[CH][kAtomPix];   // (r of pixel px is r[c][px].x + r[c][px].y)
     if (pre_ok) fetch(0);
     for (int plane = 0; plane < g.M; ++plane) {
-        const int mo = plane / group, t = plane - mo * group;
-        if (t == 0) {
-#pragma unroll
-            for (int c = 0; c < CH; ++c)
-#pragma unroll
-                for (int px = 0; px < kAtomPix; ++px) r[c][px] = Pair<T>(T(0));
-        }
-        ATOM_WALK_STAGE(plane, plane + 1 < g.M, plane + 1);
-        ATOM_WALK_MACS(plane, r);
+        ATOM_TERMS_PLANE(plane, r);
         if (t != group - 1) continue;
         // r_m is complete: fold into the two sums, in double
         double pa = 0.0, pb = 0.0;
@@ -216,13 +198,10 @@ int launch_atom_terms(const tnmf_hip_ctx *ctx, const Geo &g, int dtype, int grou
     const AtomPlan p = atom_terms_plan(g);
     const size_t lds = (size_t)p.SH * p.SW * esize(dtype);
     const size_t blocks = (size_t)g.N * p.slots;
-    const int rows = g.M * g.C;
-    const size_t n_taps = (size_t)rows * g.Ay * p.NBO * 2 * kAtomPix;
-    const unsigned tap_blocks = (unsigned)std::min<size_t>((n_taps + kAtomThreads - 1) / kAtomThreads, (size_t)ctx->num_cu * 8);
+    const int trc = launch_atom_taps(ctx, g, dtype, W, taps, s);
+    if (trc != TNMF_OK) return trc;
     with_dtype(dtype, [&](auto zero) {
         using T = decltype(zero);
-        hipLaunchKernelGGL(k_atom_taps<T>, dim3(tap_blocks), dim3(kAtomThreads), 0, s, rows, g.Ay, g.Ax, p.NBO, (const T *)W,
-                           (T *)taps);
         switch (p.CH) {
             case 1: launch_chunked<T, 1>(g, p, group, (unsigned)blocks, lds, V, G, R, taps, H, partials, s); break;
             case 2: launch_chunked<T, 2>(g, p, group, (unsigned)blocks, lds, V, G, R, taps, H, partials, s); break;

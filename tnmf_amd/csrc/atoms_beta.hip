@@ -39,17 +39,7 @@ __global__ __launch_bounds__(kAtomThreads) void k_atom_terms_beta(Geo g, AtomPla
     T *Hs = reinterpret_cast<T *>(smem_raw);
     const int Mo = g.M / group;
 
-    unsigned bid = blockIdx.x;
-    const int chunk = bid % p.chunks;
-    bid /= p.chunks;
-    const int txi = bid % p.tiles_x;
-    bid /= p.tiles_x;
-    const int tyi = bid % p.tiles_y;
-    const int n = bid / p.tiles_y;
-    const int slot = (tyi * p.tiles_x + txi) * p.chunks + chunk;
-    const int c0 = chunk * CH;
-    const int nc = g.C - c0 < CH ? g.C - c0 : CH;   // channels of this chunk (uniform)
-
+    ATOM_TERMS_BLOCK();
     ATOM_WALK_PIXELS();
 
     // V, R and the clipped G of this thread's pixels, every channel of the chunk, and the two factors of atom_beta.h: read
@@ -86,15 +76,7 @@ __global__ __launch_bounds__(kAtomThreads) void k_atom_terms_beta(Geo g, AtomPla
     Pair<T> r[CH][kAtomPix];   // (r of pixel px is r[c][px].x + r[c][px].y)
     if (pre_ok) fetch(0);
     for (int plane = 0; plane < g.M; ++plane) {
-        const int mo = plane / group, t = plane - mo * group;
-        if (t == 0) {
-#pragma unroll
-            for (int c = 0; c < CH; ++c)
-#pragma unroll
-                for (int px = 0; px < kAtomPix; ++px) r[c][px] = Pair<T>(T(0));
-        }
-        ATOM_WALK_STAGE(plane, plane + 1 < g.M, plane + 1);
-        ATOM_WALK_MACS(plane, r);
+        ATOM_TERMS_PLANE(plane, r);
         if (t != group - 1) continue;
         // r_m is complete: fold into the three sums, in double
         double pa = 0.0, pb = 0.0, pg = 0.0;
