@@ -74,19 +74,23 @@ def test_mirrored_rules_are_those_of_the_sources():
         assert line in events_h, line
     # the occurrence walk the wave kernels share: the image table and the lane loop, and one call per wave kernel with a
     # lane's first tap and stride
-    walk = _read(CSRC, 'event_walk.h')
+    walk, modes = _read(CSRC, 'event_walk.h'), _read(CSRC, 'modes.h')
     for line in ('if (mode == TNMF_MODE_CIRCULAR && u >= S - (a - 1)) {',
-                 'if (mode == TNMF_MODE_REFLECT && u >= 1 && u <= a - 1) {',
-                 'for (int t = first; t < taps; t += step) {'):
-        assert line in walk, line
+                 'if (mode == TNMF_MODE_REFLECT && u >= 1 && u <= a - 1) {'):
+        assert modes.count(line) == 1, line   # (axis_images: the image table, in modes.h and nowhere else)
+    assert '#include "modes.h"' in walk and 'TNMF_MODE_' not in walk and 'axis_images(mode, u, ' not in walk
+    assert 'for (int t = first; t < taps; t += step) {' in walk
     assert src.count('for_each_tap(g, o, lane, 64, [&](int t, int c, int y, int x) {') == 2   # k_events_update, k_events_gain
     assert src.count('for_each_tap(') == 2 and 'axis_images(mode, u' not in src
     api = _read(CSRC, 'api.hip')
     for line in ('g->ncy = cdiv(g->Dy + g->Ay - 1, g->ty), g->ncx = cdiv(g->Dx + g->Ax - 1, g->tx);',
-                 'S[i] = mode == TNMF_MODE_VALID ? D[i] + A[i] - 1 : mode == TNMF_MODE_FULL ? D[i] - A[i] + 1 : D[i];',
-                 'if (S[i] < 1 || (mode == TNMF_MODE_CIRCULAR && A[i] - 1 > S[i]) || (mode == TNMF_MODE_REFLECT && '
-                 'A[i] - 1 >= S[i]))'):
+                 'if (!mode_known(mode)) return TNMF_E_GEOM;',
+                 'S[0] = mode_shift_len(mode, g.Dy, g.Ay), S[1] = mode_shift_len(mode, g.Dx, g.Ax);',
+                 'return mode_axis_ok(mode, S[0], g.Ay) && mode_axis_ok(mode, S[1], g.Ax) ? TNMF_OK : TNMF_E_GEOM;'):
         assert line in api, line
+    for line in ('return mode == TNMF_MODE_VALID ? D + a - 1 : (mode == TNMF_MODE_FULL ? D - a + 1 : D);',
+                 'return S >= 1 && (mode != TNMF_MODE_CIRCULAR || a - 1 <= S) && (mode != TNMF_MODE_REFLECT || a - 1 < S);'):
+        assert modes.count(line) == 1, line
     backend = _read('tnmf_amd', 'backends', 'HIP.py')
     for line in ('nc = [-(-(d + a - 1) // c) for d, a, c in zip(self._sample_shape, self.atom_shape, cells)]',
                  "key = key * nc[i] + torch.div(q[:, i], cells[i], rounding_mode='floor')",

@@ -1,6 +1,6 @@
 """
 CPU guard of the lateral matrix: the host mirror of the H half step in full (tests/lateral_dispatch.py) is held to the
-C++ it restates (inhibit.hip, generic.h, generic.hip, api.hip, read as text), and the cases of
+C++ it restates (inhibit.hip, generic.h, generic.hip, modes.h, api.hip, read as text), and the cases of
 tests/test_hip_lateral_matrix.py are held to reaching all eight k_inhibition instances, both dtypes of k_mu_update_extra,
 k_fold_update, k_pad_H, k_fold_H and k_convolve_axis, every edge class on every instance that can have it, every refusal
 and every route of update_H_2d.  No GPU, no build.
@@ -57,33 +57,39 @@ def test_mirrored_constants_and_rules_are_those_of_the_source():
             f'hipFuncAttributeMaxDynamicSharedMemorySize, {ld.LDS_MAX // 1024} * 1024));',
             'if (ly < 1 || lx < 1 || ly > kMaxTaps || lx > kMaxTaps || !(ly & 1) || !(lx & 1)) return TNMF_E_UNSUPPORTED; '
             'if (N <= 0) return TNMF_OK;',
-            # the duplicate-position table of the fold + update
-            'if (mode == TNMF_MODE_CIRCULAR) return u >= S - l ? u - (S - l) : -1; '
-            'if (mode == TNMF_MODE_REFLECT) return (u >= 1 && u <= l) ? l - u : -1; return -1;',
-            'const int jy[2] = {Py == 1 ? 0 : uy + Ay - 1, Py == 1 ? -1 : dup_of(uy, Sy, Ay, mode)};'):
+            # the fold + update: the duplicate positions are those of modes.h
+            'const int jy[2] = {Py == 1 ? 0 : uy + Ay - 1, Py == 1 ? -1 : pad_dup(uy, Sy, Ay, mode)};'):
         assert line in inh, line
+    modes = _flat(_read('modes.h'))
+    for line in (
+            # the per-axis rule, stated once: the shift length, the limits, the duplicate-position table
+            'return mode == TNMF_MODE_VALID ? D + a - 1 : (mode == TNMF_MODE_FULL ? D - a + 1 : D);',
+            'return S >= 1 && (mode != TNMF_MODE_CIRCULAR || a - 1 <= S) && (mode != TNMF_MODE_REFLECT || a - 1 < S);',
+            'if (mode == TNMF_MODE_CIRCULAR) return u >= S - l ? u - (S - l) : -1; '
+            'if (mode == TNMF_MODE_REFLECT) return (u >= 1 && u <= l) ? l - u : -1; return -1;'):
+        assert modes.count(line) == 1, line
+    for name in ('generic.hip', 'inhibit.hip', 'volume.hip', 'event_walk.h'):   # ... and nowhere else
+        text = _read(name)
+        assert '#include "modes.h"' in text and not re.search(r'TNMF_MODE_(FULL|CIRCULAR|REFLECT)', text), name
     assert f'constexpr int kMaxTaps = {ld.kMaxTaps};' in hdr
     assert ld.PLANE_LIMIT == 1 << 31 and ld.BLOCKS_LIMIT == 0x7fffffff
     for line in (
             # launch_pad_fold and its guards; the convolution of the front end's fall-back
-            'return mode == TNMF_MODE_VALID ? d + a - 1 : (mode == TNMF_MODE_FULL ? d - a + 1 : d);',
-            'const int Sy = g.Dy == 1 && g.Ay == 1 ? 1 : mode_shift(g.Dy, g.Ay, mode), Sx = mode_shift(g.Dx, g.Ax, mode); '
-            'if (Sy < 1 || Sx < 1) return TNMF_E_GEOM;',
-            'if (mode == TNMF_MODE_CIRCULAR && (g.Ay - 1 > Sy || g.Ax - 1 > Sx)) return TNMF_E_GEOM;',
-            'if (mode == TNMF_MODE_REFLECT && (g.Ay - 1 >= Sy || g.Ax - 1 >= Sx)) return TNMF_E_GEOM;',
-            'if (mode == TNMF_MODE_CIRCULAR) return u >= S - l ? u - (S - l) : -1; '
-            'if (mode == TNMF_MODE_REFLECT) return (u >= 1 && u <= l) ? l - u : -1; return -1;',
+            'const int Sy = mode_shift_len(mode, g.Dy, g.Ay), Sx = mode_shift_len(mode, g.Dx, g.Ax); '
+            'if (!mode_axis_ok(mode, Sy, g.Ay) || !mode_axis_ok(mode, Sx, g.Ax)) return TNMF_E_GEOM;',
+            'const int jy[2] = {Py == 1 ? 0 : uy + Ay - 1, Py == 1 ? -1 : pad_dup(uy, Sy, Ay, mode)};',
             'if (ntaps < 1 || ntaps > kMaxTaps || (ntaps & 1) == 0) return TNMF_E_UNSUPPORTED;',
             'const int src = i + rad - t;'):
         assert line in gen, line
     pad_fold = gen.index('int launch_pad_fold(')
-    assert len(re.findall(r'return TNMF_E_GEOM;', gen[pad_fold:gen.index('with_dtype(', pad_fold)])) == 3
+    assert len(re.findall(r'return TNMF_E_GEOM;', gen[pad_fold:gen.index('with_dtype(', pad_fold)])) == 1   # (the three limits)
     for line in (
             # update_H_2d
             'const bool lateral = inhibition > 0 || cross_inhibition > 0;',
             'const double *ky = geom->ndim == 2 ? kernel0 : &one, *kx = geom->ndim == 2 ? kernel1 : kernel0; '
             'const int ly = geom->ndim == 2 ? len0 : 1, lx = geom->ndim == 2 ? len1 : len0;',
-            'const double xc = cross_inhibition > 0 && g.M > 1 ? cross_inhibition / (g.M - 1) : 0.0;',
+            'return cross_inhibition > 0 && M > 1 ? cross_inhibition / (M - 1) : 0.0;',
+            'const double xc = cross_weight(cross_inhibition, g.M);',
             'const size_t nE = align_up((size_t)g.N * g.M * g.Hy * g.Hs * es, 256); '
             'const size_t nG = align_up((size_t)g.N * g.M * g.Hy * g.Hx * es, 256);',
             'CHECK(ensure_hwork(ctx, nE)); E = ctx->hw; '
@@ -92,8 +98,8 @@ def test_mirrored_constants_and_rules_are_those_of_the_source():
             'if (ctx->hw_bytes < nE + 2 * nG) {',
             'CHECK(do_corr_W(ctx, g, dtype, V, Rs, W, nullptr, neg, pos, false, 0.0, s));',
             'return launch_mu_update_extra(ctx, dtype, H_inout, neg, pos, E, (size_t)g.N * g.M * g.Hy, g.Hx, g.Hs, reg, s);',
-            'const int Sy = geom->ndim == 1 ? 1 : (mode == TNMF_MODE_FULL ? g.Dy - g.Ay + 1 : g.Dy); '
-            'const int Sx = mode == TNMF_MODE_FULL ? g.Dx - g.Ax + 1 : g.Dx; if (Sy < 1 || Sx < 1) return TNMF_E_GEOM;',
+            'const int Sy = geom->ndim == 1 ? 1 : mode_shift_len(mode, g.Dy, g.Ay), Sx = mode_shift_len(mode, g.Dx, g.Ax); '
+            'if (Sy < 1 || Sx < 1) return TNMF_E_GEOM;',
             'CHECK(ensure_hwork(ctx, 3 * nP + nE));',
             'CHECK(launch_pad_fold(ctx, g, dtype, mode, false, H_inout, Hp, s)); CHECK(do_reconstruct(ctx, g, dtype, W, Hp, Rs, s));',
             'if (lateral) CHECK(launch_inhibition(ctx, dtype, g.N, g.M, Sy, Sx, H_inout, E, ky, ly, kx, lx, inhibition, xc, s));',
@@ -108,9 +114,7 @@ def test_mirrored_constants_and_rules_are_those_of_the_source():
     assert ld.HW_ALIGN == 1 << 20
     assert 'if (extra && (!fused || g.Hs % SP_TX != 0 || Cfg::ONE_D)) return TNMF_E_UNSUPPORTED;' in _flat(_read('split_kernels.h'))
     # volumes share the guards of the modes
-    vol = _flat(_read('volume.hip'))
-    assert 'if (mode == TNMF_MODE_CIRCULAR && v.A[i] - 1 > q.S[i]) return TNMF_E_GEOM;' in vol
-    assert 'if (mode == TNMF_MODE_REFLECT && v.A[i] - 1 >= q.S[i]) return TNMF_E_GEOM;' in vol
+    assert 'if (!mode_axis_ok(mode, q.S[i], v.A[i])) return TNMF_E_GEOM;' in _flat(_read('volume.hip'))
 
 
 def test_launch_chain_is_that_of_the_source():

@@ -36,19 +36,22 @@ def test_mirrored_constants_and_rules_are_those_of_the_source():
     """The lines the mirror restates.  When one of them changes, tests/schedule_dispatch.py and the matrix's cases have to
     be looked at again."""
     api, gen, hdr = (_flat(_read(n)) for n in ('api.hip', 'generic.hip', 'common.h'))
-    # ---- validation: the 2-D entry and the volume entry, the same lines in the same order
+    # ---- validation: the 2-D entry and the volume entry, the same lines in the same order; the list's check stated once
+    assert api.count('if (n_ops < 0 || (n_ops > 0 && !ops)) return TNMF_E_NULL; '
+                     'if (!V || !W_inout || !H_inout || !acc) return TNMF_E_NULL;') == 2
+    check = api[api.index('int check_ops(const tnmf_hip_op *ops, int n_ops, int N) {'):api.index('inline bool is_vol(')]
     for line in (
-            'if (n_ops < 0 || (n_ops > 0 && !ops)) return TNMF_E_NULL; if (!V || !W_inout || !H_inout || !acc) return TNMF_E_NULL;',
             'if (ops[i].kind != TNMF_OP_UPDATE_H && ops[i].kind != TNMF_OP_GRAD_W && ops[i].kind != TNMF_OP_APPLY_W) '
-            'return TNMF_E_UNSUPPORTED; if (ops[i].kind == TNMF_OP_APPLY_W) continue;'):
-        assert api.count(line) == 2, line
-    assert 'if (ops[i].n0 < 0 || ops[i].n1 < ops[i].n0 || ops[i].n1 > g.N) return TNMF_E_GEOM;' in api
-    assert 'if (ops[i].n0 < 0 || ops[i].n1 < ops[i].n0 || ops[i].n1 > v.N) return TNMF_E_GEOM;' in api
+            'return TNMF_E_UNSUPPORTED; if (ops[i].kind == TNMF_OP_APPLY_W) continue;',
+            'if (ops[i].n0 < 0 || ops[i].n1 < ops[i].n0 || ops[i].n1 > N) return TNMF_E_GEOM;'):
+        assert line in check and api.count(line) == 1, line
+    assert check.index('return TNMF_E_UNSUPPORTED;') < check.index('return TNMF_E_GEOM;')
     vol = api[api.index('int vol_api_run_schedule('):api.index('int vol_api_pad_fold(')]
-    assert vol.index('return TNMF_E_UNSUPPORTED;') < vol.index('return TNMF_E_GEOM;') < vol.index('vol_scratch(')
-    assert vol.index('return TNMF_E_GEOM;') < vol.index('switch (op.kind)')
+    assert vol.index('!acc) return TNMF_E_NULL;') < vol.index('CHECK(check_ops(ops, n_ops, v.N));') < vol.index('vol_scratch(') \
+        < vol.index('switch (op.kind)')
     two = api[api.index('int tnmf_hip_run_schedule('):api.index('int tnmf_hip_axpby(')]
-    assert two.index('return TNMF_E_UNSUPPORTED;') < two.index('return TNMF_E_GEOM;') < two.index('std::vector<tnmf_hip_op> joined;')
+    assert two.index('!acc) return TNMF_E_NULL;') < two.index('CHECK(check_ops(ops, n_ops, g.N));') \
+        < two.index('std::vector<tnmf_hip_op> joined;')
     for line in (
             # ---- joining
             'run.erase(std::remove_if(run.begin(), run.end(), [](const tnmf_hip_op &o) { return o.n1 <= o.n0; }), run.end());',

@@ -104,9 +104,11 @@ def test_constants_and_rules_are_those_of_the_sources():
                  'const T *w0 = W + (size_t)(v.y / block * block + v.y % stride) * taps;        // the first candidate'):
         assert line in alternatives, line
     for line in ('if ((unsigned)y < (unsigned)g.Dy && (unsigned)x < (unsigned)g.Dx) f(t, c, y, x);',
-                 'if ((unsigned)lx < (unsigned)g.Ax) phi += (double)w[cAA + ly * g.Ax + lx];',
-                 'return o >= 0 && o + a <= D;'):
+                 'if ((unsigned)lx < (unsigned)g.Ax) phi += (double)w[cAA + ly * g.Ax + lx];'):
         assert line in walk, line
+    # axis_whole: with the image table, in modes.h
+    assert '#include "modes.h"' in walk and 'axis_whole' not in walk.split('#pragma once')[1]
+    assert _read(CSRC, 'modes.h').count('return o >= 0 && o + a <= D;') == 1
 
 
 def test_known_answers_of_the_rules():

@@ -111,10 +111,12 @@ def test_mirrored_rules_are_those_of_the_sources():
     assert '#include "event_walk.h"' in src and 'axis_images(' not in src
     header = _read(CSRC, 'solve.h')
     assert 'long long events_nnls_workspace(long long n_rows);' in header and 'while slot < capacity' in header
-    walk = _read(CSRC, 'event_walk.h')
+    walk, modes = _read(CSRC, 'event_walk.h'), _read(CSRC, 'modes.h')
     for line in ('if (mode == TNMF_MODE_CIRCULAR && u >= S - (a - 1)) {',
-                 'if (mode == TNMF_MODE_REFLECT && u >= 1 && u <= a - 1) {',
-                 'for (int t = first; t < taps; t += step) {',
+                 'if (mode == TNMF_MODE_REFLECT && u >= 1 && u <= a - 1) {'):
+        assert modes.count(line) == 1, line   # (axis_images: the image table, in modes.h and nowhere else)
+    assert '#include "modes.h"' in walk and 'TNMF_MODE_' not in walk and 'axis_images(mode, u, ' not in walk
+    for line in ('for (int t = first; t < taps; t += step) {',
                  'for (int ky = 0; ky < o.ny; ++ky) {',
                  'if ((unsigned)ly >= (unsigned)g.Ay) continue;',
                  'for (int kx = 0; kx < o.nx; ++kx) {',

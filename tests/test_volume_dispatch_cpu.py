@@ -1,6 +1,6 @@
 """
 CPU guard of the volume matrix: the host mirror of the three-shift-axis family (tests/volume_dispatch.py) is held to the
-C++ it restates (volume.hip, api.hip, read as text), its index maps of the reconstruction modes to the oracle's pad and
+C++ it restates (volume.hip, modes.h, api.hip, read as text), its index maps of the reconstruction modes to the oracle's pad and
 fold, and the cases of tests/test_hip_volume_matrix.py to reaching every cell at 256 and at 304 compute units.  No GPU, no
 build.
 """
@@ -60,20 +60,28 @@ def test_mirrored_constants_and_rules_are_those_of_the_source():
             f'const long long lim = {hex(vd.LIM)}LL;',
             'const long long tiles = (hvox + kVolBlock - 1) / kVolBlock;',
             'return vox < lim && hvox < lim && avox * v.M * v.C < lim && tiles * v.N * (v.M > v.C ? v.M : v.C) < lim;',
-            # ---- the reconstruction modes: the index maps and the guards
-            'if (mode == TNMF_MODE_FULL) { const int u = j - l; return (u >= 0 && u < S) ? u : -1; }',
-            'if (j >= l) return j - l; return mode == TNMF_MODE_CIRCULAR ? S - l + j : l - j;',
-            'if (mode == TNMF_MODE_CIRCULAR) return u >= S - l ? u - (S - l) : -1;',
-            'if (mode == TNMF_MODE_REFLECT) return (u >= 1 && u <= l) ? l - u : -1;',
-            'q.S[i] = mode == TNMF_MODE_VALID ? v.H[i] : (mode == TNMF_MODE_FULL ? v.D[i] - v.A[i] + 1 : v.D[i]);',
-            'if (q.S[i] < 1) return TNMF_E_GEOM;',
-            'if (mode == TNMF_MODE_CIRCULAR && v.A[i] - 1 > q.S[i]) return TNMF_E_GEOM;',
-            'if (mode == TNMF_MODE_REFLECT && v.A[i] - 1 >= q.S[i]) return TNMF_E_GEOM;',
-            'const int jz[2] = {uz + q.A[0] - 1, vol_pad_dup(uz, q.S[0], q.A[0], mode)};',
+            # ---- the reconstruction modes: the index maps and the guards are those of modes.h (below)
+            'const int uz = pad_src(jz, q.S[0], q.A[0], mode), uy = pad_src(jy, q.S[1], q.A[1], mode), '
+            'ux = pad_src(jx, q.S[2], q.A[2], mode);',
+            'q.S[i] = mode_shift_len(mode, v.D[i], v.A[i]); if (!mode_axis_ok(mode, q.S[i], v.A[i])) return TNMF_E_GEOM;',
+            'const int jz[2] = {uz + q.A[0] - 1, pad_dup(uz, q.S[0], q.A[0], mode)};',
             # ---- k_vol_lateral
             'if (xc != T(0)) for (int m = 0; m < M; ++m) S += G[o0 + (size_t)m * vox];',
             'G[o] = inh * (gv - H[o]) + xc * (S - gv);'):
         assert line in vol, line
+    modes = _flat('modes.h')
+    for line in (
+            # ---- the per-axis rule of the modes, stated once: the index maps, the shift length, the limits
+            'if (mode == TNMF_MODE_FULL) { const int u = j - l; return (u >= 0 && u < S) ? u : -1; }',
+            'if (j >= l) return j - l; return mode == TNMF_MODE_CIRCULAR ? S - l + j : l - j;',
+            'if (mode == TNMF_MODE_CIRCULAR) return u >= S - l ? u - (S - l) : -1;',
+            'if (mode == TNMF_MODE_REFLECT) return (u >= 1 && u <= l) ? l - u : -1;',
+            'return mode == TNMF_MODE_VALID ? D + a - 1 : (mode == TNMF_MODE_FULL ? D - a + 1 : D);',
+            'return S >= 1 && (mode != TNMF_MODE_CIRCULAR || a - 1 <= S) && (mode != TNMF_MODE_REFLECT || a - 1 < S);'):
+        assert modes.count(line) == 1, line
+    for name in ('generic.hip', 'inhibit.hip', 'volume.hip', 'event_walk.h'):   # ... and nowhere else
+        text = _flat(name)
+        assert '#include "modes.h"' in text and not re.search(r'TNMF_MODE_(FULL|CIRCULAR|REFLECT)', text), name
     # the cap of the strided grids: pad / fold and the lateral terms
     assert vol.count(f'const size_t cap = (size_t)ctx->num_cu * {vd.GRID_PER_CU}; if (blocks > cap) blocks = cap;') == 2
     for line in (
@@ -97,13 +105,13 @@ def test_mirrored_constants_and_rules_are_those_of_the_source():
             'if (!r_is_valid) CHECK(vol_reconstruct(v, dtype, W, H_inout, Rs, s));',
             'if (is_vol(geom)) return vol_api_grad_W(ctx, geom, V, R_or_null, R_or_null != nullptr, W, H, neg, pos, stream);',
             # ---- vol_api_update_H_ex
-            'if (mode < TNMF_MODE_VALID || mode > TNMF_MODE_REFLECT) return TNMF_E_UNSUPPORTED; if (v.N == 0) return TNMF_OK;',
+            'if (!mode_known(mode)) return TNMF_E_UNSUPPORTED; if (v.N == 0) return TNMF_OK;',
             'if (inhibition < 0 || cross_inhibition < 0) return TNMF_E_GEOM;',
             'if (klen[i] < 1 || klen[i] > kMaxTaps || !(klen[i] & 1)) return TNMF_E_UNSUPPORTED;',
-            'const double xc = cross_inhibition > 0 && v.M > 1 ? cross_inhibition / (v.M - 1) : 0.0;',
+            'return cross_inhibition > 0 && M > 1 ? cross_inhibition / (M - 1) : 0.0;',
+            'const double xc = cross_weight(cross_inhibition, v.M);',
             'if (mode == TNMF_MODE_VALID && !lateral) return vol_api_update_H(ctx, geom, V, W, H_inout, R_scratch, 0, eps, sparsity, stream);',
-            'S[i] = mode == TNMF_MODE_VALID ? v.H[i] : (mode == TNMF_MODE_FULL ? v.D[i] - v.A[i] + 1 : v.D[i]); '
-            'if (S[i] < 1) return TNMF_E_GEOM;',
+            'S[i] = mode_shift_len(mode, v.D[i], v.A[i]); if (S[i] < 1) return TNMF_E_GEOM;',
             'CHECK(vol_lateral(ctx, dtype, (size_t)v.N, v.M, svox, G0, H_inout, inhibition, xc, s));'):
         assert line in api, line
     ex = api[api.index('int vol_api_update_H_ex('):api.index('int vol_api_run_schedule(')]

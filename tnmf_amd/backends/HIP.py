@@ -21,7 +21,7 @@ import torch
 from .. import _lib, sharding, transforms as _transforms
 from ..events_host import pursuit_loop
 from ..patches_host import fold_table
-from ._Backend import Backend, sliceNone
+from ._Backend import Backend, axis_images, sliceNone
 
 _DTYPES = {np.dtype('float32'): (torch.float32, 0), np.dtype('float64'): (torch.float64, 1)}
 
@@ -1096,7 +1096,7 @@ class HIP_Backend(Backend):
     def event_list(self, sample: torch.Tensor, plane: torch.Tensor, shift: torch.Tensor):
         """The lists tnmf_hip_events_render / _update take, built on the device for checked events (_check_events):
         (images [I, 4] int32 sorted by (sample, cell), cell_start [cells + 1] int32, events [K, 4] int32).  The images of
-        an event per shift axis are the header's table; a stable sort keeps, inside a cell, the order image combination,
+        an event per shift axis are ``_Backend.axis_images``; a stable sort keeps, inside a cell, the order image combination,
         then event."""
         k = len(self.atom_shape)
         K = sample.numel()
@@ -1104,15 +1104,8 @@ class HIP_Backend(Backend):
         with self._timed('event_list'):
             per_axis = []
             for i, (a, s) in enumerate(zip(self.atom_shape, self._transform_shape)):
-                u = shift[:, i]
-                if mode == 'valid':
-                    per_axis.append([(u, None)])
-                elif mode == 'circular':
-                    per_axis.append([(u + (a - 1), None), (u - (s - (a - 1)), u >= s - (a - 1))])
-                elif mode == 'reflect':
-                    per_axis.append([(u + (a - 1), None), ((a - 1) - u, (u >= 1) & (u <= a - 1))])
-                else:
-                    per_axis.append([(u + (a - 1), None)])
+                first, second, has_second = axis_images(mode, shift[:, i], a, s)
+                per_axis.append([(first, None)] + ([] if has_second is None else [(second, has_second)]))
             every = torch.arange(K, dtype=torch.int64, device=self._device)
             es, qs = [], []
             for combo in itertools.product(*per_axis):

@@ -105,6 +105,18 @@ def shift_shape(reconstruction_mode: str, sample_shape: Sequence[int], atom_shap
     raise ValueError(f'unknown reconstruction mode {reconstruction_mode!r}')
 
 
+def axis_images(mode: str, u, a: int, s: int):
+    """(first, second, has_second): the positions in the padded frame ``[D + A - 1]`` that copy the shifts ``u`` of one axis
+    (atom extent ``a``, shift extent ``s``) -- the table of include/tnmf_hip.h, "events".  ``has_second`` says where the
+    second one exists: a 'circular' shift in the wrap zone, a 'reflect' shift in the mirror zone; None for the modes that
+    have none.  Elementwise ``+ - >= <= &`` only: numpy arrays and torch tensors alike."""
+    if mode == 'circular':
+        return u + (a - 1), u - (s - (a - 1)), u >= s - (a - 1)
+    if mode == 'reflect':
+        return u + (a - 1), (a - 1) - u, (u >= 1) & (u <= a - 1)
+    return (u if mode == 'valid' else u + (a - 1)), None, None
+
+
 class Backend(abc.ABC):
     """Numerical back end of :class:`tnmf_amd.TransformInvariantNMF.TransformInvariantNMF`."""
 

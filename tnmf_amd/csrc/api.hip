@@ -19,6 +19,7 @@
 #include "fft.h"
 #include "generic.h"
 #include "mfma.h"
+#include "modes.h"
 #include "patches.h"
 #include "peaks.h"
 #include "split.h"
@@ -51,6 +52,24 @@ int to_geo(const tnmf_hip_geom *in, Geo *g) {
     g->Hx = g->Dx + g->Ax - 1;
     g->Hs = in->h_row_stride > 0 ? in->h_row_stride : g->Hx;
     if (g->Hs < g->Hx) return TNMF_E_GEOM;
+    return TNMF_OK;
+}
+
+// what the H update adds to its denominator (TransformInvariantNMF.py:227-230)
+inline double reg_of(double eps, double sparsity) { return eps + (sparsity > 0 ? sparsity : 0.0); }
+// the weight of the other atoms' gradients in the lateral term (TransformInvariantNMF.py:266-268)
+inline double cross_weight(double cross_inhibition, int M) {
+    return cross_inhibition > 0 && M > 1 ? cross_inhibition / (M - 1) : 0.0;
+}
+
+// the operation list of a schedule on N samples, whole, before anything runs: kinds and slices (the W update names no samples)
+int check_ops(const tnmf_hip_op *ops, int n_ops, int N) {
+    for (int i = 0; i < n_ops; ++i) {
+        if (ops[i].kind != TNMF_OP_UPDATE_H && ops[i].kind != TNMF_OP_GRAD_W && ops[i].kind != TNMF_OP_APPLY_W)
+            return TNMF_E_UNSUPPORTED;
+        if (ops[i].kind == TNMF_OP_APPLY_W) continue;
+        if (ops[i].n0 < 0 || ops[i].n1 < ops[i].n0 || ops[i].n1 > N) return TNMF_E_GEOM;
+    }
     return TNMF_OK;
 }
 
@@ -417,7 +436,7 @@ int vol_api_update_H(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const void *V
     }
     if (!r_is_valid) CHECK(vol_reconstruct(v, dtype, W, H_inout, Rs, s));
     CHECK(tap_objective(ctx, dtype, nullptr, eps, V, nullptr, Rs, (size_t)v.N, (size_t)v.C * vol_vox(v), s));
-    const double reg = eps + (sparsity > 0 ? sparsity : 0.0);   // TransformInvariantNMF.py:227-230
+    const double reg = reg_of(eps, sparsity);
     return vol_corr_W(v, dtype, V, Rs, W, H_inout, nullptr, nullptr, true, reg, s);
 }
 
@@ -427,7 +446,7 @@ int vol_api_update_H_ex(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, 
                         void *H_inout, void *R_scratch, double eps, double sparsity, double inhibition,
                         double cross_inhibition, const double *const kern[3], const int klen[3], void *stream) {
     VOL_ENTER(ctx, geom);
-    if (mode < TNMF_MODE_VALID || mode > TNMF_MODE_REFLECT) return TNMF_E_UNSUPPORTED;
+    if (!mode_known(mode)) return TNMF_E_UNSUPPORTED;
     if (v.N == 0) return TNMF_OK;
     if (!V || !W || !H_inout) return TNMF_E_NULL;
     if (inhibition < 0 || cross_inhibition < 0) return TNMF_E_GEOM;
@@ -437,13 +456,13 @@ int vol_api_update_H_ex(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, 
             if (!kern[i]) return TNMF_E_NULL;
             if (klen[i] < 1 || klen[i] > kMaxTaps || !(klen[i] & 1)) return TNMF_E_UNSUPPORTED;
         }
-    const double reg = eps + (sparsity > 0 ? sparsity : 0.0);   // TransformInvariantNMF.py:227-230
-    const double xc = cross_inhibition > 0 && v.M > 1 ? cross_inhibition / (v.M - 1) : 0.0;   // (:266-268)
+    const double reg = reg_of(eps, sparsity);
+    const double xc = cross_weight(cross_inhibition, v.M);
     if (mode == TNMF_MODE_VALID && !lateral)
         return vol_api_update_H(ctx, geom, V, W, H_inout, R_scratch, 0, eps, sparsity, stream);
     int S[3];
     for (int i = 0; i < 3; ++i) {
-        S[i] = mode == TNMF_MODE_VALID ? v.H[i] : (mode == TNMF_MODE_FULL ? v.D[i] - v.A[i] + 1 : v.D[i]);
+        S[i] = mode_shift_len(mode, v.D[i], v.A[i]);
         if (S[i] < 1) return TNMF_E_GEOM;
     }
     const size_t es = esize(dtype), planes = (size_t)v.N * v.M;
@@ -492,17 +511,11 @@ int vol_api_run_schedule(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const voi
     const size_t es = esize(dtype);
     const size_t vs = (size_t)v.C * vol_vox(v) * es, hs = (size_t)v.M * vol_hvox(v) * es;
     const size_t wn = (size_t)v.M * v.C * vol_avox(v);
+    CHECK(check_ops(ops, n_ops, v.N));
     int nmax = 0;
-    for (int i = 0; i < n_ops; ++i) {
-        // (kinds and ranges of the whole list before anything runs, as on one and two shift axes: a refused list leaves
-        // W, H and acc as they were; the W update names no samples)
-        if (ops[i].kind != TNMF_OP_UPDATE_H && ops[i].kind != TNMF_OP_GRAD_W && ops[i].kind != TNMF_OP_APPLY_W)
-            return TNMF_E_UNSUPPORTED;
-        if (ops[i].kind == TNMF_OP_APPLY_W) continue;
-        if (ops[i].n0 < 0 || ops[i].n1 < ops[i].n0 || ops[i].n1 > v.N) return TNMF_E_GEOM;
-        if (ops[i].n1 - ops[i].n0 > nmax) nmax = ops[i].n1 - ops[i].n0;
-    }
-    const double reg = eps + (sparsity > 0 ? sparsity : 0.0);   // TransformInvariantNMF.py:227-230
+    for (int i = 0; i < n_ops; ++i)
+        if (ops[i].kind != TNMF_OP_APPLY_W && ops[i].n1 - ops[i].n0 > nmax) nmax = ops[i].n1 - ops[i].n0;
+    const double reg = reg_of(eps, sparsity);
     // scratch for the largest slice: [R | energy words | partial sums of the W gradient], and one gradient behind it
     Vol vmax = v;
     vmax.N = nmax;
@@ -547,7 +560,7 @@ int vol_api_run_schedule(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const voi
 int vol_api_pad_fold(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, bool fold, const void *in, void *out,
                      void *stream) {
     VOL_ENTER(ctx, geom);
-    if (mode < TNMF_MODE_VALID || mode > TNMF_MODE_REFLECT) return TNMF_E_UNSUPPORTED;
+    if (!mode_known(mode)) return TNMF_E_UNSUPPORTED;
     if (v.N > 0 && (!in || !out)) return TNMF_E_NULL;
     return vol_pad_fold(ctx, v, dtype, mode, fold, in, out, s);
 }
@@ -1048,7 +1061,7 @@ int tnmf_hip_convolve_axis(tnmf_hip_ctx *ctx, int dtype, size_t rows, int len, s
 int tnmf_hip_pad_H(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *H, void *Hpad, void *stream) {
     if (is_vol(geom)) return vol_api_pad_fold(ctx, geom, mode, false, H, Hpad, stream);
     ENTER(ctx, geom);
-    if (mode < TNMF_MODE_VALID || mode > TNMF_MODE_REFLECT) return TNMF_E_UNSUPPORTED;
+    if (!mode_known(mode)) return TNMF_E_UNSUPPORTED;
     if (g.N > 0 && (!H || !Hpad)) return TNMF_E_NULL;
     if (g.Hs != g.Hx) return TNMF_E_STRIDE;
     return launch_pad_fold(ctx, g, dtype, mode, false, H, Hpad, s);
@@ -1057,7 +1070,7 @@ int tnmf_hip_pad_H(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const
 int tnmf_hip_fold_H(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *Gpad, void *G, void *stream) {
     if (is_vol(geom)) return vol_api_pad_fold(ctx, geom, mode, true, Gpad, G, stream);
     ENTER(ctx, geom);
-    if (mode < TNMF_MODE_VALID || mode > TNMF_MODE_REFLECT) return TNMF_E_UNSUPPORTED;
+    if (!mode_known(mode)) return TNMF_E_UNSUPPORTED;
     if (g.N > 0 && (!Gpad || !G)) return TNMF_E_NULL;
     return launch_pad_fold(ctx, g, dtype, mode, true, Gpad, G, s);
 }
@@ -1070,14 +1083,13 @@ static int update_H_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, c
                        double inhibition, double cross_inhibition, const double *kernel0, int len0,
                        const double *kernel1, int len1, const double *beta, void *stream) {
     ENTER(ctx, geom);
-    if (mode < TNMF_MODE_VALID || mode > TNMF_MODE_REFLECT) return TNMF_E_UNSUPPORTED;
+    if (!mode_known(mode)) return TNMF_E_UNSUPPORTED;
     if (g.N == 0) return TNMF_OK;
     if (!V || !W || !H_inout) return TNMF_E_NULL;
     const bool lateral = inhibition > 0 || cross_inhibition > 0;
     if (lateral && (!kernel0 || (geom->ndim == 2 && !kernel1))) return TNMF_E_NULL;
     if (inhibition < 0 || cross_inhibition < 0) return TNMF_E_GEOM;
-    double reg = eps;
-    if (sparsity > 0) reg += sparsity;  // TransformInvariantNMF.py:227-230
+    const double reg = reg_of(eps, sparsity);
     const size_t es = esize(dtype);
     void *Rs = R_scratch;
     if (!Rs) {
@@ -1090,7 +1102,7 @@ static int update_H_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, c
     const double one = 1.0;
     const double *ky = geom->ndim == 2 ? kernel0 : &one, *kx = geom->ndim == 2 ? kernel1 : kernel0;
     const int ly = geom->ndim == 2 ? len0 : 1, lx = geom->ndim == 2 ? len1 : len0;
-    const double xc = cross_inhibition > 0 && g.M > 1 ? cross_inhibition / (g.M - 1) : 0.0;   // (:266-268)
+    const double xc = cross_weight(cross_inhibition, g.M);
 
     if (mode == TNMF_MODE_VALID) {
         const size_t nE = align_up((size_t)g.N * g.M * g.Hy * g.Hs * es, 256);
@@ -1123,8 +1135,7 @@ static int update_H_2d(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, c
     // reconstruction modes: a 'valid' half step on the padded activations, folded back (adjoint of the pad) inside the
     // update kernel.  H is C-contiguous with the shift shape of the mode.
     if (g.Hs != g.Hx) return TNMF_E_STRIDE;
-    const int Sy = geom->ndim == 1 ? 1 : (mode == TNMF_MODE_FULL ? g.Dy - g.Ay + 1 : g.Dy);
-    const int Sx = mode == TNMF_MODE_FULL ? g.Dx - g.Ax + 1 : g.Dx;
+    const int Sy = geom->ndim == 1 ? 1 : mode_shift_len(mode, g.Dy, g.Ay), Sx = mode_shift_len(mode, g.Dx, g.Ax);
     if (Sy < 1 || Sx < 1) return TNMF_E_GEOM;
     const size_t nP = align_up((size_t)g.N * g.M * g.Hy * g.Hx * es, 256);
     const size_t nE = lateral ? align_up((size_t)g.N * g.M * Sy * Sx * es, 256) : 0;
@@ -1249,15 +1260,7 @@ int tnmf_hip_run_schedule(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const vo
     const size_t es = esize(dtype);
     const size_t vs = (size_t)g.C * g.Dy * g.Dx * es, hs = (size_t)g.M * g.Hy * g.Hs * es;
     const size_t wn = (size_t)g.M * g.C * g.Ay * g.Ax;
-    // scratch for the largest slice of the list: R of the slice (unless the caller brought one), split-K partials, and the
-    // gradient of one batch behind them
-    for (int i = 0; i < n_ops; ++i) {
-        // (checked for the whole list before anything runs: the persistent kernel walks it on the device)
-        if (ops[i].kind != TNMF_OP_UPDATE_H && ops[i].kind != TNMF_OP_GRAD_W && ops[i].kind != TNMF_OP_APPLY_W)
-            return TNMF_E_UNSUPPORTED;
-        if (ops[i].kind == TNMF_OP_APPLY_W) continue;
-        if (ops[i].n0 < 0 || ops[i].n1 < ops[i].n0 || ops[i].n1 > g.N) return TNMF_E_GEOM;
-    }
+    CHECK(check_ops(ops, n_ops, g.N));
     // Consecutive H half steps commute when their slices are disjoint -- the H update of a sample reads that sample and W
     // only (NumPy.py:93-120), and W does not change between them -- so a RUN of them is executed as the H half step of the
     // union: the slices sorted and joined where they touch.  GSG-MU / GSAG-MU (TransformInvariantNMF.py:474-479,493-504: H for
@@ -1296,8 +1299,7 @@ int tnmf_hip_run_schedule(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const vo
     int nmax = 1;
     for (int i = 0; i < n_ops; ++i)
         if (ops[i].kind != TNMF_OP_APPLY_W && ops[i].n1 - ops[i].n0 > nmax) nmax = ops[i].n1 - ops[i].n0;
-    double reg = eps;
-    if (sparsity > 0) reg += sparsity;  // TransformInvariantNMF.py:227-230
+    const double reg = reg_of(eps, sparsity);
     // A whole problem that is tiny (BASELINE config 1): every kernel would run for a few microseconds and the list would be
     // launch latency -- the persistent schedule kernel walks it in ONE launch.  (Small batches of a LARGE problem stay on
     // the per-operation path below: measured on the reference's mini-batch geometry, 768 x 1 x 32 x 32 with batch_size 3,
@@ -1305,7 +1307,6 @@ int tnmf_hip_run_schedule(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, const vo
     // the launches they replace: 28.5 ms per ASG epoch against 26.7 ms.)
     // (Round 4 built an XCD-local flavour of that kernel for exactly that case -- the workgroups of ONE XCD, barriers without
     // the L2 write-back: 22.3 ms per ASG epoch against 12.0 on the per-operation path below, profiles/r04_xcd_local_schedule_kernel.txt.)
-    (void)nmax;
     const bool tiny = (size_t)g.N * g.M * g.Hy * g.Hx <= ((size_t)1 << 18);
     if (n_ops > 0 && tiny && ctx->persistent != 0 && (ctx->path == TNMF_PATH_AUTO || ctx->path == TNMF_PATH_GENERIC) &&
         generic_schedule_fits(ctx, g, dtype)) {
@@ -1563,16 +1564,11 @@ static int events_geo(const tnmf_hip_geom *geom, EventGeo *g) {
     return TNMF_OK;
 }
 
-// the shift shape of a reconstruction mode, checked against the limits of "reconstruction modes" above, per axis
+// the shift shape of a reconstruction mode, checked against the limits of modes.h, per axis
 static int events_shift_shape(const EventGeo &g, int mode, int S[2]) {
-    if (mode < TNMF_MODE_VALID || mode > TNMF_MODE_REFLECT) return TNMF_E_GEOM;
-    const int D[2] = {g.Dy, g.Dx}, A[2] = {g.Ay, g.Ax};
-    for (int i = 0; i < 2; ++i) {
-        S[i] = mode == TNMF_MODE_VALID ? D[i] + A[i] - 1 : mode == TNMF_MODE_FULL ? D[i] - A[i] + 1 : D[i];
-        if (S[i] < 1 || (mode == TNMF_MODE_CIRCULAR && A[i] - 1 > S[i]) || (mode == TNMF_MODE_REFLECT && A[i] - 1 >= S[i]))
-            return TNMF_E_GEOM;
-    }
-    return TNMF_OK;
+    if (!mode_known(mode)) return TNMF_E_GEOM;
+    S[0] = mode_shift_len(mode, g.Dy, g.Ay), S[1] = mode_shift_len(mode, g.Dx, g.Ax);
+    return mode_axis_ok(mode, S[0], g.Ay) && mode_axis_ok(mode, S[1], g.Ax) ? TNMF_OK : TNMF_E_GEOM;
 }
 
 // the preamble of the events entry points that take a mode: the arguments that must be there, the geometry, the shift shape
@@ -1612,7 +1608,7 @@ int tnmf_hip_events_update(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mod
     if (n_events > 0 && f.g.N > 0 && (!W_eff || !events || !strength_inout || !V || !R)) return TNMF_E_NULL;
     TNMF_HIP_TRY(hipSetDevice(ctx->device));
     return events_update(ctx, f, geom->dtype, W_eff, events, strength_inout, n_events, V, R,
-                         eps + (sparsity > 0 ? sparsity : 0.), static_cast<hipStream_t>(stream));
+                         reg_of(eps, sparsity), static_cast<hipStream_t>(stream));
 }
 
 int tnmf_hip_events_gain(tnmf_hip_ctx *ctx, const tnmf_hip_geom *geom, int mode, const void *W_eff, const int *events,

@@ -1,29 +1,12 @@
-// The occurrence of an event on the device, shared by the kernels of events.hip and pursuit.hip: its images per axis, the
-// walk over the taps of every image clipped to the sample, the value phi of the occurrence at a pixel, and the wave's sum.
-// For landscape.hip and alternatives.hip also the residual of the list without a row, the sums of several values of a wave
-// at once and the test for an occurrence that is one image wholly inside the sample.
+// The occurrence of an event on the device, shared by the kernels of events.hip and pursuit.hip: its images (per axis:
+// axis_images of modes.h), the walk over the taps of every image clipped to the sample, the value phi of the occurrence at a
+// pixel, and the wave's sum.  For landscape.hip and alternatives.hip also the residual of the list without a row and the sums
+// of several values of a wave at once (the test for one image wholly inside the sample is axis_whole of modes.h).
 // Device code only; everything is inlined into the kernel that calls it, the lambda of for_each_tap included.
 #pragma once
 
 #include "events.h"
-
-// the images of the shift u on one axis (atom extent a, shift extent S): their padded positions, at most two
-__device__ __forceinline__ int axis_images(int mode, int u, int a, int S, int q[2]) {
-    if (mode == TNMF_MODE_VALID) {
-        q[0] = u;
-        return 1;
-    }
-    q[0] = u + a - 1;
-    if (mode == TNMF_MODE_CIRCULAR && u >= S - (a - 1)) {
-        q[1] = u - (S - (a - 1));
-        return 2;
-    }
-    if (mode == TNMF_MODE_REFLECT && u >= 1 && u <= a - 1) {
-        q[1] = (a - 1) - u;
-        return 2;
-    }
-    return 1;
-}
+#include "modes.h"
 
 // the images of the shift (uy, ux) of the mode with shift shape (Sy, Sx): ny * nx of them, at (qy[iy], qx[ix])
 struct Occurrence {
@@ -127,13 +110,4 @@ __device__ __forceinline__ bool wave_sum_many(double (&v)[N], int lane, int *whi
     }
     *which = s;
     return own;
-}
-
-// the shift u on one axis is in range and its occurrence is one image wholly inside the sample
-__device__ __forceinline__ bool axis_whole(int mode, int u, int a, int S, int D) {
-    if ((unsigned)u >= (unsigned)S) return false;
-    int q[2];
-    if (axis_images(mode, u, a, S, q) != 1) return false;
-    const int o = q[0] - (a - 1);
-    return o >= 0 && o + a <= D;
 }

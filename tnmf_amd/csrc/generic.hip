@@ -7,6 +7,7 @@
 //   corr_W      :101-119   O[n,m,u,v] = sum_c sum_{a,b} W[m,c,a,b] * X[n,c,u+a-(Ay-1),v+b-(Ax-1)]      X in {V, R}
 //   corr_H      :77-90     G[m,c,a,b] = sum_n sum_{y,x} H[n,m,y+Ay-1-a,x+Ax-1-b] * X[n,c,y,x]          X in {V, R}
 #include "generic.h"
+#include "modes.h"
 #include "rowsum.h"
 
 namespace {
@@ -989,28 +990,9 @@ int launch_convolve_axis(const tnmf_hip_ctx *ctx, int dtype, const void *in, voi
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// reconstruction modes: pad the activations / fold the gradient (reference: backends/_PyTorchBackend.py:42-52)
+// reconstruction modes: pad the activations / fold the gradient (the per-axis rule: modes.h)
 // ------------------------------------------------------------------------------------------------------------
 namespace {
-
-// activation index copied to padded position j of one axis (-1: a zero); S = activation length, a = atom length
-__device__ __forceinline__ int pad_src(int j, int S, int a, int mode) {
-    const int l = a - 1;
-    if (mode == TNMF_MODE_FULL) {
-        const int u = j - l;
-        return (u >= 0 && u < S) ? u : -1;
-    }
-    if (j >= l) return j - l;
-    return mode == TNMF_MODE_CIRCULAR ? S - l + j : l - j;   // wrap / mirror (without repeating the edge)
-}
-
-// second padded position (besides u + a - 1) that copies activation u, or -1
-__device__ __forceinline__ int pad_dup(int u, int S, int a, int mode) {
-    const int l = a - 1;
-    if (mode == TNMF_MODE_CIRCULAR) return u >= S - l ? u - (S - l) : -1;
-    if (mode == TNMF_MODE_REFLECT) return (u >= 1 && u <= l) ? l - u : -1;
-    return -1;
-}
 
 template <typename T>
 __global__ void k_pad_H(size_t rows, int Sy, int Sx, int Ay, int Ax, int Py, int Px, int mode,
@@ -1052,21 +1034,10 @@ __global__ void k_fold_H(size_t rows, int Sy, int Sx, int Ay, int Ax, int Py, in
 
 }  // namespace
 
-// shift length of one axis for a mode (reference: backends/_Backend.py:60-73)
-static inline int mode_shift(int d, int a, int mode) {
-    return mode == TNMF_MODE_VALID ? d + a - 1 : (mode == TNMF_MODE_FULL ? d - a + 1 : d);
-}
-
 int launch_pad_fold(const tnmf_hip_ctx *ctx, const Geo &g, int dtype, int mode, bool fold, const void *in, void *out,
                     hipStream_t s) {
-    const int Sy = g.Dy == 1 && g.Ay == 1 ? 1 : mode_shift(g.Dy, g.Ay, mode), Sx = mode_shift(g.Dx, g.Ax, mode);
-    if (Sy < 1 || Sx < 1) return TNMF_E_GEOM;
-    // 'circular' wraps at most once: a pad of A-1 needs A-1 <= S (torch's circular pad raises otherwise).  'full' pads
-    // zeros (F.pad mode='constant'): any atom up to the sample's length, however short that leaves the activations
-    if (mode == TNMF_MODE_CIRCULAR && (g.Ay - 1 > Sy || g.Ax - 1 > Sx)) return TNMF_E_GEOM;
-    // 'reflect' mirrors without repeating the edge: a pad of A-1 needs A-1 < S (torch's reflect pad raises otherwise,
-    // _PyTorchBackend.py:42-52 / torch.nn.functional.pad); pad == S would read one element past the activation row
-    if (mode == TNMF_MODE_REFLECT && (g.Ay - 1 >= Sy || g.Ax - 1 >= Sx)) return TNMF_E_GEOM;
+    const int Sy = mode_shift_len(mode, g.Dy, g.Ay), Sx = mode_shift_len(mode, g.Dx, g.Ax);
+    if (!mode_axis_ok(mode, Sy, g.Ay) || !mode_axis_ok(mode, Sx, g.Ax)) return TNMF_E_GEOM;
     const size_t rows = (size_t)g.N * g.M;
     const size_t total = rows * (fold ? (size_t)Sy * Sx : (size_t)g.Hy * g.Hx);
     if (total == 0) return TNMF_OK;

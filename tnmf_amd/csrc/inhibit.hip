@@ -11,6 +11,7 @@
 // window along the convolution axis: one LDS read per 8 / 4 multiply-adds).  With cross inhibition the G of every atom
 // is parked in E on the way and a second walk over the atoms (its reads hit in L2) turns it into E.
 #include "generic.h"
+#include "modes.h"
 
 namespace {
 
@@ -265,15 +266,6 @@ __global__ void k_mu_update_extra(T *__restrict__ H, const T *__restrict__ neg, 
     }
 }
 
-// activation index copied to padded position j of one axis (-1: a zero) and the second padded copy of activation u
-// (generic.hip has the same tables for tnmf_hip_pad_H / tnmf_hip_fold_H; reference: backends/_PyTorchBackend.py:42-52)
-__device__ __forceinline__ int dup_of(int u, int S, int a, int mode) {
-    const int l = a - 1;
-    if (mode == TNMF_MODE_CIRCULAR) return u >= S - l ? u - (S - l) : -1;
-    if (mode == TNMF_MODE_REFLECT) return (u >= 1 && u <= l) ? l - u : -1;
-    return -1;
-}
-
 // reconstruction modes: the gradient with respect to an activation is the sum of the gradients at the padded positions
 // that copy it (fold = adjoint of the pad), then the multiplicative update -- in one pass:
 //   H[u] = H[u] * sum_copies negp / (sum_copies posp + E[u] + reg)
@@ -287,8 +279,8 @@ __global__ void k_fold_update(size_t rows, int Sy, int Sx, int Ay, int Ax, int P
         const size_t rest = e / Sx;
         const int uy = (int)(rest % Sy);
         const size_t r = rest / Sy;
-        const int jy[2] = {Py == 1 ? 0 : uy + Ay - 1, Py == 1 ? -1 : dup_of(uy, Sy, Ay, mode)};
-        const int jx[2] = {ux + Ax - 1, dup_of(ux, Sx, Ax, mode)};
+        const int jy[2] = {Py == 1 ? 0 : uy + Ay - 1, Py == 1 ? -1 : pad_dup(uy, Sy, Ay, mode)};
+        const int jx[2] = {ux + Ax - 1, pad_dup(ux, Sx, Ax, mode)};
         T an = T(0), ap = T(0);
 #pragma unroll
         for (int a = 0; a < 2; ++a)

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "volume.h"
+#include "modes.h"
 
 namespace {
 
@@ -163,23 +164,7 @@ __global__ void k_vol_corr_H_finalize(int n, int P, const double *__restrict__ p
     pos[i] = (T)b;
 }
 
-// ---- reconstruction modes (backends/_PyTorchBackend.py:42-52): the same per-axis maps as the 1-D / 2-D kernels of
-// generic.hip.  S = activation length of the axis in this mode, a = atom length; the padded length is always D + a - 1.
-__device__ __forceinline__ int vol_pad_src(int j, int S, int a, int mode) {   // activation copied to padded position j, or -1
-    const int l = a - 1;
-    if (mode == TNMF_MODE_FULL) {
-        const int u = j - l;
-        return (u >= 0 && u < S) ? u : -1;
-    }
-    if (j >= l) return j - l;
-    return mode == TNMF_MODE_CIRCULAR ? S - l + j : l - j;
-}
-__device__ __forceinline__ int vol_pad_dup(int u, int S, int a, int mode) {   // second padded copy of activation u, or -1
-    const int l = a - 1;
-    if (mode == TNMF_MODE_CIRCULAR) return u >= S - l ? u - (S - l) : -1;
-    if (mode == TNMF_MODE_REFLECT) return (u >= 1 && u <= l) ? l - u : -1;
-    return -1;
-}
+// ---- reconstruction modes: the per-axis maps of modes.h on three axes (S = activation lengths, P = padded lengths)
 
 struct Vol3 {
     int S[3], A[3], P[3];
@@ -192,8 +177,8 @@ __global__ void k_vol_pad(size_t planes, Vol3 q, int mode, const T *__restrict__
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
         const size_t r = e / pvox, w = e - r * pvox;
         const int jx = (int)(w % q.P[2]), jy = (int)((w / q.P[2]) % q.P[1]), jz = (int)(w / ((size_t)q.P[2] * q.P[1]));
-        const int uz = vol_pad_src(jz, q.S[0], q.A[0], mode), uy = vol_pad_src(jy, q.S[1], q.A[1], mode),
-                  ux = vol_pad_src(jx, q.S[2], q.A[2], mode);
+        const int uz = pad_src(jz, q.S[0], q.A[0], mode), uy = pad_src(jy, q.S[1], q.A[1], mode),
+                  ux = pad_src(jx, q.S[2], q.A[2], mode);
         Hp[e] = (uz >= 0 && uy >= 0 && ux >= 0) ? H[((r * q.S[0] + uz) * q.S[1] + uy) * q.S[2] + ux] : T(0);
     }
 }
@@ -205,9 +190,9 @@ __global__ void k_vol_fold(size_t planes, Vol3 q, int mode, const T *__restrict_
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
         const size_t r = e / svox, w = e - r * svox;
         const int ux = (int)(w % q.S[2]), uy = (int)((w / q.S[2]) % q.S[1]), uz = (int)(w / ((size_t)q.S[2] * q.S[1]));
-        const int jz[2] = {uz + q.A[0] - 1, vol_pad_dup(uz, q.S[0], q.A[0], mode)};
-        const int jy[2] = {uy + q.A[1] - 1, vol_pad_dup(uy, q.S[1], q.A[1], mode)};
-        const int jx[2] = {ux + q.A[2] - 1, vol_pad_dup(ux, q.S[2], q.A[2], mode)};
+        const int jz[2] = {uz + q.A[0] - 1, pad_dup(uz, q.S[0], q.A[0], mode)};
+        const int jy[2] = {uy + q.A[1] - 1, pad_dup(uy, q.S[1], q.A[1], mode)};
+        const int jx[2] = {ux + q.A[2] - 1, pad_dup(ux, q.S[2], q.A[2], mode)};
         T acc = T(0);
 #pragma unroll
         for (int a = 0; a < 2; ++a)
@@ -315,12 +300,8 @@ int vol_pad_fold(const tnmf_hip_ctx *ctx, const Vol &v, int dtype, int mode, boo
     for (int i = 0; i < 3; ++i) {
         q.A[i] = v.A[i];
         q.P[i] = v.H[i];
-        q.S[i] = mode == TNMF_MODE_VALID ? v.H[i] : (mode == TNMF_MODE_FULL ? v.D[i] - v.A[i] + 1 : v.D[i]);
-        if (q.S[i] < 1) return TNMF_E_GEOM;
-        // (the same limits as launch_pad_fold of generic.hip: 'circular' wraps at most once, 'reflect' mirrors without
-        // the edge, 'full' pads zeros and has none)
-        if (mode == TNMF_MODE_CIRCULAR && v.A[i] - 1 > q.S[i]) return TNMF_E_GEOM;
-        if (mode == TNMF_MODE_REFLECT && v.A[i] - 1 >= q.S[i]) return TNMF_E_GEOM;
+        q.S[i] = mode_shift_len(mode, v.D[i], v.A[i]);
+        if (!mode_axis_ok(mode, q.S[i], v.A[i])) return TNMF_E_GEOM;
     }
     const size_t planes = (size_t)v.N * v.M;
     const size_t total = planes * (fold ? (size_t)q.S[0] * q.S[1] * q.S[2] : (size_t)q.P[0] * q.P[1] * q.P[2]);

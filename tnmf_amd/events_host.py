@@ -13,7 +13,7 @@ from typing import Callable, Optional, Tuple
 import numpy as np
 
 from . import transforms as _transforms
-from .backends._Backend import shift_shape as _shift_shape
+from .backends._Backend import axis_images as _axis_images, shift_shape as _shift_shape
 
 
 def _shapes(W: np.ndarray, sample_shape: Tuple[int, ...], mode: str):
@@ -64,22 +64,17 @@ def find_peaks_numpy(H: np.ndarray, threshold: float, radius: Tuple[int, ...], g
 
 def event_images(shift: np.ndarray, atom_shape: Tuple[int, ...], shift_shape: Tuple[int, ...], mode: str):
     """(event [I], q [I, k]): the images of the events with shifts ``shift[K, k]`` in the padded activation frame
-    ``[D + A - 1]`` of a reconstruction mode -- the table of include/tnmf_hip.h, "events": per axis one position, and a
-    second one for a 'circular' shift in the wrap zone or a 'reflect' shift in the mirror zone; over the axes their
-    Cartesian product."""
+    ``[D + A - 1]`` of a reconstruction mode: per axis the one or two positions of ``_Backend.axis_images``; over the axes
+    their Cartesian product."""
     shift = np.asarray(shift, dtype=np.int64).reshape(-1, len(atom_shape))
     event, q = np.arange(len(shift), dtype=np.int64), np.empty((len(shift), 0), dtype=np.int64)
     for i, (a, s) in enumerate(zip(atom_shape, shift_shape)):
-        u = shift[event, i]
-        first = u if mode == 'valid' else u + (a - 1)
-        if mode == 'circular':
-            more, second = np.flatnonzero(u >= s - (a - 1)), u - (s - (a - 1))
-        elif mode == 'reflect':
-            more, second = np.flatnonzero((u >= 1) & (u <= a - 1)), (a - 1) - u
-        else:
-            more, second = np.zeros(0, dtype=np.int64), u
-        q = np.concatenate([np.column_stack([q, first]), np.column_stack([q[more], second[more]])])
-        event = np.concatenate([event, event[more]])
+        first, second, has_second = _axis_images(mode, shift[event, i], a, s)
+        q = np.column_stack([q, first])
+        if has_second is not None:
+            more = np.flatnonzero(has_second)
+            q = np.concatenate([q, np.column_stack([q[more, :-1], second[more]])])
+            event = np.concatenate([event, event[more]])
     return event, q
 
 
@@ -612,13 +607,11 @@ def pursuit_numpy(W: np.ndarray, sample_shape: Tuple[int, ...], n_samples: int, 
             window = pad[(slice(None), slice(None)) + tuple(slice(jj, jj + q) for jj, q in zip(j, Q))]
             G += np.einsum('pc,nc...->np...', W64[(slice(None), slice(None)) + j], window)
         for i, (a, s) in enumerate(zip(A, S)):      # the fold of the mode, axis by axis
-            u = np.arange(s)
-            out = np.take(G, u if mode == 'valid' else u + (a - 1), axis=2 + i)
-            if mode in ('circular', 'reflect'):
-                more = np.flatnonzero(u >= s - (a - 1)) if mode == 'circular' else np.flatnonzero((u >= 1) & (u <= a - 1))
-                second = more - (s - (a - 1)) if mode == 'circular' else (a - 1) - more
-                where = (slice(None),) * (2 + i) + (more,)
-                out[where] += np.take(G, second, axis=2 + i)
+            first, second, has_second = _axis_images(mode, np.arange(s), a, s)
+            out = np.take(G, first, axis=2 + i)
+            if has_second is not None:
+                more = np.flatnonzero(has_second)
+                out[(slice(None),) * (2 + i) + (more,)] += np.take(G, second[more], axis=2 + i)
             G = out
         with np.errstate(divide='ignore', invalid='ignore'):
             g = np.where((G > 0) & (b > 0), G * G / (2. * b), 0.)
